@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: m-modes/sec through MModeTransform + DirtyMapMaker.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 One *step* = one sidereal day of synthetic CHIME-pathfinder-shaped data at BASELINE.json's metric configuration
 (128 feeds -> 379 stacked baselines, 256 frequencies, 1024 RA samples, lmax = mmax = 512; cfg 3 of SURVEY.md 8d)
@@ -25,6 +25,11 @@ frequencies ARE the resident pool (no aliasing), value = (mmax+1) / T_max.  ``--
 256 frequencies of a 256*N-frequency job, value = N * (mmax+1) / T_max.  After the timed region the rank-local Maps are
 all-gathered (``parallel.allgather_map``, the north star's single RCCL collective) and its time is reported.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  ``--full`` adds every secondary measurement
+and check: the CPU baseline, the stages and the Dirty kernel each alone, the extras (complex64 B, the dense makers,
+host-streamed B, many days per read of B) and, for N > 1, the rank census and the all-gather.  ``--dump-outputs DIR``
+writes the map of the last timed step (rank 0's frequencies) as DIR/map.npy, for comparing two builds output for output.
+
 Prints ONE compact JSON line (< 4 KB) LAST on rank 0's stdout; the full record goes to bench_extra.json beside this file.
 """
 
@@ -46,6 +51,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 EXTRA_FILE = "bench_extra.json"
 LINE_LIMIT = 4096  # the driver keeps about 8 KB of stdout: the result line must fit with room to spare
+DUMP_BYTES = 64 << 20  # --dump-outputs: an output larger than this is written as a sample
+DUMP_SAMPLE = 1 << 22  # values of that sample (float64: 32 MiB)
 
 
 def _sig(x, n=6):
@@ -182,6 +189,23 @@ def emit(out):
     print(compact_line(out), flush=True)
 
 
+def dump_outputs(path, name, t):
+    """``--dump-outputs``: the device tensor ``t`` as ``path/<name>.npy`` in float64.  One of more than DUMP_BYTES is
+    written as a fixed sample: the flattened array cut into DUMP_SAMPLE equal strides, one value of each at an offset
+    drawn from a generator of fixed seed, so that every run with the same arguments writes the same elements."""
+    import torch
+
+    flat = t.reshape(-1)
+    if flat.numel() * 8 > DUMP_BYTES:
+        stride = flat.numel() // DUMP_SAMPLE
+        idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, DUMP_SAMPLE)
+        out = flat[torch.from_numpy(idx).to(flat.device)]
+    else:
+        out = t
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), out.to(torch.float64).cpu().numpy())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -197,15 +221,22 @@ def parse():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"], help="N > 1: 'strong' (default) splits the metric's 256 frequencies over the ranks -- the job BASELINE.json names; 'weak' gives every rank its own 256")
     ap.add_argument("--b-dtype", default="complex128", choices=["complex128", "complex64"])
     ap.add_argument("--pool-freqs", type=int, default=0, help="frequencies' worth of distinct B tiles resident (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline: budget of timed windows (the process arm gets 3 windows of 0.22 x this)")
+    ap.add_argument("--full", action="store_true", help="also every secondary measurement and check (CPU baseline, stages and Dirty kernel alone, extras, rank census and all-gather); a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the map of the last timed step as DIR/map.npy (float64; a map over 64 MiB as a fixed seeded sample of 2^22 values)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline (--full): budget of timed windows (the process arm gets 3 windows of 0.22 x this)")
     ap.add_argument("--no-overlap", action="store_true", help="A/B switch: alm2map on the caller's stream between the slabs' solves (DirtyMapMaker.overlap_sht = False) instead of beside them")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements")
-    ap.add_argument("--extra-resident", action="store_true", help="secondary measurements: also the labelled multi-day modes of ML / Wiener (beam Gram products / singular bases resident beside B); off by default")
-    ap.add_argument("--no-allgather", action="store_true")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the secondary measurements")
+    ap.add_argument("--extra-resident", action="store_true", help="secondary measurements (--full): also the labelled multi-day modes of ML / Wiener (beam Gram products / singular bases resident beside B); off by default")
+    ap.add_argument("--no-allgather", action="store_true", help="--full without the all-gather of the maps (N > 1)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo + --same-device: rehearse the N>1 code path on a one-GPU box")
     ap.add_argument("--same-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # (the ranks of N > 1 run in this file's directory)
+    return args
 
 
 def _cpu_worker(rank, barrier, queue, seed, npairs, nra, lmax, ms, repeats, window):
@@ -693,6 +724,8 @@ def dense_day(args, kind):
     _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 0))
     c1 = {k: counter(k) for k in c0}
     assert eng.fills == fills_before or args.warmup == 0, "B was generated inside the timed region"
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, "map", out_map.map._dev)
 
     day_s = elapsed / args.steps
     scale = nfreq_cfg / nfreq  # a frequency sample is scaled to the config's day (frequencies are independent)
@@ -917,7 +950,7 @@ def launch_ranks(args):
     if ndev < n and not args.same_device:
         raise SystemExit(f"bench.py --gpus {n}: only {ndev} GPU(s) visible (one rank per GPU over RCCL; --backend gloo --same-device rehearses the N > 1 code path on one GPU)")
     cpu = None
-    if not args.no_cpu_baseline and args.maker == "dirty":
+    if args.full and not args.no_cpu_baseline and args.maker == "dirty":
         from draco_amd import workloads as _wl
 
         cpu = cpu_baseline(_wl.CONFIGS[args.config], args.cpu_seconds)
@@ -925,8 +958,9 @@ def launch_ranks(args):
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), DMM_BENCH_LAUNCHER="1")
+    dump = ["--dump-outputs", args.dump_outputs] if args.dump_outputs else []  # (absolute: the last one given is what the ranks use)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+           "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:], *dump]
     proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, text=True)
     line = None
     for ln in proc.stdout:
@@ -971,7 +1005,7 @@ def main():
         # are exactly the resident pool.  N = 1: both forms are the same job.
         args.scaling = "strong" if world > 1 else "weak"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from draco_amd import workloads as _wl  # (the oracle is imported inside cpu_baseline only)
 
         if args.maker == "dirty":
@@ -1003,7 +1037,7 @@ def main():
         return float(t.item())
 
     ranks_rec = None
-    if world > 1:
+    if world > 1 and args.full:
         # who is really there: every rank contributes (rank, local device index) through the SAME kind of collective the
         # map gather uses (`all_gather_into_tensor`: RCCL under nccl), so the record says how many ranks RCCL saw
         mine = torch.tensor([rank, torch.cuda.current_device()], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
@@ -1038,9 +1072,10 @@ def main():
 
     for _ in range(max(args.warmup, 1) if args.steps else args.warmup):
         job.step()  # (the first pass fills the pool: at least one untimed pass so that B is resident when the clock starts)
-    # reference points outside the timed region: the stages each alone on the GPU
-    alone_ms, _ = job.timed_launches(job.to_alm)
-    stage_ms = job.stage_alone_ms()
+    if args.full:
+        # reference points outside the timed region: the stages each alone on the GPU
+        alone_ms, _ = job.timed_launches(job.to_alm)
+        stage_ms = job.stage_alone_ms()
     fills_before = job.dm._get_engine().fills
     eng = job.dm._get_engine()
     eng.launch_events = []
@@ -1074,6 +1109,8 @@ def main():
     # a retry of the caching allocator inside the timed region = the GPU idled while torch freed and re-allocated its
     # cache (what unbounded host run-ahead did to round 2's 20-step line): such a number is not the product's
     assert allocator["num_alloc_retries"] == 0 and allocator["num_ooms"] == 0, f"caching allocator retried inside the timed region: {allocator}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "map", out_map.map._dev)
     if world > 1:
         elapsed = allreduce_max(elapsed)
     launch_ms = [a.elapsed_time(b) for a, b, _, _ in ev]
@@ -1092,7 +1129,7 @@ def main():
     # failure: N x 6.4 GB next to everything else) and the ranks AGREE on going ahead with one all-reduce, so that no
     # rank enters a collective the others skip, (3) what fails after that is recorded and agreed on the same way.
     gather = None
-    if world > 1 and not args.no_allgather:
+    if world > 1 and args.full and not args.no_allgather:
         if rank == 0:
             print("headline before the all-gather measurement: " + json.dumps({"value": value, "ms_per_step": ms_per_step, "n_gpus": world, "steps": args.steps}), file=sys.stderr, flush=True)
 
@@ -1170,11 +1207,6 @@ def main():
             "parallelism": f"freq-sharded x{world}, {args.scaling} scaling (no collective in the timed region)",
             "alm2map": ("caller's stream, per solved slab, between the slabs' solves" if (args.no_overlap or args.b_dtype == "complex64") else "side stream, per solved slab, beside the next slab's solves") + " (BaseMapMaker.process; default by B storage type, DirtyMapMaker.overlap_sht)",
         },
-        # SURVEY 8d asks for the stage times next to the metric; each measured alone on the GPU after warmup (in the
-        # step the SHT runs beside the solves).  value_to_alm = (mmax+1) / (T_fft + T_solve): the metric with T ending
-        # at "a_lm of all (m,f) resident", i.e. without DirtyMapMaker's final alm2map
-        "stages_alone_ms": stage_ms,
-        "value_to_alm": scale * (lmax + 1) / ((stage_ms["T_fft"] + stage_ms["T_solve"]) * 1e-3),
         "roofline": {
             "kernel": "k_dirty (a = B^H N^-1 v, batched over (m,f))",
             "bound": "hbm",
@@ -1186,21 +1218,27 @@ def main():
             "bytes_per_launch": job.dirty_bytes,
             "avg_launch_ms": dirty_avg_ms,
             "launches": nlaunch,
-            "alone": {
-                "avg_launch_ms": alone_ms,
-                "achieved": job.dirty_bytes / (alone_ms * 1e-3) / 1e9,
-                "frac": job.dirty_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "note": "same kernel, same launches through DirtyMapMaker.make_alm, no concurrent alm2map (untimed reference pass after warmup)",
-            },
         },
     }
+    if args.full:
+        # SURVEY 8d asks for the stage times next to the metric; each measured alone on the GPU after warmup (in the
+        # step the SHT runs beside the solves).  value_to_alm = (mmax+1) / (T_fft + T_solve): the metric with T ending
+        # at "a_lm of all (m,f) resident", i.e. without DirtyMapMaker's final alm2map
+        out["stages_alone_ms"] = stage_ms
+        out["value_to_alm"] = scale * (lmax + 1) / ((stage_ms["T_fft"] + stage_ms["T_solve"]) * 1e-3)
+        out["roofline"]["alone"] = {
+            "avg_launch_ms": alone_ms,
+            "achieved": job.dirty_bytes / (alone_ms * 1e-3) / 1e9,
+            "frac": job.dirty_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "note": "same kernel, same launches through DirtyMapMaker.make_alm, no concurrent alm2map (untimed reference pass after warmup)",
+        }
     out["allocator"] = allocator
     if ranks_rec is not None:
         out["ranks"] = ranks_rec
     if gather is not None:
         out["allgather"] = gather
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         out["extra"] = extras(args, cfg, job)
 
     if rank == 0:
@@ -1324,6 +1362,7 @@ def extras(args, cfg, job):
                 a2.maker, a2.tiles, a2.freqs, a2.pool_freqs, a2.steps, a2.warmup, a2.b_dtype = kind, "screen", min(32, nfreq), 16, 1, 1, "complex128"
                 a2.gram_resident = resident == 1
                 a2.basis_resident = resident == 2
+                a2.dump_outputs = None  # (the outputs are the headline's)
                 rec = dense_day(a2, kind)
                 extra[key] = {k: rec[k] for k in ("metric", "value", "unit", "ms_per_step", "day_scale", "config", "roofline", "roofline_secondary", "kernel_classes_ms_per_day_timed", "allocator")}
             except Exception as e:  # noqa: BLE001

@@ -86,3 +86,20 @@ def test_emit_prints_the_compact_line_last_and_writes_the_full_record(tmp_path, 
     assert full["extra"]["ml_day"]["roofline"]["frac"] == pytest.approx(out["extra"]["ml_day"]["roofline"]["frac"], rel=1e-8)
     assert "arms" in full["cpu_baseline"]
     assert (tmp_path / "gpurun_out" / "bench_extra.json").exists()
+
+
+def test_dump_outputs_writes_small_outputs_whole_and_large_ones_as_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+
+    small = torch.randn((4, 4, 12288), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), "map", small)
+    assert np.array_equal(np.load(tmp_path / "a" / "map.npy"), small.numpy())
+    big = torch.arange(3 * bench.DUMP_SAMPLE + 5, dtype=torch.float32)  # > 64 MiB in float64
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "map", big)
+    s = np.load(tmp_path / "b" / "map.npy")
+    assert s.dtype == np.float64 and s.shape == (bench.DUMP_SAMPLE,) and s.nbytes <= 64 << 20
+    assert np.array_equal(s, np.load(tmp_path / "c" / "map.npy"))  # the same elements every run
+    assert (np.diff(s) > 0).all() and s[0] < 3 and s[-1] >= 3 * (bench.DUMP_SAMPLE - 1)  # one per stride, strides cover the array
+    assert not np.array_equal(s % 3, np.zeros_like(s))  # at drawn offsets, not at the strides' starts

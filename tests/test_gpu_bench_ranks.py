@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("scaling", [None, "weak"])
 def test_bench_two_ranks_on_one_gpu(scaling):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2",
-           "--backend", "gloo", "--same-device", "--pool-freqs", "16", "--no-cpu-baseline"] + (["--scaling", scaling] if scaling else [])
+           "--backend", "gloo", "--same-device", "--pool-freqs", "16", "--full", "--no-cpu-baseline"] + (["--scaling", scaling] if scaling else [])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -47,10 +48,11 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 
 def test_bench_default_command_shape_prints_one_short_parsable_last_line():
-    """What round 4 got wrong: the driver keeps the tail of stdout and parses the LAST line.  The default command shape (N = 1,
-    extras and CPU baseline on) at cfg 2 with a short CPU budget: the last line of stdout is JSON, under 4 KB, carries the
-    contract's keys, `roofline` and `cpu_baseline`, and names the file the full record went to -- which exists and holds more."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "2", "--cpu-seconds", "4", "--pool-freqs", "16"]
+    """What round 4 got wrong: the driver keeps the tail of stdout and parses the LAST line.  The default command shape with
+    `--full` (N = 1, extras and CPU baseline on) at cfg 2 with a short CPU budget: the last line of stdout is JSON, under 4 KB,
+    carries the contract's keys, `roofline` and `cpu_baseline`, and names the file the full record went to -- which exists
+    and holds more."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "2", "--cpu-seconds", "4", "--pool-freqs", "16", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -64,3 +66,19 @@ def test_bench_default_command_shape_prints_one_short_parsable_last_line():
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["repeats"] >= 1 and len(d["cpu_baseline"]["sample"]) <= 200
     full = json.load(open(os.path.join(ROOT, d["extra_file"])))
     assert full["value"] == pytest.approx(d["value"], rel=1e-5) and "arms" in full["cpu_baseline"] and "extra" in full
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_map(tmp_path):
+    """A plain run (no --full) measures the headline only: no CPU baseline, no stage-alone passes, no extras; `--steps`
+    is the number of timed days, and `--dump-outputs` writes the last timed day's map (cfg 1: whole, float64)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--config", "1", "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    d = json.loads(res.stdout.splitlines()[-1])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(64 * 1e3 / d["ms_per_step"], rel=1e-4)  # (lmax + 1) m-modes per timed day
+    assert d["cpu_baseline"] is None and "stages_alone_ms" not in d and "secondary" not in d and "alone" not in d["roofline"]
+    assert d["roofline"]["launches"] % 3 == 0  # the Dirty launches of exactly three days
+    m = np.load(tmp_path / "out" / "map.npy")
+    assert m.dtype == np.float64 and m.shape == (4, 4, 12 * 32**2) and np.isfinite(m).all() and np.abs(m).max() > 0
