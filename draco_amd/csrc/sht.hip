@@ -6,7 +6,9 @@
 //  (Q +- iU) = sum a^{+-2}_lm +-2Y_lm,  a^{+-2}_lm = -(E_lm +- i B_lm); pols (T,E,B,V)<->(I,Q,U,V).)
 //
 // Two stages each way, per chunk of frequencies, through a ring-coefficient scratch
-//   b[f][pol][ring][m]   complex128
+//   b[f][pol][ring][m]   complex128 (analysis; synthesis with npol = 1)
+//   b[f / 4][transform (T,Q) | (U,V)][ring][m][f % 4][re | im][pol of the pair]   float64 (synthesis with npol = 4:
+//                        sht_common.h, syn4_at -- whole lines written by the Legendre stage, contiguous runs read per ring)
 //   synthesis:  (1) Legendre:  b_m(ring) = sum_l a_lm * {lambda_lm | F1_lm, F2_lm}(theta_ring)
 //               (2) phases:    map(ring, j) = Re sum_m c_m b_m e^{i m phi_j}
 //   analysis:   (1') phases:   g_m(ring) = (4 pi / npix) sum_j map_j e^{-i m phi_j}
@@ -154,13 +156,23 @@ int check_args(const char* who, dmm_ctx* ctx, const void* a, const void* b, int 
   return DMM_OK;
 }
 
+// frequencies per chunk: whole groups of kSynF for npol = 4 (the synthesis scratch is frequency-grouped), only the last
+// chunk of a transform ragged
 size_t chunk_freqs(int nfreq, int npol, int nring, int mmax) {
+  const size_t grp = npol == 4 ? kSynF : 1;
   const size_t per_f = (size_t)npol * nring * (mmax + 1) * sizeof(double2);
-  size_t nf = ((size_t)1 << 30) / per_f;  // ~1 GiB of ring coefficients at a time
-  if (nf < 1) nf = 1;
+  size_t nf = ((size_t)1 << 30) / per_f / grp * grp;  // ~1 GiB of ring coefficients at a time
+  if (nf < grp) nf = grp;
   if (nf > (size_t)nfreq) nf = nfreq;
   const size_t nchunk = ((size_t)nfreq + nf - 1) / nf;  // equal chunks: no near-empty tail launch
-  return ((size_t)nfreq + nchunk - 1) / nchunk;
+  const size_t c = ((size_t)nfreq + nchunk - 1) / nchunk;
+  return c < (size_t)nfreq ? (c + grp - 1) / grp * grp : c;
+}
+
+// bytes of the ring-coefficient scratch of a chunk of nfc frequencies (npol = 4: whole frequency groups)
+size_t coef_scratch_bytes(size_t nfc, int npol, int nring, int mmax) {
+  const size_t nfs = npol == 4 ? (nfc + kSynF - 1) / kSynF * kSynF : nfc;
+  return nfs * npol * nring * (size_t)(mmax + 1) * sizeof(double2);
 }
 
 // the ring classes of a geometry (see RingClass) with the launch shape of each
@@ -203,13 +215,24 @@ std::vector<ClassLaunch> ring_classes(const ShtGeom& g) {
   return out;
 }
 
-// LDS bytes of the FFT ring kernels for a class; 0 if the class must take the direct kernel
-size_t ring_fft_lds(const ShtGeom& g, const ClassLaunch& c, int nrow, int force_direct, bool synth = false) {
+// LDS bytes of the FFT ring kernels of the analysis for a class; 0 if the class must take the direct kernel
+size_t ring_fft_lds(const ShtGeom& g, const ClassLaunch& c, int nrow, int force_direct) {
   if (force_direct) return 0;
   if (c.blue && c.rc.r_hi > g.blue_rmax) return 0;
-  // synthesis: rings shorter than the band limit stage their rotated coefficients [nrow][2][mmax+1] (k_ring_synth_fft)
-  const size_t rot = synth && c.blue && 4 * c.rc.r_lo < g.mmax + 1 ? (size_t)nrow * 2 * (g.mmax + 1) : 0;
-  const size_t lds = ((size_t)nrow * (c.rc.M + 1) + c.rc.M / 2 + (c.blue ? c.nphi_max : 0) + rot) * sizeof(double2);
+  const size_t lds = ((size_t)nrow * (c.rc.M + 1) + c.rc.M / 2 + (c.blue ? c.nphi_max : 0)) * sizeof(double2);
+  return lds <= 160 * 1024 ? lds : 0;
+}
+
+// LDS bytes of k_ring_synth_fft<npol, nb, ...> for a class (nb transforms per pass); 0 if the class must take the direct
+// kernel.  Rings shorter than the band limit (all rings with stage_all) stage the rotated coefficients of a pass,
+// [nb][2][mmax+1].
+size_t ring_synth_lds(const ShtGeom& g, const ClassLaunch& c, int nb, bool stage_all, int force_direct) {
+  if (force_direct) return 0;
+  if (c.blue && c.rc.r_hi > g.blue_rmax) return 0;
+  const int nm = g.mmax + 1;
+  const bool staged = stage_all || 4 * (c.blue ? c.rc.r_lo : g.nside) < nm;
+  const size_t lds = ((size_t)nb * (c.rc.M + 1) + c.rc.M / 2 + (c.blue ? c.nphi_max : 0) + (staged ? (size_t)nb * 2 * nm : 0)) *
+                     sizeof(double2);
   return lds <= 160 * 1024 ? lds : 0;
 }
 
@@ -231,7 +254,6 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
   lp.n_m = n_m;
   lp.alm = alm;
   lp.b = b;
-  lp.m_identity = (ctx->opt_sht_variant & 32) ? 1 : 0;
   if (NPOL == 4 && !(ctx->opt_sht_variant & 8)) {  // bit 3: force the vector-ALU kernel
     const int npair = (g.nring + 1) / 2;
     const int nrc = (npair + kThreads - 1) / kThreads;
@@ -274,19 +296,36 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
   rp.map_ref = nullptr;
   rp.radix8 = (ctx->opt_sht_variant & 2048) ? 0 : 1;  // bit 11: the radix-4 passes of rounds 1-4 (A/B)
   rp.npix = 12LL * g.nside * g.nside;
-  constexpr int NROWS = NPOL == 4 ? 2 : 1;  // complex transforms per ring (two polarisations each)
+  rp.stage_all = 0;
+  // NPOL = 4: a block per (ring, frequency group, transform (T,Q) | (U,V)); NPOL = 1: per (ring, frequency)
+  constexpr int KF = NPOL == 4 ? kSynF : 1;
+  const dim3 per_ring((nf + KF - 1) / KF, NPOL == 4 ? 2 : 1);
   const int force_direct = ctx->opt_sht_variant & 4;
   for (const ClassLaunch& c : ring_classes(g)) {
-    const size_t lds2 = ring_fft_lds(g, c, NROWS, force_direct, true), lds1 = ring_fft_lds(g, c, 1, force_direct, true);
+    // transforms per pass: the most with which two blocks still fit a CU's LDS (a larger block waits for the CUs that the
+    // solve kernel beside it leaves: 30 x longer in the day), with every ring staged (coalesced loads) if that fits,
+    // else only the aliased ones; failing both, one
+    int nb = 0;
+    size_t lds = 0;
+    rp.stage_all = 0;
+    for (int tier = 0; tier < 3 && nb == 0; ++tier)
+      for (int b = KF; b >= 1 && nb == 0; b >>= 1) {
+        const size_t l = ring_synth_lds(g, c, b, tier == 0, force_direct);
+        if (l != 0 && l <= (tier < 2 ? (size_t)80 * 1024 : (size_t)160 * 1024)) nb = b, lds = l, rp.stage_all = tier == 0;
+      }
+    const dim3 grid(c.nblock, per_ring.x, per_ring.y);
     int rc;
-    if (lds1 == 0) {
+    if (nb == 0) {
       rc = launch_ring(k_ring_synth<NPOL>, dim3(c.nblock, nf), kThreads, (size_t)NPOL * (g.mmax + 1) * sizeof(double2), ctx->stream, rp, c.rc);
-    } else if (NROWS == 2 && lds2 != 0 && lds2 <= 80 * 1024) {  // both transforms in one block while two blocks still fit a CU
-      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, NROWS, true>, dim3(c.nblock, nf), kFftThreads, lds2, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_synth_fft<NPOL, NROWS, false>, dim3(c.nblock, nf), kFftThreads, lds2, ctx->stream, rp, c.rc);
+    } else if (nb == 4) {
+      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 4 : 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
+                  : launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 4 : 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
+    } else if (nb == 2) {
+      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 2 : 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
+                  : launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 2 : 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
     } else {
-      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, 1, true>, dim3(c.nblock, nf, NROWS), kFftThreads, lds1, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_synth_fft<NPOL, 1, false>, dim3(c.nblock, nf, NROWS), kFftThreads, lds1, ctx->stream, rp, c.rc);
+      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
+                  : launch_ring(k_ring_synth_fft<NPOL, 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
     }
     if (rc) return rc;
   }
@@ -305,6 +344,7 @@ int anal_chunk(dmm_ctx* ctx, const ShtGeom& g, const double* map, int n_m, int n
   rp.map_ref = map_ref;
   rp.radix8 = (ctx->opt_sht_variant & 2048) ? 0 : 1;  // bit 11: the radix-4 passes of rounds 1-4 (A/B)
   rp.npix = 12LL * g.nside * g.nside;
+  rp.stage_all = 0;
   constexpr int NROWS = NPOL == 4 ? 2 : 1;
   const int force_direct = ctx->opt_sht_variant & 4;
   for (const ClassLaunch& c : ring_classes(g)) {
@@ -361,7 +401,7 @@ int dmm_alm2map(dmm_ctx* ctx, const void* alm, int nfreq, int npol, int lmax, in
   if (rc) return rc;
   const size_t nfc = chunk_freqs(nfreq, npol, g.nring, mmax);
   void* scratch = nullptr;
-  rc = dmm_get_scratch(ctx, nfc * npol * g.nring * (size_t)(mmax + 1) * sizeof(double2), &scratch);
+  rc = dmm_get_scratch(ctx, coef_scratch_bytes(nfc, npol, g.nring, mmax), &scratch);
   if (rc) return rc;
   const int64_t npix = 12LL * nside * nside;
   const int n_m = mmax + 1;
@@ -388,7 +428,7 @@ int dmm_map2alm(dmm_ctx* ctx, const double* map, int nfreq, int npol, int lmax, 
   if (rc) return rc;
   const int64_t npix = 12LL * nside * nside;
   size_t nfc = chunk_freqs(nfreq, npol, g.nring, mmax);
-  const size_t b_bytes = nfc * npol * g.nring * (size_t)(mmax + 1) * sizeof(double2);
+  const size_t b_bytes = coef_scratch_bytes(nfc, npol, g.nring, mmax);  // (the synthesis of the iterations reuses it grouped)
   const size_t r_bytes = niter > 0 ? nfc * npol * (size_t)npix * sizeof(double) : 0;
   void* scratch = nullptr;
   rc = dmm_get_scratch(ctx, b_bytes + r_bytes, &scratch);

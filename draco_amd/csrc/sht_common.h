@@ -14,6 +14,23 @@ namespace {
 constexpr int kThreads = 256;
 constexpr double kBig = 0x1p+740, kSmallStep = 0x1p-800;
 
+// The ring-coefficient scratch of the NPOL = 4 synthesis (alm2map, and the residual of map2alm's iterations) is
+// frequency-grouped, in doubles:
+//   b[fgroup][r:2][ring][m][fi:kSynF][comp:2][p:2]
+//   r = 0: transform (T, Q); r = 1: transform (U, V) (the pairing of the ring stage);  comp = re / im;
+//   p = polarisation within the pair in the order the MFMA lanes of the Legendre stage hold them: (T, Q) and (V, U).
+// One 128-byte line per (group, r, ring, m): a wave store of the synthesis (four rings x 16 lanes of one m) writes eight
+// whole lines, and a ring block that owns (ring, group, r) reads one contiguous run of (mmax + 1) x 128 bytes.  Slots of
+// frequencies beyond the chunk's last are never written and never read.  (The analysis keeps b[f][pol][ring][m].)
+constexpr int kSynF = 4;
+constexpr int kSynRow = kSynF * 4;  // doubles per (group, r, ring, m)
+// offset (doubles) of the [comp][p] quadruple of frequency f (of the chunk), transform r at (m, ring)
+__host__ __device__ __forceinline__ int64_t syn4_at(int f, int m, int ring, int r, int nring, int nm) {
+  return ((((int64_t)(f / kSynF) * 2 + r) * nring + ring) * nm + m) * kSynRow + 4 * (f % kSynF);
+}
+// polarisation slot p of pol (0..3: T, Q, U, V) in its transform r = pol >> 1
+__host__ __device__ __forceinline__ int syn4_slot(int pol) { return pol == 1 || pol == 2 ? 1 : 0; }
+
 struct ShtGeom {          // device tables for one (nside, lmax, mmax)
   int nside, lmax, mmax, nring;
   double* z;              // [nring] cos(theta)
@@ -46,8 +63,7 @@ struct LegParams {
   int npol;               // 1 or 4
   int n_m;                // m-stride of alm (= mmax+1 of the alm buffer)
   const double2* alm;     // [nf, npol, n_m, lmax+1]
-  double2* b;             // [nf, npol, nring, mmax+1]
-  int m_identity;         // 1: block b takes m = b (sht_variant bit 5, the A/B of leg_m_of_block)
+  double2* b;             // NPOL = 4: frequency-grouped (syn4_at); NPOL = 1: [nf, nring, mmax+1]
 #ifdef LEG_STAMPS
   unsigned long long* stamps;  // diagnostic build only
 #endif

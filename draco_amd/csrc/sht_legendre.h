@@ -6,18 +6,9 @@
 namespace {
 
 // ---------------------------------------------------------------- synthesis, stage 1
-// block -> m.  Every Legendre kernel reads or writes ONE m of the ring-coefficient array [freq][pol][ring][m]: 16-byte
-// pieces 8 KB apart, eight consecutive m to a 128-byte line.  Workgroups go to the eight XCDs (each with its own L2) round
-// robin by linear id, so with m = blockIdx.x the eight blocks that share a line sat on eight different L2s: every line was
-// fetched (analysis) or partially written (synthesis) eight times over.  Here the blocks b, b + 8, ..., b + 56 of one XCD
-// take eight consecutive m (groups of 64; a last partial group keeps m = b).
-__device__ __forceinline__ int leg_m_of_block(int b, int n_m, int variant_identity) {
-  if (variant_identity) return b;
-  const int q = b >> 6, r = b & 63;
-  if (q * 64 + 64 > n_m) return b;
-  return q * 64 + (r & 7) * 8 + (r >> 3);
-}
-
+// block -> m = blockIdx.x.  The NPOL = 4 forms write whole 128-byte lines of the frequency-grouped scratch (sht_common.h)
+// and share no line between m, so they need no XCD-aware map of blocks to m (the analysis keeps one, leg_m_of_block below;
+// on the headline day the synthesis with and without it: 247.1 / 247.9 against 247.3 / 247.0 ms per day).
 template <int NPOL, int NR, int MINW>
 __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
   const int m = blockIdx.x, f = blockIdx.y;
@@ -135,19 +126,22 @@ __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
       if (r >= npair) continue;
       const int rs = nring - 1 - r;  // southern mirror (== r on the equator)
       const Ring& g = R[t];
-      auto put = [&](int pol, int ring, double2 s, double2 an, double sgn) {
-        p.b[(((int64_t)f * NPOL + pol) * nring + ring) * mstride + m] = make_double2(s.x + sgn * an.x, s.y + sgn * an.y);
-      };
-      put(0, r, g.Ts, g.Ta, 1.0);
-      if (rs != r) put(0, rs, g.Ts, g.Ta, -1.0);
-      if (NPOL == 4) {
-        put(1, r, g.Qs, g.Qa, 1.0);
-        put(2, r, g.Us, g.Ua, 1.0);
-        put(3, r, g.Vs, g.Va, 1.0);
+      auto val = [&](double2 s, double2 an, double sgn) { return make_double2(s.x + sgn * an.x, s.y + sgn * an.y); };
+      if (NPOL == 1) {
+        p.b[((int64_t)f * nring + r) * mstride + m] = val(g.Ts, g.Ta, 1.0);
+        if (rs != r) p.b[((int64_t)f * nring + rs) * mstride + m] = val(g.Ts, g.Ta, -1.0);
+      } else {  // the frequency-grouped scratch: slot 0 / 1 of transform r as (re, re), (im, im) pairs
+        double* bout = reinterpret_cast<double*>(p.b);
+        auto put = [&](int ring, int tr, double2 v0, double2 v1) {
+          double* q = bout + syn4_at(f, m, ring, tr, nring, (int)mstride);
+          *reinterpret_cast<double2*>(q) = make_double2(v0.x, v1.x);
+          *reinterpret_cast<double2*>(q + 2) = make_double2(v0.y, v1.y);
+        };
+        put(r, 0, val(g.Ts, g.Ta, 1.0), val(g.Qs, g.Qa, 1.0));
+        put(r, 1, val(g.Vs, g.Va, 1.0), val(g.Us, g.Ua, 1.0));
         if (rs != r) {
-          put(1, rs, g.Qs, g.Qa, -1.0);
-          put(2, rs, g.Us, g.Ua, -1.0);
-          put(3, rs, g.Vs, g.Va, -1.0);
+          put(rs, 0, val(g.Ts, g.Ta, -1.0), val(g.Qs, g.Qa, -1.0));
+          put(rs, 1, val(g.Vs, g.Va, -1.0), val(g.Us, g.Ua, -1.0));
         }
       }
     }
@@ -169,12 +163,13 @@ __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
 // complete in order): the l loop has no barrier at all.  Slab pitch 72 doubles: the 16 rings of a
 // lane group and the two l rows of a half wave fall on disjoint banks.
 constexpr int kLegL = 8, kLegF = 4, kLegPitch = 72;
+static_assert(kLegF == kSynF, "a frequency group of the MFMA columns is one group of the synthesis scratch");
 
 // (the kernels' bodies take their block coordinates as arguments: one block per (m, ring chunk, frequency group))
 __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, int by, int bz) {
   typedef double v4d __attribute__((ext_vector_type(4)));
   __shared__ double slab[kThreads / 64][3][kLegL][kLegPitch];
-  const int m = leg_m_of_block(bx, p.g.mmax + 1, p.m_identity), rc = by, f0 = bz * kLegF;
+  const int m = bx, rc = by, f0 = bz * kLegF;
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nring = p.g.nring, npair = (nring + 1) / 2;
@@ -295,10 +290,11 @@ __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, 
       }
     }
   }
-  // ring coefficients: north = sym + anti, south = sym - anti; D rows = rings (kq + 4 reg), D columns = this lane's column
+  // ring coefficients: north = sym + anti, south = sym - anti; D rows = rings (kq + 4 reg), D columns = this lane's column.
+  // The lane's (T | V) and (Q | U) values of one ring are slots 0 and 1 of component c & 1 of transform c >> 1 in the
+  // frequency-grouped scratch: one 16-byte store, and the 64 lanes of a wave cover eight whole 128-byte lines.
   if (!fok) return;
-  double* bout = reinterpret_cast<double*>(p.b);
-  const int comp = c & 1;
+  double* bout = reinterpret_cast<double*>(p.b) + 2 * (c & 1);
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -306,13 +302,9 @@ __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, 
       const int rr = rc * kThreads + wave * 64 + 16 * t + kq + 4 * reg;
       if (rr >= npair) continue;
       const int rs = nring - 1 - rr;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {  // g = 0: (T | V), g = 1: (Q | U)
-        const int pol = g == 0 ? (c < 2 ? 0 : 3) : (c < 2 ? 1 : 2);
-        const double sy = acc[t][2 * g][reg], an = acc[t][2 * g + 1][reg];
-        bout[((((int64_t)f * 4 + pol) * nring + rr) * mstride + m) * 2 + comp] = sy + an;
-        if (rs != rr) bout[((((int64_t)f * 4 + pol) * nring + rs) * mstride + m) * 2 + comp] = sy - an;
-      }
+      const double tv = acc[t][0][reg], tva = acc[t][1][reg], qu = acc[t][2][reg], qua = acc[t][3][reg];
+      *reinterpret_cast<double2*>(bout + syn4_at(f, m, rr, c >> 1, nring, (int)mstride)) = make_double2(tv + tva, qu + qua);
+      if (rs != rr) *reinterpret_cast<double2*>(bout + syn4_at(f, m, rs, c >> 1, nring, (int)mstride)) = make_double2(tv - tva, qu - qua);
     }
 }
 
@@ -352,7 +344,7 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
   typedef double v4d __attribute__((ext_vector_type(4)));
   __shared__ double slab[kThreads / 64][2][kLeg2Rows][kLegPitch];
   __shared__ double ringf[kThreads / 64][2][64];
-  const int m = leg_m_of_block(bx, p.g.mmax + 1, p.m_identity), rc = by, f0 = bz * (kLegF * NFG);
+  const int m = bx, rc = by, f0 = bz * (kLegF * NFG);
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nring = p.g.nring, npair = (nring + 1) / 2;
@@ -588,9 +580,9 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
   }
   LEG_STAMP(4);
   // ring coefficients: north = sym + anti, south = sym - anti; D rows = rings (kq + 4 reg), D columns = this lane's column
-  // (the Q | U accumulators hold MINUS the F1 terms' sign convention of the first form folded into the A operand: same sums)
-  double* bout = reinterpret_cast<double*>(p.b);
-  const int comp = c & 1;
+  // (the Q | U accumulators hold MINUS the F1 terms' sign convention of the first form folded into the A operand: same sums),
+  // stored as by the first form: one 16-byte (T | V, Q | U) pair per lane and ring, eight whole 128-byte lines per wave
+  double* bout = reinterpret_cast<double*>(p.b) + 2 * (c & 1);
 #pragma unroll
   for (int h = 0; h < NFG; ++h) {
     if (!fok[h]) continue;
@@ -602,13 +594,9 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
         const int rr = 16 * (W + t * NW) + kq + 4 * reg;
         if (rr >= npair) continue;
         const int rs = nring - 1 - rr;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {  // g = 0: (T | V), g = 1: (Q | U)
-          const int pol = g == 0 ? (c < 2 ? 0 : 3) : (c < 2 ? 1 : 2);
-          const double sy = acc[h][t][2 * g][reg], an = acc[h][t][2 * g + 1][reg];
-          bout[((((int64_t)f * 4 + pol) * nring + rr) * mstride + m) * 2 + comp] = sy + an;
-          if (rs != rr) bout[((((int64_t)f * 4 + pol) * nring + rs) * mstride + m) * 2 + comp] = sy - an;
-        }
+        const double tv = acc[h][t][0][reg], tva = acc[h][t][1][reg], qu = acc[h][t][2][reg], qua = acc[h][t][3][reg];
+        *reinterpret_cast<double2*>(bout + syn4_at(f, m, rr, c >> 1, nring, (int)mstride)) = make_double2(tv + tva, qu + qua);
+        if (rs != rr) *reinterpret_cast<double2*>(bout + syn4_at(f, m, rs, c >> 1, nring, (int)mstride)) = make_double2(tv - tva, qu - qua);
       }
   }
 #ifdef LEG_STAMPS
@@ -632,6 +620,18 @@ __global__ __launch_bounds__(kThreads, 3 - NFG) void k_leg_synth_mfma2(LegParams
 }
 
 // ---------------------------------------------------------------- analysis, stage 2'
+// block -> m.  The analysis kernels read ONE m of the ring-coefficient array [freq][pol][ring][m]: 16-byte pieces 8 KB
+// apart, eight consecutive m to a 128-byte line.  Workgroups go to the eight XCDs (each with its own L2) round robin by
+// linear id, so with m = blockIdx.x the eight blocks that share a line sat on eight different L2s: every line was fetched
+// eight times over.  Here the blocks b, b + 8, ..., b + 56 of one XCD take eight consecutive m (groups of 64; a last partial
+// group keeps m = b).
+__device__ __forceinline__ int leg_m_of_block(int b, int n_m, int variant_identity) {
+  if (variant_identity) return b;
+  const int q = b >> 6, r = b & 63;
+  if (q * 64 + 64 > n_m) return b;
+  return q * 64 + (r & 7) * 8 + (r >> 3);
+}
+
 struct LegAnalParams {
   ShtGeom g;
   int nf, npol, n_m;

@@ -9,12 +9,13 @@ namespace {
 struct RingParams {
   ShtGeom g;
   int nf, npol;
-  double2* b;     // [nf, npol, nring, mmax+1]
+  double2* b;     // [nf, npol, nring, mmax+1]; the NPOL = 4 synthesis: frequency-grouped (syn4_at)
   double* map;    // [nf, npol, npix]
   int64_t npix;
   const double* map_ref;  // analysis only, or nullptr: the field analysed is map_ref - map (the residual of a Jacobi iteration of
                           // map2alm, formed on the way in instead of by a pass of its own over the maps)
   int radix8;             // 1 (default): the in-LDS transforms with three stages per pass (fft_dif8 / fft_dit8); 0: two (sht_variant bit 11)
+  int stage_all;          // synthesis: 1 = every ring stages the rotated coefficients of a pass in LDS (k_ring_synth_fft), 0 = the aliased ones
 };
 
 // A launch covers one CLASS of rings that share an FFT length:
@@ -53,7 +54,13 @@ __global__ __launch_bounds__(kThreads) void k_ring_synth(RingParams p, RingClass
   const int nphi = p.g.nphi[ring];
   for (int idx = threadIdx.x; idx < NPOL * nm; idx += kThreads) {
     const int pol = idx / nm, m = idx - pol * nm;
-    const double2 v = p.b[(((int64_t)f * NPOL + pol) * p.g.nring + ring) * nm + m];
+    double2 v;
+    if (NPOL == 1) {
+      v = p.b[((int64_t)f * p.g.nring + ring) * nm + m];
+    } else {  // the frequency-grouped scratch (syn4_at)
+      const double* q = reinterpret_cast<const double*>(p.b) + syn4_at(f, m, ring, pol >> 1, p.g.nring, nm) + syn4_slot(pol);
+      v = make_double2(q[0], q[2]);
+    }
     double sn, cs;
     sincos((double)m * phi0, &sn, &cs);
     const double fac = m == 0 ? 1.0 : 2.0;
@@ -178,125 +185,143 @@ __device__ __forceinline__ dmm_fft::C<double> ring_dft_at(const RingLds& l, int 
 // Synthesis: the Hermitian spectrum H_k = b_k e^{i k phi0} (k <= mmax), H_{N-k} = conj(H_k),
 // folded modulo N, makes the map real, so two polarisations ride one transform:
 // z = H_a + i H_b  ->  IDFT(z) = map_a + i map_b, and IDFT(z) = conj(DFT(conj z)).
-// NROW complex transforms per block; for NPOL = 4 transform r carries polarisations 2(r + rb), 2(r + rb) + 1 with
-// rb = blockIdx.z * NROW: the large rings run ONE transform per block so that two blocks fit a CU's LDS.
-template <int NPOL, int NROW, bool BLUE>
+// NPOL = 4: block = (ring of the class, frequency group, transform r = blockIdx.z), r = 0 carrying (T, Q) and r = 1 (U, V);
+// the group's kSynF frequencies are NB complex transforms at a time, and the block reads one contiguous run of the
+// frequency-grouped scratch (128 bytes per m).  NPOL = 1: block = (ring, frequency), one transform (NB = 1).
+// Rings shorter than the band limit (n < nm) alias many m onto one k: there (and on every ring of a launch with
+// p.stage_all, whose loads are then coalesced) the phase rotation of a pass's frequencies runs in parallel over m first, into
+// LDS, and the fold below only adds (a fixed order, so still reproducible); the other rings rotate each row where the fold
+// reads it.  Same operations in the same order per transform either way.
+template <int NPOL, int NB, bool BLUE>
 __global__ __launch_bounds__(kFftThreads) void k_ring_synth_fft(RingParams p, RingClass rc) {
   using dmm_fft::C;
+  constexpr int KF = NPOL == 4 ? kSynF : 1;  // frequencies of a block
+  static_assert(KF % NB == 0, "passes of NB transforms");
   extern __shared__ __align__(16) unsigned char smem[];
-  const int rb = blockIdx.z * NROW;
-  const int ring = class_ring(rc, p.g, blockIdx.x), f = blockIdx.y;
+  const int ring = class_ring(rc, p.g, blockIdx.x), r = NPOL == 4 ? (int)blockIdx.z : 0;
+  const int f0 = KF * blockIdx.y, nfb = min(KF, p.nf - f0);  // the block's frequencies f0 .. f0 + nfb - 1 of the chunk
   const int n = p.g.nphi[ring], M = rc.M, P = M + 1;
-  const RingLds l = ring_lds<NROW, BLUE>(smem, p.g, n, M);
+  const RingLds l = ring_lds<NB, BLUE>(smem, p.g, n, M);
   if (BLUE) __syncthreads();  // the chirp is used by the load below
   const int nm = p.g.mmax + 1;
   const double2* phase = p.g.phase + (int64_t)ring * nm;  // e^{i m phi0} of this ring
-  const double2 *browa[NROW], *browb[NROW];  // the two polarisations of transform r
-#pragma unroll
-  for (int r = 0; r < NROW; ++r) {
-    browa[r] = p.b + (((int64_t)f * NPOL + (NPOL == 4 ? 2 * (r + rb) : 0)) * p.g.nring + ring) * nm;
-    browb[r] = p.b + (((int64_t)f * NPOL + (NPOL == 4 ? 2 * (r + rb) + 1 : 0)) * p.g.nring + ring) * nm;
-  }
-  // Rings shorter than the band limit (n < nm) alias many m onto one k: there the phase rotation runs in
-  // parallel over m first, into LDS, and the fold below only adds (a fixed order, so still reproducible).
-  const bool aliased = n < nm;
-  C<double>* rot = l.chirp + (BLUE ? 4 * rc.r_hi : 0);  // [NROW][2][nm], present when the class has such rings
-  if (aliased) {
-    for (int m = threadIdx.x; m < nm; m += kFftThreads) {
-      const double2 ph = phase[m];
-      const double cs = ph.x, sn = ph.y;
-#pragma unroll
-      for (int r = 0; r < NROW; ++r) {
-        const double2 va = browa[r][m];
-        C<double> a = {va.x * cs - va.y * sn, va.x * sn + va.y * cs}, b = {0.0, 0.0};
-        if (NPOL == 4) {
-          const double2 vb = browb[r][m];
-          b = {vb.x * cs - vb.y * sn, vb.x * sn + vb.y * cs};
+  // (b_m of the transform's two polarisations a, b) of frequency f0 + fi.  NPOL = 4: slots (T, Q) of r = 0, (V, U) of r = 1
+  auto load = [&](int fi, int m, double2& va, double2& vb) {
+    if (NPOL == 1) {
+      va = p.b[((int64_t)(f0 + fi) * p.g.nring + ring) * nm + m];
+    } else {
+      const double* q = reinterpret_cast<const double*>(p.b) + syn4_at(f0 + fi, m, ring, r, p.g.nring, nm);
+      const double2 re = *reinterpret_cast<const double2*>(q), im = *reinterpret_cast<const double2*>(q + 2);
+      va = r == 0 ? make_double2(re.x, im.x) : make_double2(re.y, im.y);
+      vb = r == 0 ? make_double2(re.y, im.y) : make_double2(re.x, im.x);
+    }
+  };
+  const bool staged = p.stage_all || n < nm;
+  C<double>* rot = l.chirp + (BLUE ? 4 * rc.r_hi : 0);  // [NB][2][nm], present when the class has staged rings
+  const double2* bfilt = BLUE ? p.g.bfilt + p.g.bf_off[rc.belt ? 0 : rc.r_lo + ((int)blockIdx.x >> 1)] : nullptr;
+  const int64_t base = p.g.start[ring];
+  // passes of NB transforms: the block's later passes read their slots of the lines its first pass brought in (L2)
+  for (int fb = 0; fb < nfb; fb += NB) {
+    if (fb > 0) __syncthreads();  // the previous pass reads rot and l.buf until here
+    if (staged) {
+      // thread <-> (m, frequency of the pass): the block's run of the scratch is read front to back
+      for (int q = threadIdx.x; q < NB * nm; q += kFftThreads) {
+        const int m = q / NB, j = q - m * NB;
+        C<double> a = {0.0, 0.0}, b = {0.0, 0.0};
+        if (fb + j < nfb) {  // (slots beyond the chunk's last frequency are neither read nor stored)
+          const double2 ph = phase[m];
+          const double cs = ph.x, sn = ph.y;
+          double2 va, vb;
+          load(fb + j, m, va, vb);
+          a = {va.x * cs - va.y * sn, va.x * sn + va.y * cs};
+          if (NPOL == 4) b = {vb.x * cs - vb.y * sn, vb.x * sn + vb.y * cs};
+          if (m == 0) a.y = b.y = 0.0;  // the m = 0 term of a real field is real
         }
-        if (m == 0) a.y = b.y = 0.0;  // the m = 0 term of a real field is real
-        rot[(r * 2 + 0) * nm + m] = a;
-        rot[(r * 2 + 1) * nm + m] = b;
+        rot[(j * 2 + 0) * nm + m] = a;
+        rot[(j * 2 + 1) * nm + m] = b;
+      }
+      __syncthreads();
+    }
+    for (int k = threadIdx.x; k < M; k += kFftThreads) {
+      double zr[NB], zi[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) zr[j] = zi[j] = 0.0;
+      if (k < n && staged) {
+        for (int m = k; m < nm; m += n) {  // direct terms: z += H_a + i H_b
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            const C<double> a = rot[(j * 2 + 0) * nm + m], b = rot[(j * 2 + 1) * nm + m];
+            zr[j] += a.x - b.y;
+            zi[j] += a.y + b.x;
+          }
+        }
+        for (int m = (k == 0 ? n : n - k); m < nm; m += n) {  // mirrored terms: z += conj(H_a) + i conj(H_b)
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            const C<double> a = rot[(j * 2 + 0) * nm + m], b = rot[(j * 2 + 1) * nm + m];
+            zr[j] += a.x + b.y;
+            zi[j] += b.x - a.y;
+          }
+        }
+      } else if (k < n) {
+        // direct terms m == k (mod n)
+        for (int m = k; m < nm; m += n) {
+          const double2 ph = phase[m];
+          const double cs = ph.x, sn = ph.y;
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            if (fb + j >= nfb) continue;
+            double2 va, vb;
+            load(fb + j, m, va, vb);
+            double ar = va.x * cs - va.y * sn, ai = va.x * sn + va.y * cs;
+            double br = 0.0, bi = 0.0;
+            if (NPOL == 4) {
+              br = vb.x * cs - vb.y * sn;
+              bi = vb.x * sn + vb.y * cs;
+            }
+            if (m == 0) ai = bi = 0.0;  // the m = 0 term of a real field is real
+            zr[j] += ar - bi;           // z = H_a + i H_b
+            zi[j] += ai + br;
+          }
+        }
+        // mirrored terms m == -k (mod n), m >= 1: conj(H_a) + i conj(H_b)
+        for (int m = (k == 0 ? n : n - k); m < nm; m += n) {
+          const double2 ph = phase[m];
+          const double cs = ph.x, sn = ph.y;
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            if (fb + j >= nfb) continue;
+            double2 va, vb;
+            load(fb + j, m, va, vb);
+            const double ar = va.x * cs - va.y * sn, ai = va.x * sn + va.y * cs;
+            double br = 0.0, bi = 0.0;
+            if (NPOL == 4) {
+              br = vb.x * cs - vb.y * sn;
+              bi = vb.x * sn + vb.y * cs;
+            }
+            zr[j] += ar + bi;  // conj(a) + i conj(b) = (ar + bi) + i(br - ai)
+            zi[j] += br - ai;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        C<double> v = {zr[j], -zi[j]};  // conj(z)
+        if (BLUE && k < n) v = dmm_fft::cmul<double>(v, l.chirp[k]);
+        l.buf[j * P + k] = v;
       }
     }
     __syncthreads();
-  }
-  for (int k = threadIdx.x; k < M; k += kFftThreads) {
-    double zr[NROW], zi[NROW];
+    ring_dft<NB, BLUE>(l, bfilt, M, rc.logM, p.radix8 != 0);
+    for (int j = threadIdx.x; j < n; j += kFftThreads) {
 #pragma unroll
-    for (int r = 0; r < NROW; ++r) zr[r] = zi[r] = 0.0;
-    if (k < n && aliased) {
-      for (int m = k; m < nm; m += n) {  // direct terms: z += H_a + i H_b
-#pragma unroll
-        for (int r = 0; r < NROW; ++r) {
-          const C<double> a = rot[(r * 2 + 0) * nm + m], b = rot[(r * 2 + 1) * nm + m];
-          zr[r] += a.x - b.y;
-          zi[r] += a.y + b.x;
-        }
+      for (int jj = 0; jj < NB; ++jj) {
+        if (fb + jj >= nfb) continue;
+        const int64_t f = f0 + fb + jj;
+        const C<double> y = ring_dft_at<BLUE>(l, jj, j, M, rc.logM);  // IDFT(z)_j = conj(y)
+        p.map[(f * NPOL + 2 * r) * p.npix + base + j] = y.x;
+        if (NPOL == 4) p.map[(f * NPOL + 2 * r + 1) * p.npix + base + j] = -y.y;
       }
-      for (int m = (k == 0 ? n : n - k); m < nm; m += n) {  // mirrored terms: z += conj(H_a) + i conj(H_b)
-#pragma unroll
-        for (int r = 0; r < NROW; ++r) {
-          const C<double> a = rot[(r * 2 + 0) * nm + m], b = rot[(r * 2 + 1) * nm + m];
-          zr[r] += a.x + b.y;
-          zi[r] += b.x - a.y;
-        }
-      }
-    } else if (k < n) {
-      // direct terms m == k (mod n)
-      for (int m = k; m < nm; m += n) {
-        const double2 ph = phase[m];
-        const double cs = ph.x, sn = ph.y;
-#pragma unroll
-        for (int r = 0; r < NROW; ++r) {
-          const double2 va = browa[r][m];
-          double ar = va.x * cs - va.y * sn, ai = va.x * sn + va.y * cs;
-          double br = 0.0, bi = 0.0;
-          if (NPOL == 4) {
-            const double2 vb = browb[r][m];
-            br = vb.x * cs - vb.y * sn;
-            bi = vb.x * sn + vb.y * cs;
-          }
-          if (m == 0) ai = bi = 0.0;  // the m = 0 term of a real field is real
-          zr[r] += ar - bi;           // z = H_a + i H_b
-          zi[r] += ai + br;
-        }
-      }
-      // mirrored terms m == -k (mod n), m >= 1: conj(H_a) + i conj(H_b)
-      for (int m = (k == 0 ? n : n - k); m < nm; m += n) {
-        const double2 ph = phase[m];
-        const double cs = ph.x, sn = ph.y;
-#pragma unroll
-        for (int r = 0; r < NROW; ++r) {
-          const double2 va = browa[r][m];
-          const double ar = va.x * cs - va.y * sn, ai = va.x * sn + va.y * cs;
-          double br = 0.0, bi = 0.0;
-          if (NPOL == 4) {
-            const double2 vb = browb[r][m];
-            br = vb.x * cs - vb.y * sn;
-            bi = vb.x * sn + vb.y * cs;
-          }
-          zr[r] += ar + bi;  // conj(a) + i conj(b) = (ar + bi) + i(br - ai)
-          zi[r] += br - ai;
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < NROW; ++r) {
-      C<double> v = {zr[r], -zi[r]};  // conj(z)
-      if (BLUE && k < n) v = dmm_fft::cmul<double>(v, l.chirp[k]);
-      l.buf[r * P + k] = v;
-    }
-  }
-  __syncthreads();
-  const double2* bfilt = BLUE ? p.g.bfilt + p.g.bf_off[rc.belt ? 0 : rc.r_lo + ((int)blockIdx.x >> 1)] : nullptr;
-  ring_dft<NROW, BLUE>(l, bfilt, M, rc.logM, p.radix8 != 0);
-  const int64_t base = p.g.start[ring];
-  for (int j = threadIdx.x; j < n; j += kFftThreads) {
-#pragma unroll
-    for (int r = 0; r < NROW; ++r) {
-      const C<double> y = ring_dft_at<BLUE>(l, r, j, M, rc.logM);  // IDFT(z)_j = conj(y)
-      p.map[((int64_t)f * NPOL + (NPOL == 4 ? 2 * (r + rb) : 0)) * p.npix + base + j] = y.x;
-      if (NPOL == 4) p.map[((int64_t)f * NPOL + 2 * (r + rb) + 1) * p.npix + base + j] = -y.y;
     }
   }
 }

@@ -81,7 +81,7 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "grid_mult", "project_grid_mult";
  *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio", "project_variant", "ringmap_variant" (1 three-kernel
  *    form, 2 eight elevations per block), "sht_variant" (bits: 0-1 vector-ALU synthesis form, 2 direct ring sums,
- *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x, 6 first MFMA synthesis form,
+ *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x in the analysis, 6 first MFMA synthesis form,
  *    7 pipelined synthesis with 4 frequencies per block, 11 radix-4 ring FFTs), "sht_synth_form" (1: first MFMA form);
  *  "profile" (1: HIP-event timing of the dense solvers' kernel classes, sums cleared; 0 off). */
 int dmm_ctx_set_option(dmm_ctx* ctx, const char* name, int64_t value);
