@@ -94,6 +94,13 @@ def _tile_sizes(provider, ms, b_layout):
     return per_m[ms]
 
 
+def _two_stage_max_order(ctx):
+    """The largest matrix order the library's two-stage ML reduction takes (a property of the build)."""
+    v = C.c_int64()
+    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, b"ml_two_stage_max_order", C.byref(v)))
+    return int(v.value)
+
+
 def release_pools():
     """Give the kept block back (to the caching allocator, and on to the device)."""
     torch.cuda.synchronize()
@@ -348,6 +355,8 @@ class SolveEngine:
         if nslots == 0:
             return False
         ntel = 2 * self.provider.telescope.npairs
+        if (ntel + 63) // 64 * 64 > _two_stage_max_order(self.ctx):
+            return False  # (a basis is built by the two-stage reduction at telescope order: the full-order pass instead)
         rmax = int(self.basis_rmax)
         if buf.basis is None or buf.basis[2].numel() < nslots or buf.basis[3] != (rmax, ntel):
             buf.basis = None

@@ -162,6 +162,14 @@ int dmm_ctx_get_counter(dmm_ctx* c, const char* name, int64_t* value) {
   else if (!strcmp(name, "ml_band_bytes")) *value = c->ml_band_bytes;
   else if (!strcmp(name, "ml_tiles_ql_failed")) *value = c->ml_tiles_ql_failed;
   else if (!strcmp(name, "ml_early_chunks")) *value = c->ml_early_chunks;
+  else if (!strcmp(name, "ml_two_stage_max_order")) *value = dmm_ml_two_stage_max_order();  // (read-only: a property of the build)
+  else if (!strcmp(name, "build_ab")) {  // (read-only: 1 if built with -DDMM_AB, where "ml_reduce" = 5 is the one-kernel stage 1)
+#ifdef DMM_AB
+    *value = 1;
+#else
+    *value = 0;
+#endif
+  }
   else if (!strcmp(name, "opt_sht_synth_form")) *value = c->opt_sht_synth_form;  // (the option's current value: callers that set it around a call restore it)
   else if (!strncmp(name, "prof_", 5)) {
     const size_t len = strlen(name);

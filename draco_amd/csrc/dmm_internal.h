@@ -171,6 +171,7 @@ int dmm_set_error(int code, const char* fmt, ...);
   } while (0)
 
 int dmm_fft_tables_f64(dmm_ctx* ctx, int n, dmm_fft_tables** out);  // mfft.hip
+int dmm_ml_two_stage_max_order();  // solve_dense.hip: the largest order the ML band reduction takes
 
 static inline bool dmm_is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 

@@ -90,9 +90,16 @@ void td_reduce(TdParams& tp, int nmat, hipStream_t st) {
 
 // ---- two-stage reduction (herm_band.h): dense -> band of half-width 8 on the MFMA units, band -> tridiagonal in LDS
 constexpr size_t kSbLdsMax = 160 * 1024;
-bool sb_usable(const dmm_ctx* ctx, int n) {
-  if (ctx->opt_ml_reduce == 1) return false;
+bool sb_fits(int n) {
   return n >= 64 && n % 64 == 0 && n <= kSbRows * kThreads && sb_chase_lds(n) + 4608 <= kSbLdsMax;  // (+ the chase kernel's static scratch)
+}
+bool sb_usable(const dmm_ctx* ctx, int n) { return ctx->opt_ml_reduce != 1 && sb_fits(n); }
+// the largest order <= n the two-stage reduction takes (0: none).  A call whose telescope order is above the limit still
+// reduces its smaller sky-side matrices in two stages: the dynamic-LDS attributes are set for this order, not for n
+int sb_top(const dmm_ctx* ctx, int n) {
+  for (int k = n / 64 * 64; k >= 64; k -= 64)
+    if (sb_usable(ctx, k)) return k;
+  return 0;
 }
 // QL's rotation log shares the matrix's log region with the T factors and the chase's reflector log at its tail
 // "ml_rank_stop": the tolerance of the band reduction's rank stop (herm_band.h), relative to the lower bound of lambda_max
@@ -651,6 +658,14 @@ int sky_rhs(dmm_plan* pl, const void* B, const void* mvis, const double* mweight
 }
 }  // namespace
 
+// largest matrix order the two-stage reduction takes (dmm_ctx_get_counter "ml_two_stage_max_order"): the basis route of
+// a telescope above it is declined by the caller
+int dmm_ml_two_stage_max_order() {
+  for (int n = kSbRows * kThreads; n >= 64; n -= 64)
+    if (sb_fits(n)) return n;
+  return 0;
+}
+
 extern "C" {
 
 // (the Wiener solve stages the sky-side operand like ML does: same workspace layout)
@@ -945,7 +960,7 @@ int dmm_ml_run(dmm_plan* pl, const void* B, const void* mvis, const double* mwei
   };
   // resident beam bases (dmm_ctx_set_ml_basis): build = this call decomposes B B^H of the telescope-side tiles and leaves the bases
   const bool bs_have = ctx->ml_bs_U != nullptr && ctx->opt_ml_shortcut != 3 && ctx->opt_ml_reduce == 0 && sb_stop_tol(ctx) > 0.0 &&
-                       ntel <= kSbRows * kThreads && dmm_ml_gram_cache_slots(pl) <= ctx->ml_bs_slots;
+                       sb_usable(ctx, L.Np) && dmm_ml_gram_cache_slots(pl) <= ctx->ml_bs_slots;
   const bool bs_build = bs_have && ctx->ml_bs_build;
   const bool bs_use = bs_have && !ctx->ml_bs_build && (int64_t)ctx->ml_bs_rank_h.size() >= dmm_ml_gram_cache_slots(pl);
   DMM_REQUIRE(!ctx->ml_bs_build || bs_build, "dmm_ml_run: the basis build needs the two-stage reduction with its rank stop and enough slots");
@@ -1064,11 +1079,12 @@ int dmm_ml_run(dmm_plan* pl, const void* B, const void* mvis, const double* mwei
     DMM_HIP(hipFuncSetAttribute((const void*)k_td_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)td_sol));
     DMM_HIP(hipFuncSetAttribute((const void*)k_td_solve<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)td_sol));
     DMM_HIP(hipFuncSetAttribute((const void*)k_td_solve<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)td_sol));
-    if (sb_usable(ctx, L.Np)) DMM_HIP(hipFuncSetAttribute((const void*)k_sb_chase, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_chase_lds(L.Np)));
-    if (sb_usable(ctx, L.Np)) DMM_HIP(hipFuncSetAttribute((const void*)k_sb_sweep_one, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_one_lds(L.Np)));
+    const int sb_n = sb_top(ctx, L.Np);  // (sky-side matrices are smaller than L.Np: they may take two stages where it does not)
+    if (sb_n) DMM_HIP(hipFuncSetAttribute((const void*)k_sb_chase, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_chase_lds(sb_n)));
+    if (sb_n) DMM_HIP(hipFuncSetAttribute((const void*)k_sb_sweep_one, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_one_lds(sb_n)));
 #ifdef DMM_AB
-    if (sb_usable(ctx, L.Np) && ctx->opt_ml_reduce == 5) {
-      const int fl = (int)std::min(sb_fused_lds(std::min(L.Np, 3 * kThreads)), kSbFusedLdsMax);
+    if (sb_n && ctx->opt_ml_reduce == 5) {
+      const int fl = (int)std::min(sb_fused_lds(std::min(sb_n, 3 * kThreads)), kSbFusedLdsMax);
       DMM_HIP(hipFuncSetAttribute((const void*)k_sb_fused<1>, hipFuncAttributeMaxDynamicSharedMemorySize, fl));
       DMM_HIP(hipFuncSetAttribute((const void*)k_sb_fused<2>, hipFuncAttributeMaxDynamicSharedMemorySize, fl));
       DMM_HIP(hipFuncSetAttribute((const void*)k_sb_fused<3>, hipFuncAttributeMaxDynamicSharedMemorySize, fl));

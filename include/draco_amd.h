@@ -92,7 +92,9 @@ int dmm_ctx_set_option(dmm_ctx* ctx, const char* name, int64_t value);
  * Gram matrices dmm_ml_run formed, algorithmic bytes of stage 1 of its two-stage reductions: the numerators of
  * bench.py's rooflines), "ml_tiles_ql_failed"
  * (of those: tridiagonal QL did not converge, the tile was redone by the blocked Jacobi solver), "ml_early_chunks"
- * (chunks of early-known rejects decomposed beside the remaining certificate batches); with the "profile" option on,
+ * (chunks of early-known rejects decomposed beside the remaining certificate batches); read-only properties of the build:
+ * "ml_two_stage_max_order" (the largest matrix order the two-stage reduction takes: telescopes above it have no basis route),
+ * "build_ab" (1: built with -DDMM_AB, "ml_reduce" = 5 selects the one-kernel stage 1; 0: it runs the default form); with the "profile" option on,
  * "prof_<class>_us" / "prof_<class>_n" = summed HIP-event time (microseconds) and number of spans of a kernel class,
  * class = gram (Hermitian products B B^H / B^H N B), chol (factorisations + triangular solves), tridiag (Householder
  * reduction), band (two-stage reduction, stage 1: dense -> band), chase (stage 2: band -> tridiagonal), ql

@@ -494,9 +494,9 @@ def test_ml_two_stage_reduction_at_the_largest_order_the_lds_takes():
     """Orders 832 (the largest whose band plus the chase kernel's scratch fits the 160 KB of LDS) down to 64 in one
     pass: ntel = 820 on the telescope side (m <= 6), every sky-side order below it.  The reductions against each
     other -- stage 1 with every other two-sided update deferred (default), the same with its reading sweeps as one block
-    per matrix ("ml_reduce" = 3), as one kernel ("ml_reduce" = 5: only in a `make EXTRA=-DDMM_AB` build, the default form
-    otherwise), with no update deferred ("ml_reduce" = 2: rounds 3-5's form), one-stage ("ml_reduce" = 1) -- and sampled
-    rows against the oracle's SVD."""
+    per matrix ("ml_reduce" = 3), as one kernel ("ml_reduce" = 5, in a `make EXTRA=-DDMM_AB` build: counter "build_ab"),
+    with no update deferred ("ml_reduce" = 2: rounds 3-5's form), one-stage ("ml_reduce" = 1) -- and sampled rows against
+    the oracle's SVD.  In a default build "ml_reduce" = 5 runs the default form: its output is the default's, bit for bit."""
     import ctypes as C
 
     import torch
@@ -542,5 +542,8 @@ def test_ml_two_stage_reduction_at_the_largest_order_the_lds_takes():
     assert _rel(out[0], out[1]) < 1e-9
     assert _rel(out[2], out[1]) < 1e-9
     assert _rel(out[3], out[1]) < 1e-9
-    assert _rel(out[5], out[1]) < 1e-9
+    if counter(b"build_ab"):
+        assert _rel(out[5], out[1]) < 1e-9
+    else:
+        assert np.array_equal(out[5], out[0])
     _check_rows_against_oracle_svd(out[0], 36, mv, mw, 0, 0, (0, 6, 7, 100, 195, 209, 210), 1e-8)

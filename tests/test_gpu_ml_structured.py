@@ -596,7 +596,9 @@ def test_stage1_forms_keep_the_same_modes_on_structured_tiles():
     with the reading sweeps as one block per matrix ("ml_reduce" = 3), no update deferred ("ml_reduce" = 2: rounds 3-5) --
     on structured, cut-truncated tiles where the rank stop engages (the running diagonal of the deferred forms against the
     stored one of the undeferred): the same modes kept on every tile, a_lm within the solver's own resolution, and the
-    highest-rank tile against the oracle's SVD."""
+    highest-rank tile against the oracle's SVD.  "ml_reduce" = 5 is the one-kernel stage 1 of a `make EXTRA=-DDMM_AB`
+    build (counter "build_ab"), checked like the others there; in a default build it runs the default form, and its
+    output is the default's bit for bit."""
     import torch
 
     from draco_amd import _lib
@@ -639,6 +641,12 @@ def test_stage1_forms_keep_the_same_modes_on_structured_tiles():
     for red in (0, 3, 5):
         assert np.array_equal(ranks[red], ranks[2]), red
         assert np.abs(out[red] - out[2]).max() < 2e-8 * scale, (red, np.abs(out[red] - out[2]).max() / scale)
+    import ctypes
+
+    v = ctypes.c_int64()
+    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, b"build_ab", ctypes.byref(v)))
+    if not v.value:
+        assert np.array_equal(out[5], out[0])
     m = int(np.argmax(ranks[0]))
     ref, rank_o, _ = omm.ml_solve_with_spectrum(bt.beam_m(m, fi=0), mv.cpu().numpy()[m, :, 0], mw.cpu().numpy()[m, :, 0])
     assert int(ranks[0][m]) == rank_o
