@@ -27,6 +27,7 @@ DMM_C64, DMM_C128 = 0, 1
 DMM_B_FULL, DMM_B_PACKED = 0, 1
 DMM_E_ARG, DMM_E_UNSUPPORTED, DMM_E_NOMEM, DMM_E_STATE, DMM_E_COMM = -1, -2, -3, -4, -5
 DMM_MAX_NRA = 8192
+DMM_STACK_UNIFORM, DMM_STACK_INVERSE_VARIANCE = 0, 1
 
 
 class DmmError(RuntimeError):
@@ -108,6 +109,11 @@ _SIGS = {
     "dmm_beam_screen_pack": (_i, [_vp, _vp, _i, _i, C.POINTER(dmm_tile), _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "dmm_gemv_batch": (_i, [_vp, _vp, _i, C.POINTER(dmm_gemv_desc), _i64, _vp, _vp]),
     "dmm_row_median": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "dmm_regrid_plan_create": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "dmm_regrid_plan_destroy": (_i, [_vp]),
+    "dmm_regrid_band_wiener": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_sidereal_stack_add": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "dmm_sidereal_stack_finish": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i64]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -420,3 +420,71 @@ class CollateProducts(TelescopeStreamMixIn, ContainerTask):
             sp.add_dataset("input_flags", allocate=True)
             sp.input_flags[:] = flags[rev_input_ind, :]
         return sp
+
+
+class LanczosRegridder(ContainerTask):
+    """Interpolate the time-like axis of a dataset onto a regular grid (``transform.py:854-986``).
+
+    A maximum-likelihood inverse of a Lanczos interpolation: per (frequency, stack) row a banded Wiener solve, which
+    runs in ``libdraco_amd.so`` (``csrc/regrid.hip``); the Lanczos matrix is evaluated on the host
+    (``draco_amd/util/regrid.py``).  Config attributes, ``setup`` / ``process`` signatures and the out-of-bounds
+    ``RuntimeError`` are the reference's.  The output datasets stay on the device.
+    """
+
+    _config_names = ("samples", "start", "end", "kernel_width", "epsilon", "mask_zero_weight")
+    samples = 1024
+    start = None
+    end = None
+    kernel_width = 5
+    epsilon = 1e-3
+    mask_zero_weight = False
+
+    def setup(self, observer):
+        self.observer = io.get_telescope(observer)
+
+    def process(self, data):
+        data.redistribute("freq")
+        timelike_axis = data.vis.attrs["axis"][-1]
+        times = data.index_map[timelike_axis][:]
+        if self.start is None:
+            self.start = times[0]
+        if self.end is None:
+            self.end = times[-1]
+        if self.start < times[0] or self.end > times[-1]:
+            msg = "Start or end points for regridder fall outside bounds of input data."
+            self.log.error(msg)
+            raise RuntimeError(msg)
+        new_grid, new_vis, ni = self._regrid(data.vis, data.weight, times)
+        cont_type = data.__class__
+        new_data = cont_type(axes_from=data, allocate=False, **{timelike_axis: new_grid})
+        new_data.redistribute("freq")
+        new_data.attach("vis", new_vis)
+        new_data.attach("vis_weight", ni)
+        return new_data
+
+    def _regrid(self, vis_data, weight, times, mix=None):
+        """``(grid, vis, weight)`` on the regular grid; ``vis`` / ``weight`` device tensors shaped like the input with
+        the last axis replaced (``transform.py:951-986``).  ``mix``: see :func:`draco_amd.util.regrid.band_wiener`."""
+        from ..util import regrid
+
+        ctx = Context.get()
+        vis_d = _dev_dataset(vis_data, ctx, np.complex64)
+        w_d = _dev_dataset(weight, ctx, np.float32)
+        times = np.asarray(times, dtype=np.float64)
+        # a regular grid, padded at either end to suppress interpolation issues
+        pad = 5 * self.kernel_width
+        interp_grid = np.arange(-pad, self.samples + pad, dtype=np.float64) / self.samples
+        interp_grid = interp_grid * (self.end - self.start) + self.start
+        plan = regrid.RegridPlan(ctx, interp_grid, times, self.kernel_width)
+        try:
+            lead = tuple(vis_d.shape[:-1])
+            nt = int(vis_d.shape[-1])
+            sts, ni = regrid.band_wiener(ctx, plan, vis_d.reshape(-1, nt), w_d.reshape(-1, nt), self.epsilon, pad, self.samples, self.mask_zero_weight, mix)
+        finally:
+            ctx.sync()  # the plan's tables are freed with it
+            plan.close()
+        return interp_grid[pad:-pad].copy(), sts.reshape(*lead, self.samples), ni.reshape(*lead, self.samples)
+
+
+# Alias for compatibility
+Regridder = LanczosRegridder

@@ -71,6 +71,7 @@ class Dataset:
                 torch.float64: np.float64,
                 torch.int32: np.int32,
                 torch.uint8: np.uint8,
+                torch.uint16: np.uint16,
             }[self._dev_t.dtype]
         )
 
@@ -297,22 +298,38 @@ class _VisMixin:
 class SiderealStream(ContainerBase, _FreqMixin, _VisMixin):
     """``vis [freq, stack, ra]`` complex64 + ``vis_weight`` float32 (``containers.py:489-593``)."""
 
-    _axes = ("freq", "stack", "ra", "prod", "input")
+    _axes = ("freq", "stack", "ra", "prod", "input", "component")
     _dataset_spec = {
         "vis": {"axes": ["freq", "stack", "ra"], "dtype": np.complex64},
         "vis_weight": {"axes": ["freq", "stack", "ra"], "dtype": np.float32},
     }
-    _optional_spec = {"input_flags": {"axes": ["input", "ra"], "dtype": np.float32}}  # containers.py:525-530
+    _optional_spec = {
+        "input_flags": {"axes": ["input", "ra"], "dtype": np.float32},  # containers.py:525-530
+        # what SiderealStacker adds to its stack (containers.py:536-552): days per sample, variance over days (rr, ri, ii)
+        "sample_variance": {"axes": ["component", "freq", "stack", "ra"], "dtype": np.float32},
+        "nsample": {"axes": ["freq", "stack", "ra"], "dtype": np.uint16},
+    }
 
     def add_dataset(self, name, allocate=True):
         self._dataset_spec = dict(self._dataset_spec)
         self._dataset_spec[name] = self._optional_spec[name]
+        if "component" in self._optional_spec[name]["axes"] and "component" not in self.index_map:
+            self.index_map["component"] = np.array(["rr", "ri", "ii"])
+            self.index_attrs["component"] = {}
         if allocate:
             self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=self._optional_spec[name]["dtype"]))
 
     @property
     def input_flags(self):
         return self.datasets["input_flags"]
+
+    @property
+    def nsample(self):
+        return self.datasets["nsample"]
+
+    @property
+    def sample_variance(self):
+        return self.datasets["sample_variance"]
 
     @property
     def is_stacked(self):
@@ -344,6 +361,32 @@ class SiderealStream(ContainerBase, _FreqMixin, _VisMixin):
         t["input_a"] = np.where(conj, prod[stack["prod"]]["input_b"], prod[stack["prod"]]["input_a"])
         t["input_b"] = np.where(conj, prod[stack["prod"]]["input_a"], prod[stack["prod"]]["input_b"])
         return t
+
+
+class TimeStream(ContainerBase, _FreqMixin, _VisMixin):
+    """Time-ordered visibilities: ``vis [freq, stack, time]`` complex64 + ``vis_weight`` float32, ``time`` the samples'
+    UNIX time stamps (``containers.py:1195-1242``; gain and input_flags datasets are not carried)."""
+
+    _axes = ("freq", "stack", "time", "prod", "input")
+    _dataset_spec = {
+        "vis": {"axes": ["freq", "stack", "time"], "dtype": np.complex64},
+        "vis_weight": {"axes": ["freq", "stack", "time"], "dtype": np.float32},
+    }
+
+    def __init__(self, time=None, stack=None, prod=None, input=None, reverse_map_stack=None, **kwargs):
+        if time is not None and not isinstance(time, (int, np.integer)):
+            time = np.asarray(time, dtype=np.float64)
+        if stack is None and prod is not None and kwargs.get("axes_from") is None:
+            stack = len(prod)
+        super().__init__(time=time, stack=stack, prod=prod, input=input, **kwargs)
+        if reverse_map_stack is not None:
+            self.reverse_map["stack"] = reverse_map_stack
+
+    @property
+    def time(self):
+        return self.index_map["time"]
+
+    prodstack = SiderealStream.prodstack
 
 
 class MContainer(ContainerBase):

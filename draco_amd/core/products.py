@@ -71,7 +71,14 @@ class TransitTelescope:
     cyl_sep = 22.0      # metres between cylinder centres (east-west)
     feed_sep = 0.3048   # metres between feed positions along a cylinder (north-south)
 
-    def __init__(self, frequencies, lmax, mmax=None, num_pol_sky=4, ncyl=1, nfeed_cyl=8, npol_feed=2, npairs=None, pair_rule="canonical"):
+    #: length of a sidereal day in SI seconds (the linear time map below; caput's Observer [3P] uses skyfield)
+    SIDEREAL_S = 86164.0905
+
+    def __init__(self, frequencies, lmax, mmax=None, num_pol_sky=4, ncyl=1, nfeed_cyl=8, npol_feed=2, npairs=None, pair_rule="canonical",
+                 latitude=49.3, longitude=0.0, lsd_start=0.0):
+        #: observer position in degrees and the UNIX time at which local sidereal day 0 starts AT LONGITUDE 0: what
+        #: `unix_to_lsd` / `lsd_to_unix` (SiderealRegridder's time map) are built from
+        self.latitude, self.longitude, self.lsd_start = float(latitude), float(longitude), float(lsd_start)
         #: how a redundancy class picks its representative pair.  "canonical" (default): the smaller of the pair's key and
         #: its conjugate's -- XY at separation d and YX at -d are one class.  "halfplane": the member whose separation
         #: pos_a - pos_b lies in the half plane x > 0 (x = 0: y > 0; same position: feed order) -- every class then has
@@ -92,6 +99,18 @@ class TransitTelescope:
             self.npairs = int(npairs)
             self.uniquepairs = np.stack([np.zeros(self.npairs, int), np.arange(self.npairs)], axis=1)
             self._free = True
+
+    def unix_to_lsd(self, unix):
+        """Local sidereal day (integer part: day number, fraction: sidereal angle / 360 deg) of UNIX times.
+
+        A LINEAR map -- ``(unix - lsd_start) / 86164.0905 + longitude / 360`` -- standing in for caput's
+        ``Observer.unix_to_lsd`` [3P], which follows the Earth's rotation through skyfield: no precession, nutation or
+        leap seconds (INTEGRATION.md marks it unpinned).  The tasks call whatever observer they are given."""
+        return (np.asarray(unix, dtype=np.float64) - self.lsd_start) / self.SIDEREAL_S + self.longitude / 360.0
+
+    def lsd_to_unix(self, lsd):
+        """Inverse of :meth:`unix_to_lsd`."""
+        return (np.asarray(lsd, dtype=np.float64) - self.longitude / 360.0) * self.SIDEREAL_S + self.lsd_start
 
     def _build_pairs(self):
         """Redundancy of a regular cylinder grid, autos included."""

@@ -139,6 +139,7 @@ int dmm_ctx_set_option(dmm_ctx* c, const char* name, int64_t value) {
   else if (!strcmp(name, "gram_stage")) c->opt_gram_stage = (int)value;
   else if (!strcmp(name, "wiener_overlap")) c->opt_wiener_overlap = (int)value;
   else if (!strcmp(name, "ml_workspace_mib")) c->opt_ml_ws_mib = value > 0 ? value : 0;
+  else if (!strcmp(name, "regrid_workspace_mib")) c->opt_regrid_ws_mib = value > 0 ? value : 0;
   else if (!strcmp(name, "wiener_workspace_mib")) c->opt_wiener_ws_mib = value > 0 ? value : 0;
   else if (!strcmp(name, "profile")) {  // (re)start the per-class kernel timing: sums cleared
     prof_collect(c);

@@ -47,6 +47,7 @@ struct dmm_ctx {
   int opt_sht_variant = 0;
   int opt_sht_synth_form = 0;  // 1: the first MFMA form of the Legendre synthesis whatever sht_variant says (the map-makers' alm2map)
   int opt_ml_eigen = 0;                    // 0: by batch size (tridiagonalisation + QL for large batches, blocked Jacobi for a few matrices); 1: Jacobi; 4: tridiagonal; 2: tridiagonal with full-matrix trailing updates; 3: tridiagonal with QL made to give up (Jacobi fallback)
+  int64_t opt_regrid_ws_mib = 0;           // scratch the regridder sizes its row chunks for (0: 12 GiB)
   int64_t opt_ml_ws_mib = 0, opt_wiener_ws_mib = 0;  // workspace the ML / Wiener solves size themselves for (0: 20 / 6 GiB)
   int opt_ml_shortcut = 0;                 // 0/1: certified full-rank shortcut on; 2: eigen path always; 3: telescope side only
   int ml_probe_every = 8;                  // how thinly dmm_ml_run probes the certificate while the probes keep failing (8 ... 64 batches; remembered with the rate)

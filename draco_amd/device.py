@@ -21,6 +21,8 @@ _NP2TORCH = {
     np.dtype(np.float64): torch.float64,
     np.dtype(np.int32): torch.int32,
     np.dtype(np.uint8): torch.uint8,
+    np.dtype(np.uint16): torch.uint16,
+    np.dtype(np.int16): torch.int16,
 }
 
 

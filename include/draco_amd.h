@@ -78,7 +78,7 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *    (0 sampled null certificate, 1 off, 2 every tile), "ml_reduce" (0 two-stage with every other update deferred;
  *    3 its reading sweeps as one block per matrix; 2 none deferred; 1 one-stage), "ml_chase_split" (1: one chase launch with the full band image), "gram_stage"
  *    (1: LDS-DMA operand staging of the Gram kernel), "wiener_overlap" (0: one stream);
- *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "grid_mult", "project_grid_mult";
+ *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "regrid_workspace_mib" (0 = 12 GiB: a cfg-3 day in one launch), "grid_mult", "project_grid_mult";
  *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio", "project_variant", "ringmap_variant" (1 three-kernel
  *    form, 2 eight elevations per block), "sht_variant" (bits: 0-1 vector-ALU synthesis form, 2 direct ring sums,
  *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x in the analysis, 6 first MFMA synthesis form,
@@ -427,6 +427,51 @@ int dmm_gemv_batch(dmm_ctx* ctx, const void* A, int a_dtype, const dmm_gemv_desc
 /* out[r] = np.median(x[r, :]) for a [nrow, per_row] float64 array [dev] -- the weight the reference carries over to
  * the projected container (fgfilter.py:94,141,200,236: `np.median(mmodes.weight[mi])`). */
 int dmm_row_median(dmm_ctx* ctx, const double* x, int64_t nrow, int64_t per_row, double* out);
+
+/* ------------------------------------------------- sidereal regridding and day stacking
+ * dmm_regrid_band_wiener replaces regrid.band_wiener (reference draco/util/regrid.py:14-89, with the compiled
+ * _fast_tools._linear_covariance_banded, _fast_tools.pyx:59-88, and scipy's solveh_banded) as LanczosRegridder._regrid
+ * calls it (draco/analysis/transform.py:951-986), the mix-down / mix-up of SiderealRegridder.process
+ * (draco/analysis/sidereal.py:221-234, 256-278) fused into its load and store.  Per row k of `nrow` (one (frequency,
+ * stack) pair), with R [ngrid, nt] the Lanczos matrix of the padded grid and bw = 2 kernel_width - 1:
+ *   d = R (Ni_k o y_k),  C = band_bw(R diag(Ni_k) R^T),  nw = diag(C),  x = (C + eps I)^-1 d   (banded Cholesky)
+ * all in float64 from the float32 / complex64 inputs; the first and last `pad` grid points are dropped, x is returned
+ * as complex64 and nw as float32 (the reference's dtypes).  A row whose weights are all zero comes out as exact zeros.
+ *
+ * A plan holds R, which depends on the times only: per grid point g its span [span_start[g], span_end[g]) of time
+ * samples with non-zero kernel values (empty where no sample is in reach: span_start = span_end) and, concatenated in
+ * grid order, those values R[g, span_start[g] .. span_end[g]) as float64 -- lanczos_forward_matrix(grid, times).T
+ * (regrid.py:109-135) evaluated on the host, no sinc on the device.  All three [host].  kernel_width 1 ... 6; a span
+ * may hold at most 210 samples (the kernel's LDS tile) -- DMM_E_UNSUPPORTED otherwise.
+ *
+ * vis [nrow, nt] complex64, weight [nrow, nt] float32, out_vis [nrow, samples] complex64, out_weight [nrow, samples]
+ * float32: [dev].  samples + 2 pad = the plan's ngrid.  mask_zero_weight: zero the weight of rows that had no non-zero
+ * weight among the samples the grid reaches (transform.py:981-984).  Mixing (all four arrays [dev], or all NULL):
+ * omega [nrow] float64 fringe rate, feed_mask [nrow] float32, dphi_in [nt] / dphi_out [samples] float64 sidereal
+ * angle of the input samples / of the kept grid points (sidereal.py:256-278): the input is multiplied by
+ * feed_mask exp(-i omega dphi_in) as it is loaded (rounded to complex64, as the reference's in-place product is),
+ * the output by the conjugate factor at dphi_out as it is stored, and the weight of rows with feed_mask = 0 is zeroed.
+ * The factor rows go through the context's scratch, rows in chunks sized by the "regrid_workspace_mib" option. */
+typedef struct dmm_regrid_plan dmm_regrid_plan;
+int dmm_regrid_plan_create(dmm_ctx* ctx, int nt, int ngrid, int kernel_width, const int32_t* span_start, const int32_t* span_end,
+                           const double* kernel_values, dmm_regrid_plan** plan);
+int dmm_regrid_plan_destroy(dmm_regrid_plan* plan);
+int dmm_regrid_band_wiener(dmm_ctx* ctx, const dmm_regrid_plan* plan, const void* vis, const float* weight, int64_t nrow, double eps,
+                           int pad, int samples, int mask_zero_weight, const double* omega, const float* feed_mask,
+                           const double* dphi_in, const double* dphi_out, void* out_vis, float* out_weight);
+/* SiderealStacker (draco/analysis/sidereal.py:834-1080), one fused element-wise launch per day: West's update of the
+ * running mean `stack_vis` (complex64) and, with_variance, of the three sums of squared differences
+ * `sample_variance` [3, n] float32 and of `sum_coeff_sq` [n] float32 (:975-1030), float32 state and the reference's
+ * order of operations.  mode: DMM_STACK_UNIFORM / DMM_STACK_INVERSE_VARIANCE.  day_nsample [n] uint16 or NULL (the day
+ * is a single day: count = weight > 0).  Divisions are invert_no_zero (0 where the divisor is 0).  The caller zeroes
+ * the state before the first day.  dmm_sidereal_stack_finish is process_finish (:1032-1065): the weight normalisation
+ * of the uniform mode and Bessel's correction of the sample variance.  All arrays [dev], n elements = freq * stack * ra. */
+enum { DMM_STACK_UNIFORM = 0, DMM_STACK_INVERSE_VARIANCE = 1 };
+int dmm_sidereal_stack_add(dmm_ctx* ctx, int mode, int with_variance, const void* day_vis, const float* day_weight,
+                           const uint16_t* day_nsample, void* stack_vis, float* stack_weight, uint16_t* stack_nsample,
+                           float* sum_coeff_sq, float* sample_variance, int64_t n);
+int dmm_sidereal_stack_finish(dmm_ctx* ctx, int mode, int with_variance, float* stack_weight, const uint16_t* stack_nsample,
+                              const float* sum_coeff_sq, float* sample_variance, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """End-to-end example: sky -> SimulateSidereal -> (noise) -> MModeTransform -> {Dirty, Wiener, ML}MapMaker.
 
-    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise]
+    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise] [--regrid]
+
+--regrid: the simulated day is first sampled onto irregular time stamps (jitter, a gap, flagged samples) as a TimeStream
+and brought back to the RA grid by SiderealRegridder before the m-mode transform.
 
 Mirrors the reference's tutorial pipeline (doc/pipeline_params.yaml:1-35) with this repo's
 task classes.  Prints per-task wall time (device synchronised) and a few sanity numbers.
@@ -23,6 +26,7 @@ def main():
     ap.add_argument("--config", type=int, default=1)
     ap.add_argument("--makers", nargs="*", default=["dirty", "wiener"])
     ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--regrid", action="store_true", help="go through an irregular TimeStream and SiderealRegridder")
     ap.add_argument("--nfreq", type=int, default=0, help="override the number of frequencies")
     ap.add_argument("--pool-gb", type=float, default=0.0, help="B pool budget in GB (default: 0.6 of the free HBM)")
     args = ap.parse_args()
@@ -83,6 +87,31 @@ def main():
         gn = GaussianNoise(seed=1, ndays=733.0, recv_temp=50.0)
         gn.setup(tel)
         ss = timed("GaussianNoise_host", lambda: gn.process(ss))
+    if args.regrid:
+        from draco_amd.analysis.sidereal import SiderealRegridder
+        from draco_amd.util import regrid
+
+        nra, lsd, a = ss.vis.shape[-1], 100, 5
+        rng = np.random.default_rng(7)
+        nt = 2 * nra
+        lsds = np.sort(lsd + np.linspace(-0.03, 1.03, nt) + rng.uniform(-0.3, 0.3, nt) * 1.06 / nt)
+        lsds = lsds[(lsds < lsd + 0.5) | (lsds > lsd + 0.5 + 2.0 * a / nra)]
+        pad = 5 * a
+        grid = lsd + np.arange(-pad, nra + pad, dtype=np.float64) / nra
+        R = torch.from_numpy(regrid.lanczos_forward_matrix(grid, lsds, a).astype(np.float32)).to(ctx.device)  # [nt, ngrid]
+        idx = torch.from_numpy(np.arange(-pad, nra + pad) % nra).to(ctx.device)
+        sv = ss.vis.device(ctx)[..., idx]  # the day is periodic
+        ts = containers.TimeStream(axes_from=ss, attrs_from=ss, time=tel.lsd_to_unix(lsds), allocate=False)
+        ts.attach("vis", torch.complex(sv.real @ R.T, sv.imag @ R.T).contiguous())
+        tw = torch.ones(ts.vis.shape, dtype=torch.float32, device=ctx.device)
+        tw[..., :: 7] = 0.0
+        ts.attach("vis_weight", tw)
+        ts.attrs["lsd"] = lsd
+        rg = SiderealRegridder(samples=nra, kernel_width=a)
+        rg.setup(tel)
+        timed("SiderealRegridder_first_call", lambda: rg.process(ts))
+        sr = timed("SiderealRegridder", lambda: rg.process(ts))
+        ss = sr
     tr = MModeTransform()
     tr.setup(bt)
     mm = timed("MModeTransform", lambda: tr.process(ss))
