@@ -8,6 +8,7 @@ bulk by the provider, described by a ``dmm_tile`` table (``include/draco_amd.h``
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -126,6 +127,7 @@ class Slab:
         if pool is None or pool.numel() < self.nelem or pool.dtype != _TORCH[b_dtype]:
             pool = torch.empty(max(self.nelem, 1), dtype=_TORCH[b_dtype], device=ctx.device)
         self.pool = pool
+        self.buf = None  # the `_Buffer` of the device's B block the tiles are in (`SolveEngine.slabs`); None: `pool` is the slab's own
         if fill:
             provider.fill_pool(ctx, pool, self.fill_tiles, b_dtype, b_layout)
         h = C.c_void_p()
@@ -178,13 +180,11 @@ class SolveEngine:
         self.b_layout = b_layout
         self.pool_bytes = pool_bytes
         self.cache = cache
-        self._cached_key = None
-        self._cached_slabs = None
         self._plans: dict = {}
         self._plan_keys: list = []  # keys of `_plans` entries, least recently used first
         self.last_b_bytes = 0
         self.fills = 0  # slabs actually filled (the others were resident)
-        self.launch_events = None  # set to a list to collect (start, stop, b_bytes, ntile) per Dirty launch
+        self.launch_events = None  # set to a list to collect (start, stop, b_bytes, ntile) per Dirty / project launch
         self._ws_offer = {}
         self._basis_wkey = None
         self._ws = None
@@ -263,9 +263,6 @@ class SolveEngine:
         fs_data = np.repeat(np.arange(nf, dtype=np.int32), mmax + 1)
         fs_bt = np.repeat(np.asarray(freq_ind, dtype=np.int32), mmax + 1)
         key = (tuple(int(f) for f in freq_ind), int(mmax), int(nfreq_data), int(n_m), self.b_dtype, self.b_layout)
-        if self._cached_key == key and self._cached_slabs is not None:  # a slab installed by hand (single-tile solves)
-            yield from self._cached_slabs
-            return
         ctx = self.ctx
         ranges = self._slab_ranges(ms, mmax + 1)
         # plans are keyed by slab range; the ranges follow the HBM budget, which may drift between passes (free memory):
@@ -329,7 +326,7 @@ class SolveEngine:
     basis_max_weight_ratio = 1e6
 
     def _basis_weights_ok(self, weights):
-        """One reduction and one host read per CALL of solve / solve_many (not per slab): the verdict is remembered for
+        """One reduction and one host read per CALL of solve_many (not per slab): the verdict is remembered for
         the weight arrays it was taken on and forgotten when the next call starts -- the next day's weights are normally
         handed the same block by the caching allocator, with the same version counter."""
         key = tuple((int(w.data_ptr()), int(w._version), tuple(w.shape)) for w in weights)
@@ -341,14 +338,15 @@ class SolveEngine:
             self._basis_wkey = key
         return self._basis_wok
 
-    def _basis_on(self, slab, mvis_d, mweight_d, params, ws, alm, weights=None):
+    def _basis_on(self, slab, mvis_d, weights, params, ws, alm):
         """Hand the library the resident singular bases of the slab's buffer (``basis_cache``), building them first -- one
-        decomposition of B B^H per telescope-side tile, with unit weights -- when the buffer holds other tiles than the
-        ones they were computed from.  Not for days whose weights span too many decades (``basis_max_weight_ratio``)."""
-        buf = getattr(slab, "buf", None)
+        decomposition of B B^H per telescope-side tile, with unit weights, into day 0's ``mvis_d`` / ``alm`` -- when the
+        buffer holds other tiles than the ones they were computed from.  Not for a call any of whose days' ``weights``
+        span too many decades (``basis_max_weight_ratio``)."""
+        buf = slab.buf
         if not self.basis_cache or buf is None or buf.content is None:
             return False
-        if not self._basis_weights_ok(weights if weights is not None else [mweight_d]):
+        if not self._basis_weights_ok(weights):
             return False
         lib = _lib.lib
         nslots = int(lib.dmm_ml_gram_cache_slots(slab.plan))
@@ -369,7 +367,7 @@ class SolveEngine:
         if buf.basis_content != buf.content:
             _lib.check(lib.dmm_ctx_set_ml_basis(self.ctx.handle, ptr(U), ptr(sg), ptr(rk), nslots, rmax, 1))
             try:
-                ones = torch.ones_like(mweight_d)
+                ones = torch.ones_like(weights[0])
                 _lib.check(lib.dmm_ml_run(slab.plan, ptr(slab.pool), ptr(mvis_d), ptr(ones), float(params.get("acond", 1e-4)),
                                           float(params.get("rcond", 1e-3)), ptr(ws), ptr(alm)))
                 torch.cuda.current_stream(self.ctx.device).synchronize()  # (`ones` dies here)
@@ -384,7 +382,7 @@ class SolveEngine:
         """Hand the library the resident beam Gram products of the slab's buffer (``gram_cache``): the arrays live with
         the buffer and are started over whenever it holds other tiles than the ones they were computed from -- or the
         products of another maker / prior (``tag``: ML keeps B B^H, Wiener B S B^H)."""
-        buf = getattr(slab, "buf", None)
+        buf = slab.buf
         if not self.gram_cache or buf is None or buf.content is None:
             return False
         lib = _lib.lib
@@ -405,81 +403,40 @@ class SolveEngine:
         return True
 
     # ---- the four batched operations
-    def solve(self, kind, mvis_d, mweight_d, freq_ind, mmax, on_freqs_done=None, **params):
-        """``alm [nfreq, npol, mmax+1, lmax+1]`` complex128 on the device.
+    @contextlib.contextmanager
+    def _timed(self, slab):
+        """Around one slab launch: with ``launch_events`` a list, HIP events on the launch stream before and after it
+        are appended as ``(start, stop, b_bytes, ntile)`` (read by the caller after a sync)."""
+        if self.launch_events is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        self.launch_events.append((e0, e1, slab.b_bytes, slab.ntile))
 
-        ``on_freqs_done(alm, f0, f1)`` is called after each slab's launch with the range of
+    def solve(self, kind, mvis_d, mweight_d, freq_ind, mmax, on_freqs_done=None, slabs=None, **params):
+        """One day: ``alm [nfreq, npol, mmax+1, lmax+1]`` complex128 on the device.
+
+        :meth:`solve_many` of a group of one -- the same launches (``dmm_dirty_run_multi`` hands a single day to the
+        one-day kernel).  ``on_freqs_done(alm, f0, f1)`` is called after each slab's launch with the range of
         (data) frequencies whose every m has now been issued, so a caller can start the next
         stage for them on another stream while the following slab is filled and solved.
         """
-        tel = self.provider.telescope
-        n_m_data, _, nfreq, npairs = mvis_d.shape
-        if npairs != tel.npairs:
-            raise ValueError(f"m-modes have {npairs} baselines, the beam transfers {tel.npairs}")
-        n_m = mmax + 1
-        alm = torch.empty((nfreq, tel.num_pol_sky, n_m, tel.lmax + 1), dtype=torch.complex128, device=self.ctx.device)
-        self.last_b_bytes = 0
-        self._ws_offer = {}
-        self._basis_wkey = None  # (the weight-range verdict of the resident bases is per call)
-        self._ws = None
-        lib = _lib.lib
-        issued, f_done = 0, 0
-        for slab in self.slabs(freq_ind, mmax, nfreq, n_m):
-            self.last_b_bytes += slab.b_bytes
-            if kind == "dirty":
-                if self.launch_events is not None:  # HIP events on the launch stream, read by the caller after a sync
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                _lib.check(lib.dmm_dirty_run(slab.plan, ptr(slab.pool), ptr(mvis_d), ptr(mweight_d), ptr(alm)))
-                if self.launch_events is not None:
-                    e1.record()
-                    self.launch_events.append((e0, e1, slab.b_bytes, slab.ntile))
-            elif kind == "wiener":
-                self._offer_workspace(b"wiener_workspace_mib", 24 << 10)  # 0.0649 -> 0.0620 ms per cfg-3 solve against 6 GiB
-                ws = self._workspace(int(lib.dmm_wiener_workspace_bytes(slab.plan)))
-                cached = self._gram_cache_on(slab, ("wiener", float(params["prior_amp"]), float(params["prior_tilt"])))
-                try:
-                    _lib.check(
-                        lib.dmm_wiener_run(
-                            slab.plan, ptr(slab.pool), ptr(mvis_d), ptr(mweight_d), float(params["prior_amp"]), float(params["prior_tilt"]), ptr(ws), ptr(alm)
-                        )
-                    )
-                finally:
-                    if cached:
-                        _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
-            elif kind == "ml":
-                self._offer_workspace(b"ml_workspace_mib", 64 << 10)
-                ws = self._workspace(int(lib.dmm_ml_workspace_bytes(slab.plan)))
-                based = self._basis_on(slab, mvis_d, mweight_d, params, ws, alm)
-                cached = self._gram_cache_on(slab)
-                try:
-                    _lib.check(
-                        lib.dmm_ml_run(
-                            slab.plan, ptr(slab.pool), ptr(mvis_d), ptr(mweight_d), float(params.get("acond", 1e-4)), float(params.get("rcond", 1e-3)), ptr(ws), ptr(alm)
-                        )
-                    )
-                finally:
-                    if cached:
-                        _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
-                    if based:
-                        _lib.check(lib.dmm_ctx_set_ml_basis(self.ctx.handle, None, None, None, 0, 0, 0))
-            else:
-                raise ValueError(kind)
-            issued += slab.ntile  # slabs are consecutive ranges of the f-major, m-minor tile list
-            if on_freqs_done is not None and issued // n_m > f_done:
-                on_freqs_done(alm, f_done, issued // n_m)
-                f_done = issued // n_m
-        self._ws = None
-        return alm
+        cb = None if on_freqs_done is None else (lambda d, alm, f0, f1: on_freqs_done(alm, f0, f1))
+        return self.solve_many(kind, [mvis_d], [mweight_d], freq_ind, mmax, on_freqs_done=cb, slabs=slabs, **params)[0]
 
-    def solve_many(self, kind, mvis_l, mweight_l, freq_ind, mmax, on_freqs_done=None, **params):
-        """D sidereal days against ONE pass over B: a list of ``alm`` as :meth:`solve` returns them, one per day.
+    def solve_many(self, kind, mvis_l, mweight_l, freq_ind, mmax, on_freqs_done=None, slabs=None, **params):
+        """D sidereal days against ONE pass over B: a list of ``alm``, one per day.  The slab loop of every solve.
 
         Every slab of B is made resident once (one PCIe crossing for providers whose tiles live on the host) and
         serves all D days before the next slab replaces it.  ``"dirty"``: ``dmm_dirty_run_multi`` -- up to eight days
         share every tile READ too (the kernel keeps eight accumulators per column), each day bit-identical to its
         own :meth:`solve`.  ``"wiener"`` / ``"ml"``: the Gram matrices depend on the day's noise weights, so the days
         run one after the other inside the slab.  ``on_freqs_done(d, alm_d, f0, f1)`` as in :meth:`solve`, per day.
+        ``slabs``: ready :class:`Slab` objects to run instead of the engine's own carving of (``freq_ind``, m <= ``mmax``)
+        -- a hand-made tile list, its pool filled by the caller (single-tile solves).
         """
         tel = self.provider.telescope
         D = len(mvis_l)
@@ -490,10 +447,13 @@ class SolveEngine:
         shape = tuple(mvis_l[0].shape)
         for v, w in zip(mvis_l, mweight_l):
             if tuple(v.shape) != shape or tuple(w.shape) != shape:
-                raise ValueError("solve_many: every day must have the same [m, msign, freq, stack] shape")
+                raise ValueError("solve_many: the m-modes and weights of every day must have the same [m, msign, freq, stack] shape")
         n_m_data, _, nfreq, npairs = shape
         if npairs != tel.npairs:
             raise ValueError(f"m-modes have {npairs} baselines, the beam transfers {tel.npairs}")
+        run = {"dirty": self._run_dirty, "wiener": self._run_wiener, "ml": self._run_ml}.get(kind)
+        if run is None:
+            raise ValueError(kind)
         n_m = mmax + 1
         # (ONE allocation for the group: the caching allocator then recycles one block per group instead of juggling D of them
         # against the side stream's events -- every fresh hipMalloc of a few GB stalls the device for tens of milliseconds)
@@ -501,56 +461,58 @@ class SolveEngine:
         alms = [alm_all[d] for d in range(D)]
         self.last_b_bytes = 0
         self._ws_offer = {}
-        self._basis_wkey = None
+        self._basis_wkey = None  # (the weight-range verdict of the resident bases is per call)
         self._ws = None
-        lib = _lib.lib
-        PA = C.c_void_p * D
-        pv, pw, pa = PA(*[ptr(x) for x in mvis_l]), PA(*[ptr(x) for x in mweight_l]), PA(*[ptr(x) for x in alms])
         issued, f_done = 0, 0
-        for slab in self.slabs(freq_ind, mmax, nfreq, n_m):
+        for slab in slabs if slabs is not None else self.slabs(freq_ind, mmax, nfreq, n_m):
             self.last_b_bytes += slab.b_bytes
-            if kind == "dirty":
-                if self.launch_events is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                _lib.check(lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, D))
-                if self.launch_events is not None:
-                    e1.record()
-                    self.launch_events.append((e0, e1, slab.b_bytes, slab.ntile))
-            elif kind == "wiener":
-                self._offer_workspace(b"wiener_workspace_mib", 24 << 10)
-                ws = self._workspace(int(lib.dmm_wiener_workspace_bytes(slab.plan)))
-                cached = self._gram_cache_on(slab, ("wiener", float(params["prior_amp"]), float(params["prior_tilt"])))
-                try:
-                    for d in range(D):
-                        _lib.check(lib.dmm_wiener_run(slab.plan, ptr(slab.pool), ptr(mvis_l[d]), ptr(mweight_l[d]), float(params["prior_amp"]),
-                                                      float(params["prior_tilt"]), ptr(ws), ptr(alms[d])))
-                finally:
-                    if cached:
-                        _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
-            elif kind == "ml":
-                self._offer_workspace(b"ml_workspace_mib", 64 << 10)
-                ws = self._workspace(int(lib.dmm_ml_workspace_bytes(slab.plan)))
-                based = self._basis_on(slab, mvis_l[0], mweight_l[0], params, ws, alms[0], weights=mweight_l)
-                cached = self._gram_cache_on(slab)
-                try:
-                    for d in range(D):
-                        _lib.check(lib.dmm_ml_run(slab.plan, ptr(slab.pool), ptr(mvis_l[d]), ptr(mweight_l[d]), float(params.get("acond", 1e-4)),
-                                                  float(params.get("rcond", 1e-3)), ptr(ws), ptr(alms[d])))
-                finally:
-                    if cached:
-                        _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
-                    if based:
-                        _lib.check(lib.dmm_ctx_set_ml_basis(self.ctx.handle, None, None, None, 0, 0, 0))
-            else:
-                raise ValueError(kind)
-            issued += slab.ntile
+            run(slab, mvis_l, mweight_l, alms, params)
+            issued += slab.ntile  # slabs are consecutive ranges of the f-major, m-minor tile list
             if on_freqs_done is not None and issued // n_m > f_done:
                 for d in range(D):
                     on_freqs_done(d, alms[d], f_done, issued // n_m)
                 f_done = issued // n_m
         self._ws = None
         return alms
+
+    def _run_dirty(self, slab, mvis_l, mweight_l, alms, params):
+        """One slab's Dirty launch for all days (always the multi-day entry: with one day it makes the launch of
+        ``dmm_dirty_run``)."""
+        PA = C.c_void_p * len(alms)
+        pv, pw, pa = PA(*[ptr(x) for x in mvis_l]), PA(*[ptr(x) for x in mweight_l]), PA(*[ptr(x) for x in alms])
+        with self._timed(slab):
+            _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, len(alms)))
+
+    def _run_wiener(self, slab, mvis_l, mweight_l, alms, params):
+        """One slab's Wiener solves, day after day."""
+        lib = _lib.lib
+        amp, tilt = float(params["prior_amp"]), float(params["prior_tilt"])
+        self._offer_workspace(b"wiener_workspace_mib", 24 << 10)  # 0.0649 -> 0.0620 ms per cfg-3 solve against 6 GiB
+        ws = self._workspace(int(lib.dmm_wiener_workspace_bytes(slab.plan)))
+        cached = self._gram_cache_on(slab, ("wiener", amp, tilt))
+        try:
+            for v, w, alm in zip(mvis_l, mweight_l, alms):
+                _lib.check(lib.dmm_wiener_run(slab.plan, ptr(slab.pool), ptr(v), ptr(w), amp, tilt, ptr(ws), ptr(alm)))
+        finally:
+            if cached:
+                _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
+
+    def _run_ml(self, slab, mvis_l, mweight_l, alms, params):
+        """One slab's maximum-likelihood solves, day after day."""
+        lib = _lib.lib
+        self._offer_workspace(b"ml_workspace_mib", 64 << 10)
+        ws = self._workspace(int(lib.dmm_ml_workspace_bytes(slab.plan)))
+        based = self._basis_on(slab, mvis_l[0], mweight_l, params, ws, alms[0])
+        cached = self._gram_cache_on(slab)
+        try:
+            for v, w, alm in zip(mvis_l, mweight_l, alms):
+                _lib.check(lib.dmm_ml_run(slab.plan, ptr(slab.pool), ptr(v), ptr(w), float(params.get("acond", 1e-4)),
+                                          float(params.get("rcond", 1e-3)), ptr(ws), ptr(alm)))
+        finally:
+            if cached:
+                _lib.check(lib.dmm_ctx_set_ml_gram_cache(self.ctx.handle, None, None, 0, 0))
+            if based:
+                _lib.check(lib.dmm_ctx_set_ml_basis(self.ctx.handle, None, None, None, 0, 0, 0))
 
     def _workspace(self, nbytes):
         """The pass's workspace: one allocation, reused by every slab it is large enough for (the library drains its
@@ -565,7 +527,7 @@ class SolveEngine:
         are allocated by now): half of it, at most ``cap_mib``.  The ML eigen pass pays a fixed cost per Householder
         column; with 64 GiB (1400 cfg-3 matrices per half-batch instead of 357) that cost is shared four times wider.
 
-        Decided ONCE per pass (``solve`` clears ``_ws_offer``): the driver's free-memory figure does not count blocks
+        Decided ONCE per pass (``solve_many`` clears ``_ws_offer``): the driver's free-memory figure does not count blocks
         torch holds in its cache, so asking again per slab gave a slightly different size each time -- and a new
         allocation of tens of GiB per slab.  What torch has reserved but not handed out is ours as well."""
         if option in self._ws_offer:
@@ -587,13 +549,8 @@ class SolveEngine:
         self.last_b_bytes = 0
         for slab in self.slabs(freq_ind, mmax, nfreq, n_m):
             self.last_b_bytes += slab.b_bytes
-            if self.launch_events is not None:  # (HIP events on the launch stream, as around the Dirty launches)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _lib.check(_lib.lib.dmm_project_run(slab.plan, ptr(slab.pool), ptr(alm_d), ptr(vis)))
-            if self.launch_events is not None:
-                e1.record()
-                self.launch_events.append((e0, e1, slab.b_bytes, slab.ntile))
+            with self._timed(slab):
+                _lib.check(_lib.lib.dmm_project_run(slab.plan, ptr(slab.pool), ptr(alm_d), ptr(vis)))
         return vis
 
 

@@ -127,19 +127,26 @@ class BaseMapMaker(ContainerTask):
         return {}
 
     def make_alm(self, mmodes, on_freqs_done=None):
-        """All (m, f) solves: device ``alm [nfreq, npol, mmax+1, lmax+1]`` (``mapmaker.py:50-94``)."""
-        bt = self.beamtransfer
-        mmax = min(bt.telescope.mmax, len(mmodes.index_map["m"]) - 1)
-        bt_freq = bt.telescope.frequencies
-        mm_freq = mmodes.index_map["freq"]["centre"]
-        freq_ind = tools.find_keys(bt_freq, mm_freq, require_match=True)  # ValueError on a miss (:59)
+        """All (m, f) solves of one day: device ``alm [nfreq, npol, mmax+1, lmax+1]`` (``mapmaker.py:50-94``).
+        :meth:`make_alm_many` of a group of one; ``on_freqs_done(alm, f0, f1)`` as ``SolveEngine.solve`` calls it."""
+        cb = None if on_freqs_done is None else (lambda d, alm, f0, f1: on_freqs_done(alm, f0, f1))
+        return self.make_alm_many([mmodes], on_freqs_done=cb)[0]
 
-        mmodes.redistribute("freq")
+    def make_alm_many(self, mmodes_list, on_freqs_done=None):
+        """The a_lm of D days from one pass over B (see :meth:`process_many`): a list of device arrays
+        ``[nfreq, npol, mmax+1, lmax+1]``, one per day."""
+        bt = self.beamtransfer
+        first = mmodes_list[0]
+        mmax = min(bt.telescope.mmax, len(first.index_map["m"]) - 1)
+        freq_ind = tools.find_keys(bt.telescope.frequencies, first.index_map["freq"]["centre"], require_match=True)  # ValueError on a miss (:59)
         eng = self._get_engine()
         ctx = eng.ctx
-        mvis = _dev_dataset(mmodes.vis, ctx, np.complex128)
-        mweight = _dev_dataset(mmodes.weight, ctx, np.float64)
-        return eng.solve(self._kind, mvis, mweight, freq_ind, mmax, on_freqs_done=on_freqs_done, **self._solve_params())
+        mv, mw = [], []
+        for mm in mmodes_list:
+            mm.redistribute("freq")
+            mv.append(_dev_dataset(mm.vis, ctx, np.complex128))
+            mw.append(_dev_dataset(mm.weight, ctx, np.float64))
+        return eng.solve_many(self._kind, mv, mw, freq_ind, mmax, on_freqs_done=on_freqs_done, **self._solve_params())
 
     def alm_square(self, alm_d):
         """Device alm -> the reference's square ``[nfreq, 4, lmax+1, lmax+1]`` ndarray (``mapmaker.py:102-109``)."""
@@ -149,64 +156,51 @@ class BaseMapMaker(ContainerTask):
         out[:, :, :, :n_m] = a  # npol == 1 broadcasts over the 4 slots exactly like mapmaker.py:94
         return out
 
+    def _slabwise(self):
+        """Whether a day's solves and transforms run slab by slab (:meth:`process_many`): the built-in solver and four sky
+        polarisations.  Anything else has its whole a_lm made first (:meth:`_process_whole`)."""
+        return type(self)._solve_m in _BUILTIN_SOLVERS and self.beamtransfer.telescope.num_pol_sky == 4
+
     def process(self, mmodes):
-        """Make a map from the given m-modes (``mapmaker.py:35-118``)."""
-        bt = self.beamtransfer
-        lmax = bt.telescope.lmax
-        user_hook = type(self)._solve_m not in _BUILTIN_SOLVERS
+        """Make a map from the given m-modes (``mapmaker.py:35-118``): :meth:`process_many` of a group of one day."""
+        if self._slabwise():
+            return self.process_many([mmodes])[0]
+        return self._process_whole(mmodes)
+
+    def _process_whole(self, mmodes):
+        """One day whose a_lm is transformed whole, after all its solves: a subclass overrode ``_solve_m`` (the reference's
+        host loop), or the telescope has other than four sky polarisations (broadcast into the map's four)."""
         ctx = Context.get()
         nside = int(self.nside)
-        npix = 12 * nside**2
-        pending = None
         _bound_run_ahead(ctx, max(int(self.days_in_flight), 1))
-        if user_hook or bt.telescope.num_pol_sky != 4:
-            alm_d = self._host_loop(mmodes) if user_hook else self.make_alm(mmodes)
-            nfreq, npol, n_m, nl = alm_d.shape
-            if npol == 1:  # the reference's alm always has 4 pol slots and broadcasts into them (:71,:94)
-                alm_d = alm_d.expand(nfreq, 4, n_m, nl).contiguous()
-            maps = ctx.empty((nfreq, 4, npix), np.float64)
-            _alm2map_neighbourly(ctx, alm_d, nfreq, lmax, n_m - 1, nside, maps)
-        else:
-            # the inverse SHT (:112) of the frequencies a slab has finished runs on a side stream
-            # beside the next slab's fill + solves: it is compute-bound, they are HBM/PCIe-bound
-            overlap = (str(self.b_dtype) != "complex64") if self.overlap_sht is None else bool(self.overlap_sht)
-            side = Context.side(ctx.device_index) if overlap else ctx
-            main = torch.cuda.current_stream(ctx.device)
-            out = {}
+        user_hook = type(self)._solve_m not in _BUILTIN_SOLVERS
+        alm_d = self._host_loop(mmodes) if user_hook else self.make_alm(mmodes)
+        nfreq, npol, n_m, nl = alm_d.shape
+        if npol == 1:  # the reference's alm always has 4 pol slots and broadcasts into them (:71,:94)
+            alm_d = alm_d.expand(nfreq, 4, n_m, nl).contiguous()
+        maps = ctx.empty((nfreq, 4, 12 * nside**2), np.float64)
+        _alm2map_neighbourly(ctx, alm_d, nfreq, self.beamtransfer.telescope.lmax, n_m - 1, nside, maps)
+        return self._queued(ctx, [mmodes], [maps], None)[0]
 
-            def sht_of(alm, f0, f1):
-                nfreq, _, n_m, _ = alm.shape  # the local frequencies
-                if "maps" not in out:
-                    out["maps"] = ctx.empty((nfreq, 4, npix), np.float64)
-                if not overlap:
-                    _alm2map_neighbourly(ctx, alm[f0:f1], f1 - f0, lmax, n_m - 1, nside, out["maps"][f0:f1])
-                    return
-                side.wait_for(main)
-                side.uses(alm, out["maps"])  # read / written on the side stream: held until side.sync()
-                _alm2map_neighbourly(side, alm[f0:f1], f1 - f0, lmax, n_m - 1, nside, out["maps"][f0:f1])
-
-            alm_d = self.make_alm(mmodes, on_freqs_done=sht_of)
-            maps = out.get("maps")
-            if maps is None:  # no frequencies on this rank
-                maps = ctx.empty((alm_d.shape[0], 4, npix), np.float64)
-            elif overlap:
-                # the last slab's SHT is still running on the side stream.  Whoever reads the map is ordered behind
-                # it at that moment (Dataset's `pending`); work that does not -- the next day's transform and
-                # solves -- is not held up.  (`record_stream` guards the allocator meanwhile.)
-                pending = StreamDone(side.stream, ctx.device)
-                side.release_held()
-        # the day's last work, for the run-ahead bound of the days that follow
+    def _queued(self, ctx, mmodes_list, maps, pending):
+        """The end of a ``process`` / ``process_many`` call: ONE entry for the run-ahead bound of the calls that follow
+        -- the call's last work, ``pending`` (the side stream's) or else the current stream's -- and the days' ``Map``
+        containers around their device maps."""
         _IN_FLIGHT.setdefault(ctx.device_index, collections.deque()).append(
             pending if pending is not None else StreamDone(torch.cuda.current_stream(ctx.device), ctx.device))
-        m = containers.Map(nside=self.nside, axes_from=mmodes, comm=mmodes.comm, allocate=False)
-        m.attach("map", maps, pending=pending)
-        return m
+        out = []
+        for mm, mp in zip(mmodes_list, maps):
+            m = containers.Map(nside=self.nside, axes_from=mm, comm=mm.comm, allocate=False)
+            m.attach("map", mp, pending=pending)
+            out.append(m)
+        return out
 
     def process_many(self, mmodes_list):
         """Maps of D sidereal days from ONE pass over the beam transfers: ``[process(mm) for mm in mmodes_list]``, with
-        every slab of B brought in once for all of them.  Not a reference method: the reference's pipeline calls
-        ``process`` once per item (``doc/tutorial.rst:110-120``, the loop at ``mapmaker.py:79-94``) and reads every
-        ``beam_m`` again each time; real processing applies one set of beam transfers to many days.
+        every slab of B brought in once for all of them.  The day loop of every map-maker (``process`` is D = 1).  Not a
+        reference method: the reference's pipeline calls ``process`` once per item (``doc/tutorial.rst:110-120``, the loop
+        at ``mapmaker.py:79-94``) and reads every ``beam_m`` again each time; real processing applies one set of beam
+        transfers to many days.
 
         With B streamed from the host the PCIe crossing (56 GB/s: 28 s per cfg-3 day) is shared by the D days; with B
         resident ``DirtyMapMaker`` also shares every tile READ between up to eight days (``dmm_dirty_run_multi``).
@@ -216,71 +210,49 @@ class BaseMapMaker(ContainerTask):
         mmodes_list = list(mmodes_list)
         if not mmodes_list:
             return []
-        bt = self.beamtransfer
-        if type(self)._solve_m not in _BUILTIN_SOLVERS or bt.telescope.num_pol_sky != 4:
-            return [self.process(mm) for mm in mmodes_list]
+        if not self._slabwise():
+            return [self._process_whole(mm) for mm in mmodes_list]
         first = mmodes_list[0]
         for mm in mmodes_list[1:]:
             if len(mm.index_map["m"]) != len(first.index_map["m"]) or not np.array_equal(mm.index_map["freq"]["centre"], first.index_map["freq"]["centre"]):
                 raise ValueError("process_many: every day must cover the same frequencies and m range")
-        lmax = bt.telescope.lmax
+        lmax = self.beamtransfer.telescope.lmax
         ctx = Context.get()
         nside = int(self.nside)
         npix = 12 * nside**2
+        ndays = len(mmodes_list)
         # run-ahead in DAYS, not calls: a group of D days holds D sets of a_lm and maps, so at most
         # days_in_flight // D earlier groups (none for D > days_in_flight / 2) may still be running when this one is queued
-        _bound_run_ahead(ctx, max(int(self.days_in_flight) // len(mmodes_list), 1))
+        _bound_run_ahead(ctx, max(int(self.days_in_flight) // ndays, 1))
+        # the inverse SHT (:112) of the frequencies a slab has finished runs on a side stream
+        # beside the next slab's fill + solves: it is compute-bound, they are HBM/PCIe-bound
         overlap = (str(self.b_dtype) != "complex64") if self.overlap_sht is None else bool(self.overlap_sht)
         side = Context.side(ctx.device_index) if overlap else ctx
         main = torch.cuda.current_stream(ctx.device)
-        maps = {}
-
-        ndays = len(mmodes_list)
+        maps = []
 
         def sht_of(d, alm, f0, f1):
-            nfreq, _, n_m, _ = alm.shape
+            nfreq, _, n_m, _ = alm.shape  # the local frequencies
             if not maps:  # one allocation for the whole group (see solve_many)
                 all_maps = ctx.empty((ndays, nfreq, 4, npix), np.float64)
-                for dd in range(ndays):
-                    maps[dd] = all_maps[dd]
+                maps.extend(all_maps[dd] for dd in range(ndays))
             if overlap:
                 if d == 0:
                     side.wait_for(main)
-                side.uses(alm, maps[d])
+                side.uses(alm, maps[d])  # read / written on the side stream: held until side.sync()
             _alm2map_neighbourly(side, alm[f0:f1], f1 - f0, lmax, n_m - 1, nside, maps[d][f0:f1])
 
         alms = self.make_alm_many(mmodes_list, on_freqs_done=sht_of)
         pending = None
-        if overlap and maps:
+        if not maps:  # no frequencies on this rank
+            maps = [ctx.empty((alm.shape[0], 4, npix), np.float64) for alm in alms]
+        elif overlap:
+            # the last slab's SHT is still running on the side stream.  Whoever reads a map is ordered behind
+            # it at that moment (Dataset's `pending`); work that does not -- the next day's transform and
+            # solves -- is not held up.  (`record_stream` guards the allocator meanwhile.)
             pending = StreamDone(side.stream, ctx.device)
             side.release_held()
-        _IN_FLIGHT.setdefault(ctx.device_index, collections.deque()).append(
-            pending if pending is not None else StreamDone(torch.cuda.current_stream(ctx.device), ctx.device))
-        out = []
-        for d, mm in enumerate(mmodes_list):
-            mp = maps.get(d)
-            if mp is None:  # no frequencies on this rank
-                mp = ctx.empty((alms[d].shape[0], 4, npix), np.float64)
-            m = containers.Map(nside=self.nside, axes_from=mm, comm=mm.comm, allocate=False)
-            m.attach("map", mp, pending=pending)
-            out.append(m)
-        return out
-
-    def make_alm_many(self, mmodes_list, on_freqs_done=None):
-        """The a_lm of D days from one pass over B (see :meth:`process_many`): a list of device arrays as
-        :meth:`make_alm` returns them."""
-        bt = self.beamtransfer
-        first = mmodes_list[0]
-        mmax = min(bt.telescope.mmax, len(first.index_map["m"]) - 1)
-        freq_ind = tools.find_keys(bt.telescope.frequencies, first.index_map["freq"]["centre"], require_match=True)
-        eng = self._get_engine()
-        ctx = eng.ctx
-        mv, mw = [], []
-        for mm in mmodes_list:
-            mm.redistribute("freq")
-            mv.append(_dev_dataset(mm.vis, ctx, np.complex128))
-            mw.append(_dev_dataset(mm.weight, ctx, np.float64))
-        return eng.solve_many(self._kind, mv, mw, freq_ind, mmax, on_freqs_done=on_freqs_done, **self._solve_params())
+        return self._queued(ctx, mmodes_list, maps, pending)
 
     def _host_loop(self, mmodes):
         """A subclass overrode ``_solve_m``: honour the hook with the reference's loop (:79-94)."""
@@ -310,21 +282,13 @@ class BaseMapMaker(ContainerTask):
         mvis[m] = ctx.to_device(v)
         mw[m] = ctx.to_device(Ni)
         dt = {"complex128": _lib.DMM_C128, "complex64": _lib.DMM_C64}[str(self.b_dtype)]
+        # a slab of the one tile (m, f) -- not 0..m, as the engine would carve it -- with a pool of its own
         slab = _solve.Slab(ctx, self.beamtransfer, np.array([m], np.int32), np.array([0], np.int32), np.array([f], np.int32), dt, _lib.DMM_B_PACKED, 1, m + 1)
         eng = _solve.SolveEngine(self.beamtransfer, ctx, dt, _lib.DMM_B_PACKED, cache=True)
-        eng._cached_key = ((int(f),), int(m), 1, m + 1, dt, _lib.DMM_B_PACKED)
-        eng._cached_slabs = [_OneTile(slab)]
-        alm = eng.solve(self._kind, mvis, mw, [f], m, **self._solve_params())
+        alm = eng.solve(self._kind, mvis, mw, [f], m, slabs=[slab], **self._solve_params())
         out = alm[0, :, m, :].cpu().numpy()
         slab.close()
         return out
-
-
-class _OneTile:
-    """Adapter so that a single-tile slab (only m, not 0..m) can be fed through SolveEngine.solve."""
-
-    def __init__(self, slab):
-        self.plan, self.pool, self.b_bytes, self.ntile = slab.plan, slab.pool, slab.b_bytes, slab.ntile
 
 
 class DirtyMapMaker(BaseMapMaker):
