@@ -175,4 +175,9 @@ int dmm_fft_tables_f64(dmm_ctx* ctx, int n, dmm_fft_tables** out);  // mfft.hip
 int dmm_ml_two_stage_max_order();  // solve_dense.hip: the largest order the ML band reduction takes
 
 static inline bool dmm_is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+static inline int ilog2(int n) {  // ceil(log2 n): the number of stages of a length-n transform
+  int l = 0;
+  while ((1 << l) < n) ++l;
+  return l;
+}
 

@@ -255,5 +255,23 @@ __device__ __forceinline__ int bitrev(int k, int logM) {
   return logM == 0 ? 0 : (int)(__brev((unsigned)k) >> (32 - logM));
 }
 
+// ---- Bluestein's convolution on RB rows already multiplied by the chirp and zero-padded to M: DIF forward, pointwise
+// product with the filter spectrum (`bfilt`: float2 / double2, bit-reversed order, scaled by 1/M), DIT inverse -- natural
+// order in and out, no reordering pass.  `radix8`: the passes with three stages each.
+template <typename T, int kThreads, typename T2>
+__device__ __forceinline__ void bluestein_convolve(C<T>* buf, const C<T>* tw, const T2* bfilt, int RB, int M, int logM, int P,
+                                                   bool radix8 = false) {
+  if (radix8) fft_dif8<T, kThreads>(buf, tw, RB, M, logM, P);
+  else fft_dif<T, kThreads>(buf, tw, RB, M, logM, P);
+  for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
+    const int r = idx / M, k = idx - r * M;
+    const T2 f = bfilt[k];
+    buf[r * P + k] = cmul<T>(buf[r * P + k], {f.x, f.y});
+  }
+  __syncthreads();
+  if (radix8) fft_dit8<T, true, kThreads>(buf, tw, RB, M, logM, P);
+  else fft_dit<T, true, kThreads>(buf, tw, RB, M, logM, P);
+}
+
 
 }  // namespace dmm_fft

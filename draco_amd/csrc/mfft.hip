@@ -95,16 +95,8 @@ __global__ __launch_bounds__(kThreads) void k_mfft_pack(MfftParams p) {
     }
   }
   __syncthreads();
-  fft_dif<float>(buf, tw, RB, M, p.logM, P);
-  if (BLUESTEIN) {
-    for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
-      const int r = idx / M, k = idx - r * M;
-      const float2 f = p.bfilt[k];
-      buf[r * P + k] = cmul<float>(buf[r * P + k], {f.x, f.y});
-    }
-    __syncthreads();
-    fft_dit<float, true>(buf, tw, RB, M, p.logM, P);
-  }
+  if (BLUESTEIN) dmm_fft::bluestein_convolve<float, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
+  else fft_dif<float>(buf, tw, RB, M, p.logM, P);
 
   // pack: consecutive threads -> consecutive rows, so each (m, s) slot is one
   // RB*elem-byte contiguous store segment
@@ -210,16 +202,8 @@ __global__ __launch_bounds__(kThreads) void k_beam_mfft(BeamParams p) {
     buf[r * P + k] = v;
   }
   __syncthreads();
-  fft_dif<double>(buf, tw, RB, M, p.logM, P);
-  if (BLUESTEIN) {
-    for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
-      const int r = idx / M, k = idx - r * M;
-      const double2 f = p.bfilt[k];
-      buf[r * P + k] = cmul<double>(buf[r * P + k], {f.x, f.y});
-    }
-    __syncthreads();
-    fft_dit<double, true>(buf, tw, RB, M, p.logM, P);
-  }
+  if (BLUESTEIN) dmm_fft::bluestein_convolve<double, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
+  else fft_dif<double>(buf, tw, RB, M, p.logM, P);
   const double inv_n = 1.0 / (double)N;
   const int nslot = (p.mmax + 1) * 2;
   for (int idx = threadIdx.x; idx < nslot * RB; idx += kThreads) {
@@ -304,18 +288,8 @@ __global__ __launch_bounds__(kThreads) void k_mifft_unpack(MifftParams p) {
     buf[r * P + (BLUESTEIN ? k : bitrev(k, p.logM))] = v;
   }
   __syncthreads();
-  if (BLUESTEIN) {
-    fft_dif<double>(buf, tw, RB, M, p.logM, P);
-    for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
-      const int r = idx / M, k = idx - r * M;
-      const double2 f = p.bfilt[k];
-      buf[r * P + k] = cmul<double>(buf[r * P + k], {f.x, f.y});
-    }
-    __syncthreads();
-    fft_dit<double, true>(buf, tw, RB, M, p.logM, P);
-  } else {
-    fft_dit<double, false>(buf, tw, RB, M, p.logM, P);
-  }
+  if (BLUESTEIN) dmm_fft::bluestein_convolve<double, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
+  else fft_dit<double, false>(buf, tw, RB, M, p.logM, P);
   for (int idx = threadIdx.x; idx < RB * N; idx += kThreads) {
     const int r = idx / N, n = idx - r * N;
     if (r0 + r >= p.nrow) continue;
@@ -397,12 +371,6 @@ int upload(const std::vector<T2>& h, T2** d) {
   DMM_HIP(hipMalloc((void**)d, h.size() * sizeof(T2)));
   DMM_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T2), hipMemcpyHostToDevice));
   return DMM_OK;
-}
-
-inline int ilog2(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
 }
 
 void host_fft(std::vector<double>& re, std::vector<double>& im) {  // in-place radix-2, forward

@@ -18,6 +18,11 @@
 //                z = X_map + i X_dirty of one row); powers of two run the in-LDS radix passes, other lengths
 //                Bluestein (shared machinery, fft_lds.h);
 //   k_rm_store   tiled transpose [el][ra] -> the reference's [ra][el] layout.
+// Where nra is a power of two, the RA-space dirty beam is not asked for and every row is normalised by itself:
+//   k_rm_fused<EL, PARK>  the three stages in one pass: a block owns 8 or 16 elevations of one (pol, freq) for all m, so
+//                neither the modes nor the [el][ra] rows reach HBM (16 elevations: 128-byte pieces of the input rows;
+//                PARK: the second eight's image waits in a scratch image while the first eight's is transformed).
+// The term-weight rule (rm_term_weight), the per-(m, el) mode (rm_mode) and the row finish (rm_row_finish) are shared.
 // float64 arithmetic throughout (the reference mixes float32 and float64 by weight scheme).
 #include <math.h>
 
@@ -55,6 +60,55 @@ struct RmParams {
 constexpr int MT = 16;  // m per block in k_rm_reduce
 constexpr int kTermBatch = 8;  // (sign, EW) terms whose hv / bv loads are in flight together
 
+// Weight w of the (sign, EW separation) term t of mode m and g = w^2 var: `mode` 0 / 1 / 2 of RmParams.  The term's
+// weights do not depend on the elevation: one lane works them out -- two float64 divisions -- and the others pick them up.
+__device__ __forceinline__ void rm_term_weight(const RmParams& p, int m, int pol, int f, int t, double& w, double& g) {
+  const int s = t / p.new_, e = t - s * p.new_;
+  const int64_t wbase = ((((int64_t)m * 2 + s) * p.npol + pol) * p.nfreq + f) * p.new_;
+  double iv = (double)p.hw[wbase + e];
+  if (p.mode == 0) {
+    w = iv > 0.0 ? p.wt[e] : 0.0;
+  } else {
+    iv *= p.wt[e];  // the reference zeroes the excluded cylinders inside inv_var itself
+    if (p.mode == 1) {
+      double wsumv = 0.0;
+      for (int e2 = 0; e2 < p.new_; ++e2) wsumv += (double)p.hw[wbase + e2] * p.wt[e2];
+      w = iv * (wsumv != 0.0 ? 1.0 / wsumv : 0.0);
+    } else {
+      w = iv;
+    }
+    if (!(iv > 0.0)) w = 0.0;
+  }
+  g = w * w * (iv > 0.0 ? 1.0 / iv : 0.0);
+}
+
+// One (m, el) from its (+/-, ew) sums: the map mode (ar, ai), the dirty-beam mode rd, and the mode's share of the three
+// per-row sums over m -- dirty (point-source normalisation), q^2 (noise weight), c_m dirty^2 (dirty-beam power by Parseval).
+__device__ __forceinline__ void rm_mode(const RmParams& p, double sw, double mre, double mim, double sg, int m, int f, int el,
+                                        double& ar, double& ai, double& rd, double& acc_d, double& acc_q, double& acc_p) {
+  const double cinv = p.skip ? 1.0 : p.eps[(int64_t)f * p.nm + m] + sw;
+  const double ic = cinv != 0.0 ? 1.0 / cinv : 0.0;
+  const double win = p.window ? (double)p.window[((int64_t)f * p.nm + m) * p.nel + el] : 1.0;
+  ar = win * mre * ic;
+  ai = win * mim * ic;
+  rd = win * sw * ic;
+  const double qv = sqrt(sg) * win * ic / (double)(p.mmax + 1);  // 1 / ((mmax + 1) C): one division serves all
+  acc_d += rd;
+  acc_q += qv * qv;
+  // weight of mode m in sum_k X_ext(k)^2 of the Hermitian extension to N bins: DC and (even N) Nyquist once
+  acc_p += ((m == 0 || 2 * m == p.nra) ? 1.0 : 2.0) * rd * rd;
+}
+
+// A row from its three sums over m: normalisation, noise weight, and the dirty-beam power by Parseval --
+// sum_n d(n)^2 = (1/N) sum_k X_ext(k)^2 for d = irfft(X), the beam scaled by nrm.
+__device__ __forceinline__ void rm_row_finish(double d, double q2, double p2, int nm, int N, double& nrm, double& wv, double& dbp) {
+  const double mean = d / (double)nm;
+  nrm = mean != 0.0 ? 1.0 / mean : 0.0;
+  const double sv = 0.5 * nrm * nrm * q2;
+  wv = sv != 0.0 ? 1.0 / sv : 0.0;
+  dbp = nrm * nrm * p2 / (double)N / (double)N;
+}
+
 // One (el tile, 16 m, pol x freq) per block; EPL elevations per lane (1 is what ships).
 // Per (m, el): the (+/-, ew) sums, the map / dirty-beam modes (to s_map / s_dirty, transposed through LDS so that
 // rows are contiguous in m) and the block's share of three sums over m that the FFT stage needs per row -- dirty
@@ -69,7 +123,6 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int el0 = blockIdx.x * ET, m0 = blockIdx.y * MT, pf = blockIdx.z;
   const int pol = pf / p.nfreq, f = pf - pol * p.nfreq;
-  const int N = p.nra;
   double acc_d[EPL], acc_q[EPL], acc_p[EPL];
 #pragma unroll
   for (int u = 0; u < EPL; ++u) acc_d[u] = acc_q[u] = acc_p[u] = 0.0;
@@ -88,25 +141,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
       for (int t0 = 0; t0 < nterm; t0 += 64) {  // (one round unless there are more than 32 EW separations)
         const int t = t0 + lane;
         double w = 0.0, g = 0.0;
-        if (t < nterm) {
-          const int s = t / p.new_, e = t - s * p.new_;
-          const int64_t wbase = ((((int64_t)m * 2 + s) * p.npol + pol) * p.nfreq + f) * p.new_;
-          double iv = (double)p.hw[wbase + e];
-          if (p.mode == 0) {
-            w = iv > 0.0 ? p.wt[e] : 0.0;
-          } else {
-            iv *= p.wt[e];  // the reference zeroes the excluded cylinders inside inv_var itself
-            if (p.mode == 1) {
-              double wsumv = 0.0;
-              for (int e2 = 0; e2 < p.new_; ++e2) wsumv += (double)p.hw[wbase + e2] * p.wt[e2];
-              w = iv * (wsumv != 0.0 ? 1.0 / wsumv : 0.0);
-            } else {
-              w = iv;
-            }
-            if (!(iv > 0.0)) w = 0.0;
-          }
-          g = w * w * (iv > 0.0 ? 1.0 / iv : 0.0);
-        }
+        if (t < nterm) rm_term_weight(p, m, pol, f, t, w, g);
         w_l = w;
         g_l = g;
         const int tend = nterm - t0 < 64 ? nterm - t0 : 64;
@@ -146,18 +181,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
     for (int u = 0; u < EPL; ++u) {
       double2 rm = make_double2(0.0, 0.0);
       double rd = 0.0;
-      if (m < p.nm && el + u < p.nel) {
-        const double cinv = p.skip ? 1.0 : p.eps[(int64_t)f * p.nm + m] + sw[u];
-        const double ic = cinv != 0.0 ? 1.0 / cinv : 0.0;
-        const double win = p.window ? (double)p.window[((int64_t)f * p.nm + m) * p.nel + el + u] : 1.0;
-        rm = make_double2(win * mre[u] * ic, win * mim[u] * ic);
-        rd = win * sw[u] * ic;
-        const double qv = sqrt(sg[u]) * win * ic / (double)(p.mmax + 1);  // 1 / ((mmax + 1) C): one division serves all
-        acc_d[u] += rd;
-        acc_q[u] += qv * qv;
-        // weight of mode m in sum_k X_ext(k)^2 of the Hermitian extension to N bins: DC and (even N) Nyquist once
-        acc_p[u] += ((m == 0 || 2 * m == N) ? 1.0 : 2.0) * rd * rd;
-      }
+      if (m < p.nm && el + u < p.nel) rm_mode(p, sw[u], mre[u], mim[u], sg[u], m, f, el + u, rm.x, rm.y, rd, acc_d[u], acc_q[u], acc_p[u]);
       tmap[mi][EPL * lane + u] = rm;
       tdirty[mi][EPL * lane + u] = rd;
     }
@@ -250,6 +274,9 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   }
   __syncthreads();
   if (q.blue) {
+    // (not dmm_fft::bluestein_convolve: spelt this way the compiler fuses the OTHER product of the filter multiply's
+    // imaginary part -- fma(a.y, f.x, a.x f.y), the helper's call sites fma(f.y, a.x, f.x a.y) -- and moving over would
+    // change the last bit of every Bluestein ring map)
     dmm_fft::fft_dif<double, kThreads>(buf, tw, RB, M, q.logM, P);
     for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
       const int r = idx / M, k = idx - r * M;
@@ -262,7 +289,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   }
   // finish: y = conj(result) / N; first output = Re y, second = Im y, each times its row's normalisation
   __shared__ double red[kThreads];
-  __shared__ double s_nrm[2], s_q2[2], s_p2[2];
+  __shared__ double s_nrm[2], s_wv[2], s_dbp[2];
   for (int r = 0; r < RB; ++r) {
     const int64_t row0 = (t0 + r) * PAIR;
     if (row0 >= nrow) break;  // uniform
@@ -288,12 +315,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
         q2 += __shfl_xor(q2, o, 64);
         p2 += __shfl_xor(p2, o, 64);
       }
-      if (ln == 0) {
-        const double mean = d / (double)p.nm;
-        s_nrm[w2] = (row < nrow && mean != 0.0) ? 1.0 / mean : 0.0;
-        s_q2[w2] = q2;
-        s_p2[w2] = p2;
-      }
+      if (ln == 0) rm_row_finish(d, q2, p2, p.nm, N, s_nrm[w2], s_wv[w2], s_dbp[w2]);  // (a row past the end: all zero)
     }
     __syncthreads();
     const double sc0 = s_nrm[0] / (double)N, sc1 = s_nrm[PAIR - 1] / (double)N;
@@ -320,240 +342,85 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
     }
     if (threadIdx.x < PAIR && row0 + threadIdx.x < nrow) {
       const int w2 = threadIdx.x;
-      const double nrm = s_nrm[w2];
-      // Parseval: sum_n d(n)^2 = (1/N) sum_k X_ext(k)^2 for d = irfft(X); the beam is scaled by nrm
-      const double pw_tot = PAIR == 1 ? red[0] : nrm * nrm * s_p2[w2] / (double)N;
-      p.dbp[row0 + w2] = pw_tot / (double)N;
-      const double sv = 0.5 * nrm * nrm * s_q2[w2];
-      p.wv[row0 + w2] = sv != 0.0 ? 1.0 / sv : 0.0;
+      p.dbp[row0 + w2] = PAIR == 1 ? red[0] / (double)N : s_dbp[w2];
+      p.wv[row0 + w2] = s_wv[w2];
     }
     __syncthreads();
   }
 }
 
 // ---- the three stages in ONE pass over the m-modes (power-of-two nra, RA-space dirty beam not asked for, own-row
-// normalisation): a block owns 8 elevations of one (pol, freq) for ALL m.  Its 16 waves read the (sign, EW) terms of
-// 128 m at a time -- lane = (m, el): 64-byte pieces of the hv / bv rows, each lane 2 x nterm loads in flight --, keep the
-// sums in registers and put the map modes straight into the LDS image of the inverse FFT (two rows per complex
+// normalisation): a block owns EL elevations of one (pol, freq) for ALL m.  Its 16 waves read the (sign, EW) terms of
+// 16 x 64 / EL m at a time -- lane = (m, el): pieces of 8 EL bytes of the hv / bv rows, each lane 2 x nterm loads in flight --,
+// keep the sums in registers and put the map modes straight into the LDS image of the inverse FFT (two rows per complex
 // sequence, bit-reversed positions, the Hermitian mirror bins written by the odd row's lane); the per-row sums over m
-// never leave the block.  After the in-LDS FFT the RA rows go out as 64-byte pieces of map[ra][el] and weight[ra][el]:
+// never leave the block.  After the in-LDS FFT the RA rows go out as pieces of map[ra][el] and weight[ra][el]:
 // the [pol, el, m] modes and the [pol, el, ra] rows of the three-kernel form (1.34 GB of scratch traffic beside 2.69 GB
-// of input and output at the CHIME-like shape) never reach HBM.  Two blocks of neighbouring elevations share every
-// 128-byte line of the input: block ids are mapped so that such a pair sits on the same XCD (same L2), 8 ids apart.
-constexpr int kFuThreads = 1024, kFuEl = 8;
-__global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, int ntile_el) {
+// of input and output at the CHIME-like shape) never reach HBM.
+//   EL = 8 (round 3): 64-byte pieces.  Two blocks of neighbouring elevations share every 128-byte line of the input:
+// block ids are mapped so that such a pair sits on the same XCD (same L2), 8 ids apart.
+//   EL = 16 (round 4): HBM serves 128-byte lines: read in 64-byte pieces at a 4 KB stride -- what 8 elevations of
+// complex64 are -- it delivers 3.0 TB/s, in 128-byte pieces 6.2 (tools/probe/piece_bw.hip), and 3.0 TB/s is exactly
+// what the load phase of the 8-elevation form ran at.  So the block reads 128-byte pieces (lane = (m, 16 elevations)).
+//   PARK = false: the image of all sixteen elevations fits the LDS (nra <= 1024): one transform of eight sequences,
+// 128-byte pieces on the way out too.
+//   PARK = true: the LDS holds the inverse-FFT image of 8 elevations, no more; the block puts the modes of elevations
+// 0-7 into the LDS image and PARKS those of elevations 8-15 in a global scratch image (131 KB per block, 64-byte pieces
+// in natural order; it lives in L2 / the Infinity Cache until it is read back), transforms and stores the first eight,
+// reads the parked image in (bit reversal on the LDS side), transforms and stores the second eight.
+constexpr int kFuThreads = 1024;
+template <int EL, bool PARK>
+__global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, int ntile_el, double2* __restrict__ park) {
+  static_assert(EL == 16 || (EL == 8 && !PARK), "8 or 16 elevations per block; only sixteen are ever parked");
+  constexpr int kMW = 64 / EL;              // m per wave
+  constexpr int kSeq = PARK ? 4 : EL / 2;   // sequences in the LDS image
+  constexpr int kPass = PARK ? 2 : 1;       // passes over the tail
+  constexpr int kElOut = PARK ? 8 : EL;     // elevations per output pass
   extern __shared__ __align__(16) unsigned char smem[];
-  __shared__ double s_acc[3][kFuThreads / 64][kFuEl];
-  __shared__ double s_nrm[kFuEl], s_wv[kFuEl];
-  C<double>* buf = reinterpret_cast<C<double>*>(smem);  // [4][P]
-  C<double>* twl = buf + (size_t)4 * q.P;
+  __shared__ double s_acc[3][kFuThreads / 64][EL];
+  __shared__ double s_nrm[EL], s_wv[EL];
+  C<double>* buf = reinterpret_cast<C<double>*>(smem);  // [kSeq][P]
+  C<double>* twl = buf + (size_t)kSeq * q.P;
   const int N = p.nra, M = q.M, P = q.P;
-  // block -> (pf, elevation tile): ids L and L + 8 (same XCD under round-robin dispatch) take neighbouring tiles
-  const int L = blockIdx.x, grp = L >> 4, r16 = L & 15;
-  const int64_t tile_lin = (int64_t)2 * (grp * 8 + (r16 & 7)) + (r16 >> 3);
-  if (tile_lin >= (int64_t)ntile_el * p.npol * p.nfreq) return;
-  const int pf = (int)(tile_lin / ntile_el), tile = (int)(tile_lin - (int64_t)pf * ntile_el);
-  const int pol = pf / p.nfreq, f = pf - pol * p.nfreq;
-  const int el0 = tile * kFuEl;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int eli = lane & 7, ms = lane >> 3;
-  const int el = el0 + eli;
-  const bool el_ok = el < p.nel;
-  const int elc = el_ok ? el : p.nel - 1;
-  for (int k = threadIdx.x; k < (M >> 1); k += kFuThreads) twl[k] = {q.tw[k].x, q.tw[k].y};
-  const int nterm = 2 * p.new_;
-  double acc_d = 0.0, acc_q = 0.0, acc_p = 0.0;
-  // (measured, CHIME-like shape, 0.89 ms as it stands: the load phase alone takes 0.72 ms = 3.0 TB/s -- 64-byte pieces
-  // are what the LDS allows, 8 elevations x 2048 RA x 16 bytes --; two m per lane and pass, i.e. 32 loads in flight per
-  // lane: 0.93; the term weights from a table made by a pre-pass instead of in the loop: 0.95; blocks staggered over m
-  // so that they do not read the same rows at the same time: 1.07 -- lock step is what keeps the DRAM pages open.)
-  for (int mb = 0; mb < p.nm; mb += 8 * (kFuThreads / 64)) {
-    const int m = mb + wave * 8 + ms;
-    const bool m_ok = m < p.nm;
-    const int mc = m_ok ? m : p.nm - 1;
-    double sw = 0.0, mre = 0.0, mim = 0.0, sg = 0.0;
-    for (int t0 = 0; t0 < nterm; t0 += 8) {
-      // lane `eli` of the group works out the weights of term t0 + eli of its m; the group's lanes pick them up below
-      double w = 0.0, g = 0.0;
-      {
-        const int t = t0 + eli;
-        if (t < nterm) {
-          const int s = t / p.new_, e = t - s * p.new_;
-          const int64_t wbase = ((((int64_t)mc * 2 + s) * p.npol + pol) * p.nfreq + f) * p.new_;
-          double iv = (double)p.hw[wbase + e];
-          if (p.mode == 0) {
-            w = iv > 0.0 ? p.wt[e] : 0.0;
-          } else {
-            iv *= p.wt[e];
-            if (p.mode == 1) {
-              double wsumv = 0.0;
-              for (int e2 = 0; e2 < p.new_; ++e2) wsumv += (double)p.hw[wbase + e2] * p.wt[e2];
-              w = iv * (wsumv != 0.0 ? 1.0 / wsumv : 0.0);
-            } else {
-              w = iv;
-            }
-            if (!(iv > 0.0)) w = 0.0;
-          }
-          g = w * w * (iv > 0.0 ? 1.0 / iv : 0.0);
-        }
-      }
-      float2 h[8], b[8];
-      double w2[8], g2[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const bool live = t0 + k < nterm;
-        const int tg = live ? t0 + k : nterm - 1, s = tg / p.new_, e = tg - s * p.new_;
-        const double wk = __shfl(w, (lane & ~7) + k, 64), gk = __shfl(g, (lane & ~7) + k, 64);
-        w2[k] = live ? wk : 0.0;
-        g2[k] = live ? gk : 0.0;
-        const int64_t rbase = (((((int64_t)mc * 2 + s) * p.npol + pol) * p.nfreq + f) * p.new_ + e) * p.nel + elc;
-        h[k] = p.hv[rbase];
-        b[k] = p.bv[rbase];
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const double br = b[k].x, bi = b[k].y, hr = h[k].x, hi = h[k].y;
-        const double b2 = br * br + bi * bi;
-        sw = fma(w2[k], b2, sw);
-        mre = fma(w2[k], br * hr + bi * hi, mre);  // conj(b) * h
-        mim = fma(w2[k], br * hi - bi * hr, mim);
-        sg = fma(g2[k], b2, sg);
-      }
-    }
-    double ar = 0.0, ai = 0.0;
-    if (m_ok && el_ok) {
-      const double cinv = p.eps[(int64_t)f * p.nm + m] + sw;  // (skip_deconvolution takes the three-kernel path)
-      const double ic = cinv != 0.0 ? 1.0 / cinv : 0.0;
-      const double win = p.window ? (double)p.window[((int64_t)f * p.nm + m) * p.nel + el] : 1.0;
-      ar = win * mre * ic;
-      ai = win * mim * ic;
-      const double rd = win * sw * ic;
-      const double qv = sqrt(sg) * win * ic / (double)(p.mmax + 1);
-      acc_d += rd;
-      acc_q += qv * qv;
-      acc_p += ((m == 0 || 2 * m == N) ? 1.0 : 2.0) * rd * rd;
-    }
-    const bool edge = m == 0 || 2 * m == N;  // DC and Nyquist bins are real, and their own mirror
-    if (edge) ai = 0.0;
-    // rows 2j (A) and 2j + 1 (B) share a transform: z = X_A + i X_B, loaded conjugated at the bit-reversed position
-    const double orr = __shfl_xor(ar, 1, 64), oi = __shfl_xor(ai, 1, 64);
-    if (m_ok) {
-      const bool odd = eli & 1;
-      const double a_r = odd ? orr : ar, a_i = odd ? oi : ai, b_r = odd ? ar : orr, b_i = odd ? ai : oi;
-      C<double>* row = buf + (size_t)(eli >> 1) * P;
-      if (!odd) row[dmm_fft::bitrev(m, q.logM)] = {a_r - b_i, -(a_i + b_r)};
-      else if (!edge) row[dmm_fft::bitrev(N - m, q.logM)] = {a_r + b_i, a_i - b_r};  // X[N - m] = conj(X[m]) of both rows
-    }
+  int64_t tile_lin;
+  if constexpr (EL == 8) {
+    // block -> (pf, elevation tile): ids L and L + 8 (same XCD under round-robin dispatch) take neighbouring tiles
+    const int L = blockIdx.x, grp = L >> 4, r16 = L & 15;
+    tile_lin = (int64_t)2 * (grp * 8 + (r16 & 7)) + (r16 >> 3);
+    if (tile_lin >= (int64_t)ntile_el * p.npol * p.nfreq) return;  // (grid rounded up to 16)
+  } else {
+    tile_lin = blockIdx.x;  // (grid = tiles exactly)
   }
-  // the block's per-row sums over m: the 8 m of a wave by a butterfly, the waves in a fixed order
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    acc_d += __shfl_xor(acc_d, o, 64);
-    acc_q += __shfl_xor(acc_q, o, 64);
-    acc_p += __shfl_xor(acc_p, o, 64);
-  }
-  if (ms == 0) {
-    s_acc[0][wave][eli] = acc_d;
-    s_acc[1][wave][eli] = acc_q;
-    s_acc[2][wave][eli] = acc_p;
-  }
-  __syncthreads();
-  if (threadIdx.x < kFuEl) {
-    double d = 0.0, q2 = 0.0, p2 = 0.0;
-    for (int w2 = 0; w2 < kFuThreads / 64; ++w2) {
-      d += s_acc[0][w2][threadIdx.x];
-      q2 += s_acc[1][w2][threadIdx.x];
-      p2 += s_acc[2][w2][threadIdx.x];
-    }
-    const double mean = d / (double)p.nm;
-    const double nrm = mean != 0.0 ? 1.0 / mean : 0.0;
-    const double sv = 0.5 * nrm * nrm * q2;
-    s_nrm[threadIdx.x] = nrm;
-    s_wv[threadIdx.x] = sv != 0.0 ? 1.0 / sv : 0.0;
-    if (el0 + (int)threadIdx.x < p.nel) p.dbp[(int64_t)pf * p.nel + el0 + threadIdx.x] = nrm * nrm * p2 / (double)N / (double)N;  // Parseval
-  }
-  __syncthreads();
-  dmm_fft::fft_dit<double, false, kFuThreads>(buf, twl, 4, M, q.logM, P);
-  // y = conj(result) / N: even row = Re, odd row = -Im, each times its row's normalisation; 64-byte pieces of [ra][el]
-  {
-    const int e8 = threadIdx.x & 7;
-    const int ele = el0 + e8;
-    const double sc = s_nrm[e8] / (double)N, wv = s_wv[e8];
-    if (ele < p.nel)
-      for (int ra = threadIdx.x >> 3; ra < N; ra += kFuThreads / 8) {
-        const C<double> v = buf[(size_t)(e8 >> 1) * P + ra];
-        const int64_t o = ((int64_t)pf * p.nra + ra) * p.nel + ele;
-        p.map[o] = (e8 & 1) ? -v.y * sc : v.x * sc;
-        p.weight[o] = wv;
-      }
-  }
-}
-
-// The same with SIXTEEN elevations per block (round 4).  HBM serves 128-byte lines: read in 64-byte pieces at a 4 KB
-// stride -- what 8 elevations of complex64 are -- it delivers 3.0 TB/s, in 128-byte pieces 6.2 (tools/probe/piece_bw.hip),
-// and 3.0 TB/s is exactly what the load phase of k_rm_fused ran at.  The LDS holds the inverse-FFT image of 8 elevations, no
-// more; so the block reads 128-byte pieces (lane = (m, 16 elevations)), puts the modes of elevations 0-7 into the LDS
-// image as before and PARKS those of elevations 8-15 in a global scratch image (131 KB per block, 64-byte pieces in
-// natural order; it lives in L2 / the Infinity Cache until it is read back), transforms and stores the first eight, reads
-// the parked image in (bit reversal on the LDS side), transforms and stores the second eight.
-constexpr int kFuEl16 = 16;
-// PARK = false: the image of all sixteen elevations fits the LDS (nra <= 1024): no parking, one transform of eight
-// sequences, 128-byte pieces on the way out too.
-template <bool PARK>
-__global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, int ntile_el, double2* __restrict__ park) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  __shared__ double s_acc[3][kFuThreads / 64][kFuEl16];
-  __shared__ double s_nrm[kFuEl16], s_wv[kFuEl16];
-  C<double>* buf = reinterpret_cast<C<double>*>(smem);  // [4][P] (PARK) or [8][P]
-  C<double>* twl = buf + (size_t)(PARK ? 4 : 8) * q.P;
-  const int N = p.nra, M = q.M, P = q.P;
-  const int64_t tile_lin = blockIdx.x;  // (grid = tiles exactly)
   C<double>* const pk = reinterpret_cast<C<double>*>(park) + (size_t)blockIdx.x * 4 * N;
   const int pf = (int)(tile_lin / ntile_el), tile = (int)(tile_lin - (int64_t)pf * ntile_el);
   const int pol = pf / p.nfreq, f = pf - pol * p.nfreq;
-  const int el0 = tile * kFuEl16;
+  const int el0 = tile * EL;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int eli = lane & 15, ms = lane >> 4;  // 16 elevations x 4 m per wave: 128-byte pieces of the input rows
+  const int eli = lane & (EL - 1), ms = lane / EL;  // EL elevations x 64 / EL m per wave
   const int el = el0 + eli;
   const bool el_ok = el < p.nel;
   const int elc = el_ok ? el : p.nel - 1;
   for (int k = threadIdx.x; k < (M >> 1); k += kFuThreads) twl[k] = {q.tw[k].x, q.tw[k].y};
   const int nterm = 2 * p.new_;
   double acc_d = 0.0, acc_q = 0.0, acc_p = 0.0;
-  for (int mb = 0; mb < p.nm; mb += 4 * (kFuThreads / 64)) {
-    const int m = mb + wave * 4 + ms;
+  // (measured, CHIME-like shape, EL = 8, 0.89 ms as it stands: the load phase alone takes 0.72 ms = 3.0 TB/s -- 64-byte
+  // pieces are what the LDS allows, 8 elevations x 2048 RA x 16 bytes --; two m per lane and pass, i.e. 32 loads in flight
+  // per lane: 0.93; the term weights from a table made by a pre-pass instead of in the loop: 0.95; blocks staggered over m
+  // so that they do not read the same rows at the same time: 1.07 -- lock step is what keeps the DRAM pages open.)
+  for (int mb = 0; mb < p.nm; mb += kMW * (kFuThreads / 64)) {
+    const int m = mb + wave * kMW + ms;
     const bool m_ok = m < p.nm;
     const int mc = m_ok ? m : p.nm - 1;
     double sw = 0.0, mre = 0.0, mim = 0.0, sg = 0.0;
-    for (int t0 = 0; t0 < nterm; t0 += 8) {
-      // lane `eli` of the group works out the weights of term t0 + eli of its m; the group's lanes pick them up below
+    for (int t0 = 0; t0 < nterm; t0 += kTermBatch) {
+      // lane `eli & 7` of each 8-lane group works out the weights of term t0 + (eli & 7) of its m; the group's lanes pick
+      // them up below (with EL = 16 both halves of an m work them out: each picks them up from its own)
       double w = 0.0, g = 0.0;
-      {
-        const int t = t0 + (eli & 7);  // (both 8-lane halves of an m work the weights out: each picks them up from its own)
-        if (t < nterm) {
-          const int s = t / p.new_, e = t - s * p.new_;
-          const int64_t wbase = ((((int64_t)mc * 2 + s) * p.npol + pol) * p.nfreq + f) * p.new_;
-          double iv = (double)p.hw[wbase + e];
-          if (p.mode == 0) {
-            w = iv > 0.0 ? p.wt[e] : 0.0;
-          } else {
-            iv *= p.wt[e];
-            if (p.mode == 1) {
-              double wsumv = 0.0;
-              for (int e2 = 0; e2 < p.new_; ++e2) wsumv += (double)p.hw[wbase + e2] * p.wt[e2];
-              w = iv * (wsumv != 0.0 ? 1.0 / wsumv : 0.0);
-            } else {
-              w = iv;
-            }
-            if (!(iv > 0.0)) w = 0.0;
-          }
-          g = w * w * (iv > 0.0 ? 1.0 / iv : 0.0);
-        }
-      }
-      float2 h[8], b[8];
-      double w2[8], g2[8];
+      if (t0 + (eli & 7) < nterm) rm_term_weight(p, mc, pol, f, t0 + (eli & 7), w, g);
+      float2 h[kTermBatch], b[kTermBatch];
+      double w2[kTermBatch], g2[kTermBatch];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
+      for (int k = 0; k < kTermBatch; ++k) {
         const bool live = t0 + k < nterm;
         const int tg = live ? t0 + k : nterm - 1, s = tg / p.new_, e = tg - s * p.new_;
         const double wk = __shfl(w, (lane & ~7) + k, 64), gk = __shfl(g, (lane & ~7) + k, 64);
@@ -564,7 +431,7 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, 
         b[k] = p.bv[rbase];
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
+      for (int k = 0; k < kTermBatch; ++k) {
         const double br = b[k].x, bi = b[k].y, hr = h[k].x, hi = h[k].y;
         const double b2 = br * br + bi * bi;
         sw = fma(w2[k], b2, sw);
@@ -573,19 +440,8 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, 
         sg = fma(g2[k], b2, sg);
       }
     }
-    double ar = 0.0, ai = 0.0;
-    if (m_ok && el_ok) {
-      const double cinv = p.eps[(int64_t)f * p.nm + m] + sw;  // (skip_deconvolution takes the three-kernel path)
-      const double ic = cinv != 0.0 ? 1.0 / cinv : 0.0;
-      const double win = p.window ? (double)p.window[((int64_t)f * p.nm + m) * p.nel + el] : 1.0;
-      ar = win * mre * ic;
-      ai = win * mim * ic;
-      const double rd = win * sw * ic;
-      const double qv = sqrt(sg) * win * ic / (double)(p.mmax + 1);
-      acc_d += rd;
-      acc_q += qv * qv;
-      acc_p += ((m == 0 || 2 * m == N) ? 1.0 : 2.0) * rd * rd;
-    }
+    double ar = 0.0, ai = 0.0, rd;
+    if (m_ok && el_ok) rm_mode(p, sw, mre, mim, sg, m, f, el, ar, ai, rd, acc_d, acc_q, acc_p);  // (never launched with `skip`)
     const bool edge = m == 0 || 2 * m == N;  // DC and Nyquist bins are real, and their own mirror
     if (edge) ai = 0.0;
     // rows 2j (A) and 2j + 1 (B) share a transform: z = X_A + i X_B, loaded conjugated at the bit-reversed position
@@ -594,20 +450,20 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, 
       const bool odd = eli & 1;
       const double a_r = odd ? orr : ar, a_i = odd ? oi : ai, b_r = odd ? ar : orr, b_i = odd ? ai : oi;
       const C<double> lo = {a_r - b_i, -(a_i + b_r)}, hi = {a_r + b_i, a_i - b_r};  // bins m and N - m (= conj(X[m]) of both rows)
-      if (!PARK || eli < 8) {  // elevations 0-7 (all sixteen without parking): straight into the LDS image (bit-reversed positions)
+      if (!PARK || eli < 8) {  // straight into the LDS image (bit-reversed positions)
         C<double>* row = buf + (size_t)(eli >> 1) * P;
         if (!odd) row[dmm_fft::bitrev(m, q.logM)] = lo;
         else if (!edge) row[dmm_fft::bitrev(N - m, q.logM)] = hi;
-      } else {        // elevations 8-15: parked in natural order (64-byte pieces per image row), transformed second
+      } else {  // elevations 8-15: parked in natural order (64-byte pieces per image row), transformed second
         C<double>* row = pk + (size_t)((eli - 8) >> 1) * N;
         if (!odd) row[m] = lo;
         else if (!edge) row[N - m] = hi;
       }
     }
   }
-  // the block's per-row sums over m: the 4 m of a wave by a butterfly, the waves in a fixed order
+  // the block's per-row sums over m: the m of a wave by a butterfly, the waves in a fixed order
 #pragma unroll
-  for (int o = 16; o < 64; o <<= 1) {
+  for (int o = EL; o < 64; o <<= 1) {
     acc_d += __shfl_xor(acc_d, o, 64);
     acc_q += __shfl_xor(acc_q, o, 64);
     acc_p += __shfl_xor(acc_p, o, 64);
@@ -618,37 +474,20 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, 
     s_acc[2][wave][eli] = acc_p;
   }
   __syncthreads();
-  if (threadIdx.x < kFuEl16) {
+  if (threadIdx.x < EL) {
     double d = 0.0, q2 = 0.0, p2 = 0.0;
     for (int w2 = 0; w2 < kFuThreads / 64; ++w2) {
       d += s_acc[0][w2][threadIdx.x];
       q2 += s_acc[1][w2][threadIdx.x];
       p2 += s_acc[2][w2][threadIdx.x];
     }
-    const double mean = d / (double)p.nm;
-    const double nrm = mean != 0.0 ? 1.0 / mean : 0.0;
-    const double sv = 0.5 * nrm * nrm * q2;
-    s_nrm[threadIdx.x] = nrm;
-    s_wv[threadIdx.x] = sv != 0.0 ? 1.0 / sv : 0.0;
-    if (el0 + (int)threadIdx.x < p.nel) p.dbp[(int64_t)pf * p.nel + el0 + threadIdx.x] = nrm * nrm * p2 / (double)N / (double)N;  // Parseval
+    double dbp;
+    rm_row_finish(d, q2, p2, p.nm, N, s_nrm[threadIdx.x], s_wv[threadIdx.x], dbp);
+    if (el0 + (int)threadIdx.x < p.nel) p.dbp[(int64_t)pf * p.nel + el0 + threadIdx.x] = dbp;
   }
   __syncthreads();
-  if (!PARK) {
-    dmm_fft::fft_dit<double, false, kFuThreads>(buf, twl, 8, M, q.logM, P);
-    const int e16 = threadIdx.x & 15;
-    const int ele = el0 + e16;
-    const double sc = s_nrm[e16] / (double)N, wv = s_wv[e16];
-    if (ele < p.nel)
-      for (int ra = threadIdx.x >> 4; ra < N; ra += kFuThreads / 16) {
-        const C<double> v = buf[(size_t)(e16 >> 1) * P + ra];
-        const int64_t o = ((int64_t)pf * p.nra + ra) * p.nel + ele;
-        p.map[o] = (e16 & 1) ? -v.y * sc : v.x * sc;
-        p.weight[o] = wv;
-      }
-    return;
-  }
-  for (int half = 0; half < 2; ++half) {
-    if (half == 1) {  // the parked image of elevations 8-15 comes in (coalesced reads, bit reversal on the LDS side)
+  for (int pass = 0; pass < kPass; ++pass) {
+    if (pass == 1) {  // the parked image of elevations 8-15 comes in (coalesced reads, bit reversal on the LDS side)
       __syncthreads();
       for (int idx = threadIdx.x; idx < 4 * N; idx += kFuThreads) {
         const int j = idx / N, n = idx - j * N;
@@ -656,16 +495,16 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused16(RmParams p, RmFft q, 
       }
       __syncthreads();
     }
-    dmm_fft::fft_dit<double, false, kFuThreads>(buf, twl, 4, M, q.logM, P);
-    // y = conj(result) / N: even row = Re, odd row = -Im, each times its row's normalisation; 64-byte pieces of [ra][el]
-    const int e8 = threadIdx.x & 7;
-    const int ele = el0 + 8 * half + e8;
-    const double sc = s_nrm[8 * half + e8] / (double)N, wv = s_wv[8 * half + e8];
+    dmm_fft::fft_dit<double, false, kFuThreads>(buf, twl, kSeq, M, q.logM, P);
+    // y = conj(result) / N: even row = Re, odd row = -Im, each times its row's normalisation; pieces of 8 kElOut bytes of [ra][el]
+    const int eo = threadIdx.x & (kElOut - 1);
+    const int ele = el0 + kElOut * pass + eo;
+    const double sc = s_nrm[kElOut * pass + eo] / (double)N, wv = s_wv[kElOut * pass + eo];
     if (ele < p.nel)
-      for (int ra = threadIdx.x >> 3; ra < N; ra += kFuThreads / 8) {
-        const C<double> v = buf[(size_t)(e8 >> 1) * P + ra];
+      for (int ra = threadIdx.x / kElOut; ra < N; ra += kFuThreads / kElOut) {
+        const C<double> v = buf[(size_t)(eo >> 1) * P + ra];
         const int64_t o = ((int64_t)pf * p.nra + ra) * p.nel + ele;
-        p.map[o] = (e8 & 1) ? -v.y * sc : v.x * sc;
+        p.map[o] = (eo & 1) ? -v.y * sc : v.x * sc;
         p.weight[o] = wv;
       }
   }
@@ -697,10 +536,19 @@ __global__ __launch_bounds__(kThreads) void k_rm_store(RmParams p) {
   }
 }
 
-inline int ilog2i(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
+// Which kernels take a call: the three-kernel form, or a single pass with 8 / 16 / 16 (second eight parked) elevations
+// per block.
+enum RmForm { kRmThreeKernel, kRmSingle8, kRmSingle16, kRmSingle16Parked };
+
+// The form of a call the single pass can take.  "ringmap_variant" = 1: the three-kernel form, 2: the 8-elevation form.
+// The parked half of the image is 131 KB per block at nra = 2048 and is indexed by TILE: it grows with nfreq npol nel, and
+// the form only pays while it stays in the Infinity Cache (256 MiB) -- beyond that the 8-elevation form takes the call
+// (0.5 GB of scratch at 4096 tiles, kept by the context)
+RmForm rm_single_pass_form(bool lds16_fits, size_t park_bytes, int variant) {
+  if (variant == 1) return kRmThreeKernel;
+  if (variant == 2) return kRmSingle8;
+  if (lds16_fits) return kRmSingle16;
+  return park_bytes <= ((size_t)192 << 20) ? kRmSingle16Parked : kRmSingle8;
 }
 
 // window[f, m, el] = sum_i coef_i cos(2 pi i x), x = (m - min_m[f, el]) / (max_m[f, el] - min_m[f, el]), zero outside
@@ -745,7 +593,7 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   if (rc) return rc;
   RmFft q;
   q.M = t->M;
-  q.logM = ilog2i(t->M);
+  q.logM = ilog2(t->M);
   q.blue = t->chirp != nullptr;
   q.tw = (const double2*)t->tw;
   q.chirp = (const double2*)t->chirp;
@@ -783,35 +631,32 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   p.db = dirty_beam;
   // one pass over the m-modes where the whole inverse FFT of 8 elevations fits the LDS (power-of-two nra up to 2048)
   const size_t fused_lds = (size_t)4 * q.P * sizeof(double2) + tw_b;
-  if (!dirty_beam && !skip_deconvolution && !q.blue && nra >= 8 && fused_lds <= 150 * 1024 && ctx->opt_ringmap_variant != 1 && ctx->opt_ringmap_variant != 2) {
-    // sixteen elevations per block: 128-byte pieces of the input rows ("ringmap_variant" = 2: the 8-elevation form)
-    const int ntile_el = (nel + kFuEl16 - 1) / kFuEl16;
+  const size_t lds16 = (size_t)8 * q.P * sizeof(double2) + tw_b;  // all sixteen elevations' image in the LDS?
+  const int64_t ntile16 = (int64_t)((nel + 15) / 16) * npol * nfreq;
+  const size_t park_bytes = (size_t)ntile16 * 4 * nra * sizeof(double2);
+  const bool single_ok = !dirty_beam && !skip_deconvolution && !q.blue && nra >= 8 && fused_lds <= 150 * 1024;
+  const RmForm form = single_ok ? rm_single_pass_form(lds16 <= 150 * 1024, park_bytes, ctx->opt_ringmap_variant) : kRmThreeKernel;
+  if (form != kRmThreeKernel) {
+    const int el_blk = form == kRmSingle8 ? 8 : 16;
+    const int ntile_el = (nel + el_blk - 1) / el_blk;
     const int64_t ntile = (int64_t)ntile_el * npol * nfreq;
-    const size_t lds16 = (size_t)8 * q.P * sizeof(double2) + tw_b;  // all sixteen elevations' image in the LDS?
-    // The parked half of the image is 131 KB per block at nra = 2048 and is indexed by TILE: it grows with nfreq npol nel, and
-    // the form only pays while it stays in the Infinity Cache (256 MiB) -- beyond that the 8-elevation form below takes the
-    // call (0.5 GB of scratch at 4096 tiles, kept by the context)
-    const size_t park_bytes = (size_t)ntile * 4 * nra * sizeof(double2);
-    if (lds16 > 150 * 1024 && park_bytes > ((size_t)192 << 20)) goto eight_elevations;
-    if (lds16 <= 150 * 1024) {
-      DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-      hipLaunchKernelGGL(k_rm_fused16<false>, dim3((unsigned)ntile), dim3(kFuThreads), lds16, ctx->stream, p, q, ntile_el, (double2*)nullptr);
-    } else {
-      void* park = nullptr;
-      rc = dmm_get_scratch(ctx, park_bytes + 256, &park);
-      if (rc) return rc;
-      DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-      hipLaunchKernelGGL(k_rm_fused16<true>, dim3((unsigned)ntile), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el, (double2*)park);
+    void* park = nullptr;
+    switch (form) {
+      case kRmSingle8:  // (the grid in whole groups of 16 ids: the XCD pairing of the tiles)
+        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
+        hipLaunchKernelGGL((k_rm_fused<8, false>), dim3((unsigned)((ntile + 15) / 16 * 16)), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el, (double2*)nullptr);
+        break;
+      case kRmSingle16:
+        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        hipLaunchKernelGGL((k_rm_fused<16, false>), dim3((unsigned)ntile), dim3(kFuThreads), lds16, ctx->stream, p, q, ntile_el, (double2*)nullptr);
+        break;
+      default:  // kRmSingle16Parked
+        rc = dmm_get_scratch(ctx, park_bytes + 256, &park);
+        if (rc) return rc;
+        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
+        hipLaunchKernelGGL((k_rm_fused<16, true>), dim3((unsigned)ntile), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el, (double2*)park);
+        break;
     }
-    DMM_HIP(hipGetLastError());
-    return DMM_OK;
-  }
-eight_elevations:
-  if (!dirty_beam && !skip_deconvolution && !q.blue && nra >= 8 && fused_lds <= 150 * 1024 && ctx->opt_ringmap_variant != 1) {
-    const int ntile_el = (nel + kFuEl - 1) / kFuEl;
-    const int64_t ntile = (int64_t)ntile_el * npol * nfreq;
-    DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-    hipLaunchKernelGGL(k_rm_fused, dim3((unsigned)((ntile + 15) / 16 * 16)), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el);
     DMM_HIP(hipGetLastError());
     return DMM_OK;
   }

@@ -162,18 +162,9 @@ __global__ void k_fill_ring_tables(const double* phi0, int nring, int mmax, doub
 template <int NROW, bool BLUE>
 __device__ __forceinline__ void ring_dft(const RingLds& l, const double2* bfilt, int M, int logM, bool radix8 = false) {
   const int P = M + 1;
-  if (radix8) dmm_fft::fft_dif8<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
+  if (BLUE) dmm_fft::bluestein_convolve<double, kFftThreads>(l.buf, l.tw, bfilt, NROW, M, logM, P, radix8);
+  else if (radix8) dmm_fft::fft_dif8<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
   else dmm_fft::fft_dif<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
-  if (BLUE) {
-    for (int idx = threadIdx.x; idx < NROW * M; idx += kFftThreads) {
-      const int r = idx / M, k = idx - r * M;
-      const double2 fk = bfilt[k];
-      l.buf[r * P + k] = dmm_fft::cmul<double>(l.buf[r * P + k], {fk.x, fk.y});
-    }
-    __syncthreads();
-    if (radix8) dmm_fft::fft_dit8<double, true, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
-    else dmm_fft::fft_dit<double, true, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
-  }
 }
 
 template <bool BLUE>

@@ -220,19 +220,13 @@ def test_analytic_beam_vs_oracle(mmax, oddra, nel, nfreq):
         assert np.all(got[mmax, 1] == 0)
 
 
-@pytest.mark.parametrize("nm,nel", [(257, 77), (1025, 37)])  # nra 512: all sixteen elevations' image in the LDS; nra 2048: the second eight parked
-def test_single_pass_kernel_against_the_three_kernel_form(nm, nel):
-    """The single-pass kernel (power-of-two nra, no RA-space dirty beam, own-row normalisation: reduce, inverse FFT and
-    the [ra][el] store in one pass over the m-modes; 16 elevations per block, the second eight parked in a scratch image,
-    and the 8-elevation form of round 3) against the three-kernel form on the same
-    inputs ("ringmap_variant" = 1), at a shape with several m passes, partial elevation tiles and an odd row count."""
+def _single_pass_against_three_kernels(nm, nel, new, npol, nfreq):
     import torch
 
     from draco_amd import _lib
     from draco_amd.device import Context, ptr
 
     ctx = Context.get()
-    npol, nfreq, new = 2, 3, 4
     nra = 2 * (nm - 1)
     gen = torch.Generator(device=ctx.device).manual_seed(3)
     shp = (nm, 2, npol, nfreq, new, nel)
@@ -240,7 +234,7 @@ def test_single_pass_kernel_against_the_three_kernel_form(nm, nel):
     bv = torch.randn(shp, dtype=torch.complex64, device=ctx.device, generator=gen)
     hw = torch.rand(shp[:-1], dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
     hw[torch.rand(shp[:-1], device=ctx.device, generator=gen) < 0.1] = 0
-    table = ctx.to_device(np.array([0.0, 1.0, 1.0, 1.0]), np.float64)  # first cylinder pair excluded
+    table = ctx.to_device(np.array([0.0 if new > 1 else 1.0] + [1.0] * (new - 1)), np.float64)  # first cylinder pair excluded (kept where it is the only one)
     eps = ctx.to_device(np.full((nfreq, nm), 1e-2), np.float64)
     win = torch.rand((nfreq, nm, nel), dtype=torch.float32, device=ctx.device, generator=gen)
     out = {}
@@ -263,3 +257,25 @@ def test_single_pass_kernel_against_the_three_kernel_form(nm, nel):
                 assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max(), (v, mode)
         for a, b in zip(out[0, mode], out[2, mode]):  # the two single-pass forms differ in the order of the per-row sums over m only
             assert np.abs(a - b).max() <= 1e-13 * np.abs(b).max(), mode
+
+
+@pytest.mark.parametrize("nm,nel", [(257, 77), (1025, 37)])  # nra 512: all sixteen elevations' image in the LDS; nra 2048: the second eight parked
+def test_single_pass_kernel_against_the_three_kernel_form(nm, nel):
+    """The single-pass kernel (power-of-two nra, no RA-space dirty beam, own-row normalisation: reduce, inverse FFT and
+    the [ra][el] store in one pass over the m-modes; 16 elevations per block, the second eight parked in a scratch image,
+    and the 8-elevation form of round 3) against the three-kernel form on the same
+    inputs ("ringmap_variant" = 1), at a shape with several m passes, partial elevation tiles and an odd row count."""
+    _single_pass_against_three_kernels(nm, nel, new=4, npol=2, nfreq=3)
+
+
+@pytest.mark.parametrize(
+    "nm,nel,new",
+    [(5, nel, new) for nel in (1, 17) for new in (1, 5)]  # nra 8, the shortest the single pass takes
+    + [(1025, nel, 3) for nel in (8, 9, 24)],  # nra 2048: the parked half of the tile empty, one elevation, full
+)
+def test_single_pass_kernel_term_batches_and_tile_remainders(nm, nel, new):
+    """The same comparison where the 8-term batches and the elevation tiles are cut short: 2 terms (one batch, six dead
+    slots) and 10 (a second batch with two live), a lone elevation, and tiles whose second eight elevations are absent,
+    a single one, or all there."""
+    _single_pass_against_three_kernels(nm, nel, new, npol=1, nfreq=2)
+
