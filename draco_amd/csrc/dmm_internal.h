@@ -39,7 +39,7 @@ struct dmm_ctx {
   std::map<int64_t, void*> sht;            // SHT geometry caches keyed by (nside,lmax,mmax)
   int opt_dirty_variant = 0;               // tuning knobs, see dmm_ctx_set_option
   int opt_grid_mult = 0;
-  int opt_dirty_prio = 0;                  // 1: k_dirty's waves run at raised issue priority (A/B: beside the side stream's SHT)
+  int opt_dirty_prio = 0;                  // 1: k_dirty's waves run at raised issue priority, whatever the days per launch (A/B: beside the side stream's SHT)
   int opt_dirty_static = 0;                // 1: static striding of the dirty kernel's task list (default: dynamic hand-out)
   int opt_project_grid_mult = 0;
   int opt_project_variant = 0;
@@ -102,7 +102,6 @@ struct dmm_plan {
   int64_t ntile = 0;
   int npairs = 0, npol = 0, lmax = 0, nfreq = 0, n_m = 0, b_dtype = 0, b_layout = 0;
   std::vector<dmm_tile> tiles_h;
-  std::vector<int32_t> work_start_h;   // host copy of work_start_d
   dmm_tile* tiles_d = nullptr;
   int32_t* work_start_d = nullptr;   // [ntile+1] first column-block task of each tile (dirty)
   int32_t* work_rows_d = nullptr;    // [ntile+1] first 64-row-block task of each tile (project)
@@ -172,6 +171,16 @@ int dmm_set_error(int code, const char* fmt, ...);
   } while (0)
 
 int dmm_fft_tables_f64(dmm_ctx* ctx, int n, dmm_fft_tables** out);  // mfft.hip
+// solve_dirty.hip, for the dense solvers: the Dirty kernel over a compact list of the plan's tiles.  `tiles_d` / `work_d` are
+// device arrays of nmat tiles and the nmat + 1 prefix sums of their column-block tasks (nwork = the last of them), as
+// dmm_dirty_tile_list fills them on the host from the tile numbers `ids`.
+void dmm_dirty_tile_list(const dmm_plan* pl, const int64_t* ids, int n, std::vector<dmm_tile>& tiles, std::vector<int32_t>& work);
+// a = B^H (Ni o v) (the right-hand sides of the sky-side systems)
+int dmm_dirty_launch_list(dmm_plan* pl, const void* B, const void* mvis, const double* mweight, const dmm_tile* tiles_d,
+                          const int32_t* work_d, int nmat, int64_t nwork, void* alm);
+// a = Sl o B^H w (Wiener / ML back-projection): wbuf[i * ntel ...] belongs to tiles_d[i], Sl may be NULL
+int dmm_dirty_w_launch_list(dmm_plan* pl, const void* B, const double2* wbuf, const double* Sl, const dmm_tile* tiles_d,
+                            const int32_t* work_d, int nmat, int64_t nwork, void* alm);
 int dmm_ml_two_stage_max_order();  // solve_dense.hip: the largest order the ML band reduction takes
 
 static inline bool dmm_is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }

@@ -620,14 +620,6 @@ DenseParams make_params(const dmm_plan* pl, const Layout& L, const void* B, cons
 
 }  // namespace
 
-// implemented in solve_dirty.hip: a = S o B^H w over tiles [tile0, tile0+nmat)
-int dmm_dirty_w_launch(dmm_plan* pl, const void* B, const double2* wbuf, const double* Sl, int64_t tile0, int nmat,
-                       void* alm);
-int dmm_dirty_w_launch_list(dmm_plan* pl, const void* B, const double2* wbuf, const double* Sl, const dmm_tile* tiles_d,
-                            const int32_t* work_d, int nmat, int64_t nwork, void* alm);
-int dmm_dirty_launch_list(dmm_plan* pl, const void* B, const void* mvis, const double* mweight, const dmm_tile* tiles_d,
-                          const int32_t* work_d, int nmat, int64_t nwork, void* alm);
-
 namespace {
 // B^H Ni v of the sky-side tiles only -- the right-hand sides of their systems (the telescope-side tiles, most of the
 // bytes of B, get their a_lm from the back-projection): lists of at most `cap` tiles through the batch's device arrays
@@ -640,13 +632,7 @@ int sky_rhs(dmm_plan* pl, const void* B, const void* mvis, const double* mweight
   hipStream_t st = pl->ctx->stream;
   for (size_t i0 = 0; i0 < all.size(); i0 += cap) {
     const int nmat = (int)std::min<size_t>(cap, all.size() - i0);
-    tiles_c.resize(nmat);
-    work_c.assign(nmat + 1, 0);
-    for (int i = 0; i < nmat; ++i) {
-      tiles_c[i] = pl->tiles_h[all[i0 + i]];
-      const int ncol = pl->npol * (pl->lmax + 1 - tiles_c[i].m);
-      work_c[i + 1] = work_c[i] + (ncol + pl->cols_per_block - 1) / pl->cols_per_block;
-    }
+    dmm_dirty_tile_list(pl, all.data() + i0, nmat, tiles_c, work_c);
     DMM_HIP(hipMemcpyAsync(tiles_d, tiles_c.data(), nmat * sizeof(dmm_tile), hipMemcpyHostToDevice, st));
     DMM_HIP(hipMemcpyAsync(work_d, work_c.data(), (nmat + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     DMM_HIP(hipStreamSynchronize(st));  // the host vectors are reused
@@ -794,13 +780,7 @@ int dmm_wiener_run(dmm_plan* pl, const void* B, const void* mvis, const double* 
     double2* const Xh = Xbuf + off * L.Np * L.Np;
     std::vector<dmm_tile>& tc = tiles_c[h];
     std::vector<int32_t>& wc = work_c[h];
-    tc.resize(nmat);
-    wc.assign(nmat + 1, 0);
-    for (int i = 0; i < nmat; ++i) {
-      tc[i] = pl->tiles_h[list[i0 + i]];
-      const int ncol = pl->npol * (pl->lmax + 1 - tc[i].m);
-      wc[i + 1] = wc[i] + (ncol + pl->cols_per_block - 1) / pl->cols_per_block;
-    }
+    dmm_dirty_tile_list(pl, list.data() + i0, nmat, tc, wc);
     DMM_HIP(hipMemcpyAsync(tiles_h, tc.data(), nmat * sizeof(dmm_tile), hipMemcpyHostToDevice, S));
     DMM_HIP(hipMemcpyAsync(work_h, wc.data(), (nmat + 1) * sizeof(int32_t), hipMemcpyHostToDevice, S));
     const int T = p.T;
@@ -1124,13 +1104,7 @@ int dmm_ml_run(dmm_plan* pl, const void* B, const void* mvis, const double* mwei
     p.alm = (double2*)alm;
     p.theta = theta_b;
     // the batch's tiles (and, telescope side, the column-block prefix of the back-projection)
-    tiles_c.resize(nmat);
-    work_c.assign(nmat + 1, 0);
-    for (int i = 0; i < nmat; ++i) {
-      tiles_c[i] = pl->tiles_h[list[i0 + i]];
-      const int ncol = pl->npol * (pl->lmax + 1 - tiles_c[i].m);
-      work_c[i + 1] = work_c[i] + (ncol + pl->cols_per_block - 1) / pl->cols_per_block;
-    }
+    dmm_dirty_tile_list(pl, list.data() + i0, nmat, tiles_c, work_c);
     DMM_HIP(hipMemcpyAsync(tiles_b, tiles_c.data(), nmat * sizeof(dmm_tile), hipMemcpyHostToDevice, ctx->stream));
     DMM_HIP(hipMemcpyAsync(work_b, work_c.data(), (nmat + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     DMM_HIP(hipStreamSynchronize(ctx->stream));  // the host vectors are reused by the next batch
@@ -1397,14 +1371,8 @@ int dmm_ml_run(dmm_plan* pl, const void* B, const void* mvis, const double* mwei
     p.alm = (double2*)alm;
     H.nmat = nmat;
     H.np = p.Np;
-    H.tiles.resize(nmat);
-    H.work.assign(nmat + 1, 0);
     H.ids.assign(list.begin() + i0, list.begin() + i0 + nmat);
-    for (int i = 0; i < nmat; ++i) {
-      H.tiles[i] = pl->tiles_h[list[i0 + i]];
-      const int ncol = pl->npol * (pl->lmax + 1 - H.tiles[i].m);
-      H.work[i + 1] = H.work[i] + (ncol + pl->cols_per_block - 1) / pl->cols_per_block;
-    }
+    dmm_dirty_tile_list(pl, H.ids.data(), nmat, H.tiles, H.work);
     redo_is_sky[h] = sky;
     redo_np[h] = np_sky;
     DMM_HIP(hipMemcpyAsync(tiles_h, H.tiles.data(), nmat * sizeof(dmm_tile), hipMemcpyHostToDevice, S1));

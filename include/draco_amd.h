@@ -79,7 +79,9 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *    3 its reading sweeps as one block per matrix; 2 none deferred; 1 one-stage), "ml_chase_split" (1: one chase launch with the full band image), "gram_stage"
  *    (1: LDS-DMA operand staging of the Gram kernel), "wiener_overlap" (0: one stream);
  *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "regrid_workspace_mib" (0 = 12 GiB: a cfg-3 day in one launch), "grid_mult", "project_grid_mult";
- *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio", "project_variant", "ringmap_variant" (1 three-kernel
+ *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio" (1: the Dirty kernel's waves raise their issue priority;
+ *    it applies to dmm_dirty_run and to every group of dmm_dirty_run_multi -- the multi-day launches used to ignore it),
+ *    "project_variant", "ringmap_variant" (1 three-kernel
  *    form, 2 eight elevations per block), "sht_variant" (bits: 0-1 vector-ALU synthesis form, 2 direct ring sums,
  *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x in the analysis, 6 first MFMA synthesis form,
  *    7 pipelined synthesis with 4 frequencies per block, 11 radix-4 ring FFTs), "sht_synth_form" (1: first MFMA form);

@@ -1,7 +1,7 @@
 """Shape sweep of ``csrc/solve_dirty.hip`` at the C ABI against the long-double reference of ``tests/dirty_twin.py``.
 
-Tile tables and random pools are made by hand (no provider, no telescope), so every shape-dependent path of ``k_dirty``,
-``k_dirty_multi`` and ``k_project`` / ``k_project_rg`` is placed on purpose: rows below / on / above multiples of the
+Tile tables and random pools are made by hand (no provider, no telescope), so every shape-dependent path of ``k_dirty``
+(one day and 8 / 4 / 2 days per launch) and ``k_project`` / ``k_project_rg`` is placed on purpose: rows below / on / above multiples of the
 pipelined loop's ``kUnroll``, one or two columns per lane, both layouts, the 8/4/2/1-day groups, row groups of 8 inside
 64-row tasks, ticket and static task hand-out, every tuning variant the timing tools switch on.
 
@@ -455,7 +455,7 @@ def test_lds_limit_npairs_3072(kind):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# k_dirty_multi
+# k_dirty, several days per launch (dmm_dirty_run_multi)
 
 MULTI_D = (1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 16)
 MULTI_NPAIRS = (23, 512, 513, 763, 1024, 1025, 2048, 2049)
