@@ -185,6 +185,7 @@ class SolveEngine:
         self.last_b_bytes = 0
         self.fills = 0  # slabs actually filled (the others were resident)
         self.launch_events = None  # set to a list to collect (start, stop, b_bytes, ntile) per Dirty / project launch
+        self._alm_internal = False  # the pass's a_lm never leaves the library (`solve_many`): Dirty skips its l < m zeros
         self._ws_offer = {}
         self._basis_wkey = None
         self._ws = None
@@ -427,7 +428,7 @@ class SolveEngine:
         cb = None if on_freqs_done is None else (lambda d, alm, f0, f1: on_freqs_done(alm, f0, f1))
         return self.solve_many(kind, [mvis_d], [mweight_d], freq_ind, mmax, on_freqs_done=cb, slabs=slabs, **params)[0]
 
-    def solve_many(self, kind, mvis_l, mweight_l, freq_ind, mmax, on_freqs_done=None, slabs=None, **params):
+    def solve_many(self, kind, mvis_l, mweight_l, freq_ind, mmax, on_freqs_done=None, slabs=None, alm_internal=False, **params):
         """D sidereal days against ONE pass over B: a list of ``alm``, one per day.  The slab loop of every solve.
 
         Every slab of B is made resident once (one PCIe crossing for providers whose tiles live on the host) and
@@ -437,6 +438,9 @@ class SolveEngine:
         run one after the other inside the slab.  ``on_freqs_done(d, alm_d, f0, f1)`` as in :meth:`solve`, per day.
         ``slabs``: ready :class:`Slab` objects to run instead of the engine's own carving of (``freq_ind``, m <= ``mmax``)
         -- a hand-made tile list, its pool filled by the caller (single-tile solves).
+        ``alm_internal``: the caller hands the a_lm to ``dmm_alm2map`` alone and drops it -- ``"dirty"`` then leaves the
+        structural zeros ``l < m`` unwritten (half the a_lm's bytes; the synthesis reads ``l >= m`` only): those entries
+        of the returned arrays are undefined.
         """
         tel = self.provider.telescope
         D = len(mvis_l)
@@ -463,6 +467,7 @@ class SolveEngine:
         self._ws_offer = {}
         self._basis_wkey = None  # (the weight-range verdict of the resident bases is per call)
         self._ws = None
+        self._alm_internal = bool(alm_internal)
         issued, f_done = 0, 0
         for slab in slabs if slabs is not None else self.slabs(freq_ind, mmax, nfreq, n_m):
             self.last_b_bytes += slab.b_bytes
@@ -480,8 +485,15 @@ class SolveEngine:
         ``dmm_dirty_run``)."""
         PA = C.c_void_p * len(alms)
         pv, pw, pa = PA(*[ptr(x) for x in mvis_l]), PA(*[ptr(x) for x in mweight_l]), PA(*[ptr(x) for x in alms])
-        with self._timed(slab):
-            _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, len(alms)))
+        nofill = self._alm_internal
+        if nofill:
+            _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, b"dirty_nofill", 1))
+        try:
+            with self._timed(slab):
+                _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, len(alms)))
+        finally:
+            if nofill:
+                _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, b"dirty_nofill", 0))
 
     def _run_wiener(self, slab, mvis_l, mweight_l, alms, params):
         """One slab's Wiener solves, day after day."""

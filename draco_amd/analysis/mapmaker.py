@@ -132,9 +132,10 @@ class BaseMapMaker(ContainerTask):
         cb = None if on_freqs_done is None else (lambda d, alm, f0, f1: on_freqs_done(alm, f0, f1))
         return self.make_alm_many([mmodes], on_freqs_done=cb)[0]
 
-    def make_alm_many(self, mmodes_list, on_freqs_done=None):
+    def make_alm_many(self, mmodes_list, on_freqs_done=None, alm_internal=False):
         """The a_lm of D days from one pass over B (see :meth:`process_many`): a list of device arrays
-        ``[nfreq, npol, mmax+1, lmax+1]``, one per day."""
+        ``[nfreq, npol, mmax+1, lmax+1]``, one per day, with exact zeros at ``l < m`` (``alm_internal``: as
+        ``SolveEngine.solve_many`` -- for :meth:`process_many`, whose a_lm only the inverse SHT reads)."""
         bt = self.beamtransfer
         first = mmodes_list[0]
         mmax = min(bt.telescope.mmax, len(first.index_map["m"]) - 1)
@@ -146,7 +147,7 @@ class BaseMapMaker(ContainerTask):
             mm.redistribute("freq")
             mv.append(_dev_dataset(mm.vis, ctx, np.complex128))
             mw.append(_dev_dataset(mm.weight, ctx, np.float64))
-        return eng.solve_many(self._kind, mv, mw, freq_ind, mmax, on_freqs_done=on_freqs_done, **self._solve_params())
+        return eng.solve_many(self._kind, mv, mw, freq_ind, mmax, on_freqs_done=on_freqs_done, alm_internal=alm_internal, **self._solve_params())
 
     def alm_square(self, alm_d):
         """Device alm -> the reference's square ``[nfreq, 4, lmax+1, lmax+1]`` ndarray (``mapmaker.py:102-109``)."""
@@ -206,6 +207,7 @@ class BaseMapMaker(ContainerTask):
         resident ``DirtyMapMaker`` also shares every tile READ between up to eight days (``dmm_dirty_run_multi``).
         All days must have the same frequencies and m range.  Each day's a_lm equals its single-day ``process`` bit for
         bit.  HBM: every day in the group holds its own a_lm and maps (10.7 GB at cfg 3).
+        The a_lm is internal here (read by the inverse SHT, then dropped): its ``l < m`` entries are undefined, not zero.
         """
         mmodes_list = list(mmodes_list)
         if not mmodes_list:
@@ -242,7 +244,7 @@ class BaseMapMaker(ContainerTask):
                 side.uses(alm, maps[d])  # read / written on the side stream: held until side.sync()
             _alm2map_neighbourly(side, alm[f0:f1], f1 - f0, lmax, n_m - 1, nside, maps[d][f0:f1])
 
-        alms = self.make_alm_many(mmodes_list, on_freqs_done=sht_of)
+        alms = self.make_alm_many(mmodes_list, on_freqs_done=sht_of, alm_internal=True)
         pending = None
         if not maps:  # no frequencies on this rank
             maps = [ctx.empty((alm.shape[0], 4, npix), np.float64) for alm in alms]

@@ -122,6 +122,7 @@ int dmm_ctx_set_option(dmm_ctx* c, const char* name, int64_t value) {
   if (!strcmp(name, "dirty_variant")) c->opt_dirty_variant = (int)value;
   else if (!strcmp(name, "grid_mult")) c->opt_grid_mult = (int)value;
   else if (!strcmp(name, "dirty_static")) c->opt_dirty_static = (int)value;
+  else if (!strcmp(name, "dirty_nofill")) c->opt_dirty_nofill = (int)value;
   else if (!strcmp(name, "project_grid_mult")) c->opt_project_grid_mult = (int)value;
   else if (!strcmp(name, "project_variant")) c->opt_project_variant = (int)value;
   else if (!strcmp(name, "ml_inner_sweeps")) c->opt_ml_inner_sweeps = (int)value;

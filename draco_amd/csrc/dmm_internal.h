@@ -41,6 +41,7 @@ struct dmm_ctx {
   int opt_grid_mult = 0;
   int opt_dirty_prio = 0;                  // 1: k_dirty's waves run at raised issue priority, whatever the days per launch (A/B: beside the side stream's SHT)
   int opt_dirty_static = 0;                // 1: static striding of the dirty kernel's task list (default: dynamic hand-out)
+  int opt_dirty_nofill = 0;                // 1: dmm_dirty_run_multi leaves a_lm[l < m] unwritten (an a_lm consumed by dmm_alm2map alone)
   int opt_project_grid_mult = 0;
   int opt_project_variant = 0;
   int opt_ml_inner_sweeps = 0, opt_ml_outer_sweeps = 0;

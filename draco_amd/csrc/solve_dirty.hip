@@ -41,6 +41,9 @@ struct SolveParams {
   // CU slowed down by a neighbour on another stream simply takes fewer tasks; nullptr = static striding
   unsigned long long* ticket;
   int prio;  // 1: the kernel's waves raise their issue priority (s_setprio 3) over whatever shares their SIMDs
+  // 1: the structural zeros l < m are NOT written -- for an a_lm that never leaves the library (the map-makers' slab loop:
+  // the Legendre synthesis reads l >= m alone); half of the square a_lm's bytes, written beside the stream of B
+  int nofill;
 };
 
 __device__ __forceinline__ int64_t find_tile(const int32_t* __restrict__ ws, int64_t ntile, int64_t w) {
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(kThreads) void k_dirty(SolveParams p, const BT* __r
     __syncthreads();
 
     // structural zeros l < m (mapmaker.py:76 zero fill): written by the first column block
-    if (cb == 0)
+    if (cb == 0 && !p.nofill)
       for (int idx = threadIdx.x; idx < p.npol * g.m; idx += kThreads) {
         const int pol = idx / g.m, l = idx - pol * g.m;
         const int64_t o = g.alm_at(pol, l);
@@ -482,6 +485,7 @@ SolveParams base_params(const dmm_plan* pl) {
   p.Sl = nullptr;
   p.ticket = nullptr;
   p.prio = pl->ctx->opt_dirty_prio;
+  p.nofill = 0;
   return p;
 }
 
@@ -695,7 +699,8 @@ int dmm_dirty_run_multi(dmm_plan* pl, const void* B, const void* const* mvis, co
   }
   if (pl->ntile == 0) return DMM_OK;
   DMM_HIP(hipSetDevice(pl->ctx->device));
-  const SolveParams p = base_params(pl);
+  SolveParams p = base_params(pl);
+  p.nofill = pl->ctx->opt_dirty_nofill != 0;  // (this entry alone: dmm_dirty_run and the back-projections always fill)
   // groups of 8, 4, 2 days per read of B (8 days' w = Ni o v take 8 x 12 KB of LDS at cfg 3), then a last single day
   const size_t w_day = (size_t)2 * pl->npairs * sizeof(double2);  // LDS of one day's w = Ni o v
   const int nd_max = 8 * w_day <= 128 * 1024 ? 8 : (4 * w_day <= 128 * 1024 ? 4 : (2 * w_day <= 128 * 1024 ? 2 : 1));

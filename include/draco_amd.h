@@ -81,6 +81,9 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "regrid_workspace_mib" (0 = 12 GiB: a cfg-3 day in one launch), "grid_mult", "project_grid_mult";
  *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio" (1: the Dirty kernel's waves raise their issue priority;
  *    it applies to dmm_dirty_run and to every group of dmm_dirty_run_multi -- the multi-day launches used to ignore it),
+ *    "dirty_nofill" (1: dmm_dirty_run_multi does not write the structural zeros alm[l < m] -- they stay whatever the memory
+ *    held; for an a_lm that only dmm_alm2map reads, which loads l >= m alone: same maps, half the a_lm bytes written; every
+ *    other entry always writes them),
  *    "project_variant", "ringmap_variant" (1 three-kernel
  *    form, 2 eight elevations per block), "sht_variant" (bits: 0-1 vector-ALU synthesis form, 2 direct ring sums,
  *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x in the analysis, 6 first MFMA synthesis form,
@@ -239,7 +242,8 @@ int dmm_dirty_run(dmm_plan* plan, const void* B, const void* mvis, const double*
  * (mapmaker.py:79-94) is run once per pipeline item (doc/tutorial.rst:110-120) against the same beam transfers; here
  * up to 8 days share every tile read (4 ND f64 FMAs per 16 bytes of B instead of 4).  mvis / mweight / alm: [host]
  * arrays of `nday` device pointers, each as in dmm_dirty_run; the alm arrays must be distinct.  Every day's result is
- * bit-identical to dmm_dirty_run's on that day (same accumulation order). */
+ * bit-identical to dmm_dirty_run's on that day (same accumulation order).  With the context option "dirty_nofill" = 1
+ * the entries l < m of every alm are left unwritten instead of zeroed. */
 int dmm_dirty_run_multi(dmm_plan* plan, const void* B, const void* const* mvis, const double* const* mweight,
                         void* const* alm, int nday);
 
