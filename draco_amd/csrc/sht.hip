@@ -236,14 +236,31 @@ size_t ring_synth_lds(const ShtGeom& g, const ClassLaunch& c, int nb, bool stage
   return lds <= 160 * 1024 ? lds : 0;
 }
 
-template <typename K>
-int launch_ring(K kern, dim3 grid, int threads, size_t lds, hipStream_t st, const RingParams& rp, const RingClass& rc) {
+using RingKernel = void (*)(RingParams, RingClass);
+
+int launch_ring(RingKernel kern, dim3 grid, int threads, size_t lds, hipStream_t st, const RingParams& rp, const RingClass& rc) {
   if (lds > 160 * 1024) return dmm_set_error(DMM_E_UNSUPPORTED, "SHT ring stage needs %zu bytes of LDS (nside too large)", lds);
   DMM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, rp, rc);
   DMM_HIP(hipGetLastError());
   return DMM_OK;
 }
+
+RingParams ring_params(const ShtGeom& g, int nf, int npol, double2* b, double* map, const double* map_ref) {
+  RingParams rp;
+  rp.g = g;
+  rp.nf = nf;
+  rp.npol = npol;
+  rp.b = b;
+  rp.map = map;
+  rp.map_ref = map_ref;
+  rp.npix = 12LL * g.nside * g.nside;
+  rp.stage_all = 0;
+  return rp;
+}
+
+// f<NPOL>(...) for the two supported polarisation counts
+#define DMM_BY_NPOL(npol, f, ...) ((npol) == 4 ? f<4>(__VA_ARGS__) : f<1>(__VA_ARGS__))
 
 template <int NPOL>
 int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int nf, double2* b, double* map) {
@@ -257,13 +274,6 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
   if (NPOL == 4 && !(ctx->opt_sht_variant & 8)) {  // bit 3: force the vector-ALU kernel
     const int npair = (g.nring + 1) / 2;
     const int nrc = (npair + kThreads - 1) / kThreads;
-#ifdef LEG_STAMPS  // diagnostic build (-DLEG_STAMPS): every wave of the synthesis kernel leaves its phase clocks
-    static unsigned long long* stamps_d = nullptr;
-    const size_t nst = (size_t)(g.mmax + 1) * nrc * ((nf + 2 * kLegF - 1) / (2 * kLegF)) * 4 * 8;
-    if (!stamps_d) (void)hipMalloc((void**)&stamps_d, 64 << 20);
-    (void)hipMemsetAsync(stamps_d, 0, nst * 8, ctx->stream);
-    lp.stamps = stamps_d;
-#endif
     const int nx = g.mmax + 1;
     // the pipelined kernel addresses a block's a_lm columns with 32-bit byte offsets from one base: its frequency groups must
     // span less than 4 GiB (8 frequencies: lmax <= 2895; 4: lmax <= 4095) -- beyond that the first form, with 64-bit pointers
@@ -279,28 +289,20 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
       const int nz = (nf + 2 * kLegF - 1) / (2 * kLegF);
       hipLaunchKernelGGL(k_leg_synth_mfma2<2>, dim3(nx, nrc, nz), dim3(kThreads), 0, ctx->stream, lp);
     }
-  } else
-  switch (ctx->opt_sht_variant & 3) {
-    case 1: hipLaunchKernelGGL((k_leg_synth<NPOL, 1, 1>), dim3(g.mmax + 1, nf), dim3(kThreads), 0, ctx->stream, lp); break;
-    case 2: hipLaunchKernelGGL((k_leg_synth<NPOL, 2, 1>), dim3(g.mmax + 1, nf), dim3(kThreads), 0, ctx->stream, lp); break;
-    case 3: hipLaunchKernelGGL((k_leg_synth<NPOL, 1, 6>), dim3(g.mmax + 1, nf), dim3(kThreads), 0, ctx->stream, lp); break;
-    default: hipLaunchKernelGGL((k_leg_synth<NPOL, 2, 4>), dim3(g.mmax + 1, nf), dim3(kThreads), 0, ctx->stream, lp); break;
+  } else {
+    hipLaunchKernelGGL(k_leg_synth<NPOL>, dim3(g.mmax + 1, nf), dim3(kThreads), 0, ctx->stream, lp);
   }
   DMM_HIP(hipGetLastError());
-  RingParams rp;
-  rp.g = g;
-  rp.nf = nf;
-  rp.npol = NPOL;
-  rp.b = b;
-  rp.map = map;
-  rp.map_ref = nullptr;
-  rp.radix8 = (ctx->opt_sht_variant & 2048) ? 0 : 1;  // bit 11: the radix-4 passes of rounds 1-4 (A/B)
-  rp.npix = 12LL * g.nside * g.nside;
-  rp.stage_all = 0;
+  RingParams rp = ring_params(g, nf, NPOL, b, map, nullptr);
   // NPOL = 4: a block per (ring, frequency group, transform (T,Q) | (U,V)); NPOL = 1: per (ring, frequency)
   constexpr int KF = NPOL == 4 ? kSynF : 1;
   const dim3 per_ring((nf + KF - 1) / KF, NPOL == 4 ? 2 : 1);
   const int force_direct = ctx->opt_sht_variant & 4;
+  // k_ring_synth_fft by [log2 of the transforms per pass][Bluestein]
+  constexpr int N2 = NPOL == 4 ? 2 : 1, N4 = NPOL == 4 ? 4 : 1;
+  static const RingKernel fft_kernel[3][2] = {{k_ring_synth_fft<NPOL, 1, false>, k_ring_synth_fft<NPOL, 1, true>},
+                                              {k_ring_synth_fft<NPOL, N2, false>, k_ring_synth_fft<NPOL, N2, true>},
+                                              {k_ring_synth_fft<NPOL, N4, false>, k_ring_synth_fft<NPOL, N4, true>}};
   for (const ClassLaunch& c : ring_classes(g)) {
     // transforms per pass: the most with which two blocks still fit a CU's LDS (a larger block waits for the CUs that the
     // solve kernel beside it leaves: 30 x longer in the day), with every ring staged (coalesced loads) if that fits,
@@ -313,20 +315,10 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
         const size_t l = ring_synth_lds(g, c, b, tier == 0, force_direct);
         if (l != 0 && l <= (tier < 2 ? (size_t)80 * 1024 : (size_t)160 * 1024)) nb = b, lds = l, rp.stage_all = tier == 0;
       }
-    const dim3 grid(c.nblock, per_ring.x, per_ring.y);
-    int rc;
-    if (nb == 0) {
-      rc = launch_ring(k_ring_synth<NPOL>, dim3(c.nblock, nf), kThreads, (size_t)NPOL * (g.mmax + 1) * sizeof(double2), ctx->stream, rp, c.rc);
-    } else if (nb == 4) {
-      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 4 : 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 4 : 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
-    } else if (nb == 2) {
-      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 2 : 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_synth_fft<NPOL, NPOL == 4 ? 2 : 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
-    } else {
-      rc = c.blue ? launch_ring(k_ring_synth_fft<NPOL, 1, true>, grid, kFftThreads, lds, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_synth_fft<NPOL, 1, false>, grid, kFftThreads, lds, ctx->stream, rp, c.rc);
-    }
+    const int rc = nb == 0 ? launch_ring(k_ring_synth<NPOL>, dim3(c.nblock, nf), kThreads, (size_t)NPOL * (g.mmax + 1) * sizeof(double2),
+                                         ctx->stream, rp, c.rc)
+                           : launch_ring(fft_kernel[nb >> 1][c.blue], dim3(c.nblock, per_ring.x, per_ring.y), kFftThreads, lds,
+                                         ctx->stream, rp, c.rc);
     if (rc) return rc;
   }
   return DMM_OK;
@@ -335,30 +327,19 @@ int synth_chunk(dmm_ctx* ctx, const ShtGeom& g, const double2* alm, int n_m, int
 template <int NPOL>
 int anal_chunk(dmm_ctx* ctx, const ShtGeom& g, const double* map, int n_m, int nf, double2* b, double2* alm, int accumulate,
                const double* map_ref = nullptr) {
-  RingParams rp;
-  rp.g = g;
-  rp.nf = nf;
-  rp.npol = NPOL;
-  rp.b = b;
-  rp.map = const_cast<double*>(map);
-  rp.map_ref = map_ref;
-  rp.radix8 = (ctx->opt_sht_variant & 2048) ? 0 : 1;  // bit 11: the radix-4 passes of rounds 1-4 (A/B)
-  rp.npix = 12LL * g.nside * g.nside;
-  rp.stage_all = 0;
+  const RingParams rp = ring_params(g, nf, NPOL, b, const_cast<double*>(map), map_ref);
   constexpr int NROWS = NPOL == 4 ? 2 : 1;
   const int force_direct = ctx->opt_sht_variant & 4;
+  // k_ring_anal_fft by [both transforms of a frequency in one block][Bluestein]
+  static const RingKernel fft_kernel[2][2] = {{k_ring_anal_fft<NPOL, 1, false>, k_ring_anal_fft<NPOL, 1, true>},
+                                              {k_ring_anal_fft<NPOL, NROWS, false>, k_ring_anal_fft<NPOL, NROWS, true>}};
   for (const ClassLaunch& c : ring_classes(g)) {
     const size_t lds2 = ring_fft_lds(g, c, NROWS, force_direct), lds1 = ring_fft_lds(g, c, 1, force_direct);
-    int rc;
-    if (lds1 == 0) {
-      rc = launch_ring(k_ring_anal<NPOL>, dim3(c.nblock, nf), kThreads, (size_t)NPOL * c.nphi_max * sizeof(double), ctx->stream, rp, c.rc);
-    } else if (NROWS == 2 && lds2 != 0 && lds2 <= 80 * 1024) {
-      rc = c.blue ? launch_ring(k_ring_anal_fft<NPOL, NROWS, true>, dim3(c.nblock, nf), kFftThreads, lds2, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_anal_fft<NPOL, NROWS, false>, dim3(c.nblock, nf), kFftThreads, lds2, ctx->stream, rp, c.rc);
-    } else {
-      rc = c.blue ? launch_ring(k_ring_anal_fft<NPOL, 1, true>, dim3(c.nblock, nf, NROWS), kFftThreads, lds1, ctx->stream, rp, c.rc)
-                  : launch_ring(k_ring_anal_fft<NPOL, 1, false>, dim3(c.nblock, nf, NROWS), kFftThreads, lds1, ctx->stream, rp, c.rc);
-    }
+    const bool both = NROWS == 2 && lds2 != 0 && lds2 <= 80 * 1024;
+    const int rc = lds1 == 0 ? launch_ring(k_ring_anal<NPOL>, dim3(c.nblock, nf), kThreads, (size_t)NPOL * c.nphi_max * sizeof(double),
+                                           ctx->stream, rp, c.rc)
+                             : launch_ring(fft_kernel[both][c.blue], dim3(c.nblock, nf, both ? 1 : NROWS), kFftThreads,
+                                           both ? lds2 : lds1, ctx->stream, rp, c.rc);
     if (rc) return rc;
   }
   LegAnalParams lp;
@@ -369,14 +350,8 @@ int anal_chunk(dmm_ctx* ctx, const ShtGeom& g, const double* map, int n_m, int n
   lp.b = b;
   lp.alm = alm;
   lp.accumulate = accumulate;
-  lp.m_identity = (ctx->opt_sht_variant & 32) ? 1 : 0;
   if (NPOL == 4 && !(ctx->opt_sht_variant & 8)) {  // bit 3: force the vector-ALU kernels
-    // 4-wave blocks, two per CU, the ring pairs in passes of 256 (default since round 4: map2alm 0.116 -> 0.110 ms per
-    // frequency at cfg 3, -4.4 % with three iterations); bit 4 of sht_variant: the 8-wave block of rounds 1-3 (A/B)
-    if (ctx->opt_sht_variant & 16)
-      hipLaunchKernelGGL((k_leg_anal_mfma<kAnThreads, 1>), dim3(g.mmax + 1, (nf + kLegF - 1) / kLegF), dim3(kAnThreads), 0, ctx->stream, lp);
-    else
-      hipLaunchKernelGGL((k_leg_anal_mfma<256, 1>), dim3(g.mmax + 1, (nf + kLegF - 1) / kLegF), dim3(256), 0, ctx->stream, lp);
+    hipLaunchKernelGGL(k_leg_anal_mfma, dim3(g.mmax + 1, (nf + kLegF - 1) / kLegF), dim3(kThreads), 0, ctx->stream, lp);
     DMM_HIP(hipGetLastError());
     return DMM_OK;
   }
@@ -409,7 +384,7 @@ int dmm_alm2map(dmm_ctx* ctx, const void* alm, int nfreq, int npol, int lmax, in
     const int nf = (int)((size_t)(nfreq - f0) < nfc ? (size_t)(nfreq - f0) : nfc);
     const double2* a = (const double2*)alm + (int64_t)f0 * npol * n_m * (lmax + 1);
     double* mp = map + (int64_t)f0 * npol * npix;
-    rc = npol == 4 ? synth_chunk<4>(ctx, g, a, n_m, nf, (double2*)scratch, mp) : synth_chunk<1>(ctx, g, a, n_m, nf, (double2*)scratch, mp);
+    rc = DMM_BY_NPOL(npol, synth_chunk, ctx, g, a, n_m, nf, (double2*)scratch, mp);
     if (rc) return rc;
   }
   return DMM_OK;
@@ -440,13 +415,13 @@ int dmm_map2alm(dmm_ctx* ctx, const double* map, int nfreq, int npol, int lmax, 
     const int nf = (int)((size_t)(nfreq - f0) < nfc ? (size_t)(nfreq - f0) : nfc);
     double2* a = (double2*)alm + (int64_t)f0 * npol * n_m * (lmax + 1);
     const double* mp = map + (int64_t)f0 * npol * npix;
-    rc = npol == 4 ? anal_chunk<4>(ctx, g, mp, n_m, nf, b, a, 0) : anal_chunk<1>(ctx, g, mp, n_m, nf, b, a, 0);
+    rc = DMM_BY_NPOL(npol, anal_chunk, ctx, g, mp, n_m, nf, b, a, 0);
     if (rc) return rc;
     for (int it = 0; it < niter; ++it) {  // a += A(map - S a)
-      rc = npol == 4 ? synth_chunk<4>(ctx, g, a, n_m, nf, b, resid) : synth_chunk<1>(ctx, g, a, n_m, nf, b, resid);
+      rc = DMM_BY_NPOL(npol, synth_chunk, ctx, g, a, n_m, nf, b, resid);
       if (rc) return rc;
       // the residual map - S a is formed by the ring analysis as it reads (one pass over the maps less than a k_sub launch)
-      rc = npol == 4 ? anal_chunk<4>(ctx, g, resid, n_m, nf, b, a, 1, mp) : anal_chunk<1>(ctx, g, resid, n_m, nf, b, a, 1, mp);
+      rc = DMM_BY_NPOL(npol, anal_chunk, ctx, g, resid, n_m, nf, b, a, 1, mp);
       if (rc) return rc;
     }
   }

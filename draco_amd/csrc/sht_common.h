@@ -64,9 +64,6 @@ struct LegParams {
   int n_m;                // m-stride of alm (= mmax+1 of the alm buffer)
   const double2* alm;     // [nf, npol, n_m, lmax+1]
   double2* b;             // NPOL = 4: frequency-grouped (syn4_at); NPOL = 1: [nf, nring, mmax+1]
-#ifdef LEG_STAMPS
-  unsigned long long* stamps;  // diagnostic build only
-#endif
 };
 
 // LDS image of one (f, m): coefficient rows + npol a_lm columns

@@ -5,12 +5,88 @@
 
 namespace {
 
+// ---------------------------------------------------------------- pieces every Legendre kernel shares
+typedef double v4d __attribute__((ext_vector_type(4)));  // accumulator tile of v_mfma_f64_16x16x4_f64
+
+// generation state of one north/south ring pair at one m
+struct LegRing {
+  double x, inv_s2, xs2, lam, lam_prev;
+  int nsc;  // pending 2^-800 blocks; < 0: ring takes no part (skipped, or r beyond the last pair)
+};
+
+__device__ __forceinline__ LegRing leg_ring_start(const ShtGeom& g, int m, int r, int npair) {
+  LegRing R = {0.0, 0.0, 0.0, 0.0, 0.0, -1};
+  if (r < npair) {
+    const double sth = g.sth[r];
+    R.x = g.z[r];
+    R.inv_s2 = 1.0 / (sth * sth);
+    R.xs2 = R.x * R.inv_s2;
+    if (!ring_skips_m(m, g.lmax, sth)) lam_start(g.lfac[m], m, sth, R.lam, R.nsc);
+  }
+  return R;
+}
+
+// lam_l = x lam_{l-1} ra - lam_{l-2} rb
+__device__ __forceinline__ void leg_advance(LegRing& R, double ra, double rb) {
+  const double nxt = R.x * R.lam * ra - R.lam_prev * rb;
+  R.lam_prev = R.lam;
+  R.lam = nxt;
+}
+
+// One step of a ring that takes part (nsc >= 0), handing back a 2^-800 block once the value has grown by one.
+// RARE marks the rescale as the exception, which keeps it a branch: the MFMA kernels' form (turned into selects, its two
+// f64 multiplies run at every step on the pipe the MFMAs need).  The vector-ALU kernels keep the select form the compiler
+// gives them unprompted (as a branch it costs k_leg_synth<4> another 108 bytes of scratch).
+template <bool RARE = false>
+__device__ __forceinline__ void leg_step(LegRing& R, double ra, double rb) {
+  leg_advance(R, ra, rb);
+  const bool big = R.nsc > 0 && fabs(R.lam) > kBig;
+  if (RARE ? __builtin_expect(big, 0) : big) {
+    R.lam *= kSmallStep;
+    R.lam_prev *= kSmallStep;
+    --R.nsc;
+  }
+}
+
+// spin-2 factors of (l, ring) from lam = lambda_l and lam_prev = lambda_{l-1} (l < 2: c1..c4 are zero, F1 = F2 = 0)
+__device__ __forceinline__ void leg_spin2(const Coef& q, double inv_s2, double xs2, double lam, double lam_prev, double& F1,
+                                          double& F2) {
+  F1 = fma(q.cd * xs2, lam_prev, -fma(q.c1, inv_s2, q.c2) * lam);
+  F2 = fma(q.c4 * inv_s2, lam_prev, -q.c3 * xs2 * lam);
+}
+
+__device__ __forceinline__ double bcast_lane(double v, int src) {  // lane src's v as a scalar: two v_readlane
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+  return __hiloint2double(hi, lo);
+}
+
+// Column (lane & 15) of the MFMA B operands and D tiles, in all three MFMA kernels: frequency fi of the block's group and
+// real c of  (T.x, T.y, V.x, V.y) beside lambda,  (E.x, E.y, B.x, B.y) beside F1,  (B.y, -B.x, -E.y, E.x) beside F2
+// (the analysis: Q, U for E, B).  As (polarisation, re | im): polTV, pol1 and pol2 with comp, comp ^ 1; f2neg: the minus.
+struct LegCol {
+  int fi, c, comp, polTV, pol1, pol2;
+  bool f2neg;
+};
+__device__ __forceinline__ LegCol leg_col(int lane) {
+  LegCol k;
+  k.fi = (lane & 15) >> 2;
+  k.c = lane & 3;
+  k.comp = k.c & 1;
+  k.polTV = k.c < 2 ? 0 : 3;
+  k.pol1 = k.c < 2 ? 1 : 2;
+  k.pol2 = k.c < 2 ? 2 : 1;
+  k.f2neg = k.c == 1 || k.c == 2;
+  return k;
+}
+
 // ---------------------------------------------------------------- synthesis, stage 1
 // block -> m = blockIdx.x.  The NPOL = 4 forms write whole 128-byte lines of the frequency-grouped scratch (sht_common.h)
 // and share no line between m, so they need no XCD-aware map of blocks to m (the analysis keeps one, leg_m_of_block below;
 // on the headline day the synthesis with and without it: 247.1 / 247.9 against 247.3 / 247.0 ms per day).
-template <int NPOL, int NR, int MINW>
-__global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
+template <int NPOL>
+__global__ __launch_bounds__(kThreads, 4) void k_leg_synth(LegParams p) {
+  constexpr int NR = 2;  // ring pairs per thread
   const int m = blockIdx.x, f = blockIdx.y;
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const kptr coef = (kptr)p.g.coef + 8 * coef_row0(m, lmax);   // [nl][8]
@@ -20,62 +96,41 @@ __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
     a[q] = (kptr)(p.alm + (((int64_t)f * NPOL + q) * p.n_m + m) * (lmax + 1) + m);
 
   const int nring = p.g.nring, npair = (nring + 1) / 2;  // north rings incl. equator
-  const double lfac_m = p.g.lfac[m];
   const int64_t mstride = p.g.mmax + 1;
   // accumulators: [sym, anti] for I, V (and Q, U); lambda-parity terms go to (T, V, Q1, U1),
   // opposite-parity (F2) terms to (Q2, U2): the pairing is static per parity (no selects)
-  struct Ring {
-    double x, inv_s2, xs2, lam, lam_prev;
-    int nsc;  // pending 2^-800 blocks; < 0: ring takes no part
+  struct Sums {
     double2 Ts, Ta, Vs, Va, Qs, Qa, Us, Ua;
   };
   // each thread advances NR ring pairs (r, r + kThreads, ...: polar and equatorial mixed) together:
   // independent recurrences interleave and every LDS operand serves both
   for (int r0 = 0; r0 < npair; r0 += NR * kThreads) {
-    Ring R[NR];
+    LegRing R[NR];
+    Sums S[NR];
 #pragma unroll
     for (int t = 0; t < NR; ++t) {
-      const int r = r0 + t * kThreads + threadIdx.x;
-      const bool live = r < npair;
-      const int rr = live ? r : 0;
-      const double x = p.g.z[rr], sth = p.g.sth[rr];
-      R[t].x = x;
-      R[t].inv_s2 = 1.0 / (sth * sth);
-      R[t].xs2 = x * R[t].inv_s2;
-      R[t].lam = R[t].lam_prev = 0.0;
-      R[t].nsc = -1;
-      if (live && !ring_skips_m(m, lmax, sth)) lam_start(lfac_m, m, sth, R[t].lam, R[t].nsc);
+      R[t] = leg_ring_start(p.g, m, r0 + t * kThreads + threadIdx.x, npair);
       const double2 z2 = {0.0, 0.0};
-      R[t].Ts = R[t].Ta = R[t].Vs = R[t].Va = R[t].Qs = R[t].Qa = R[t].Us = R[t].Ua = z2;
+      S[t].Ts = S[t].Ta = S[t].Vs = S[t].Va = S[t].Qs = S[t].Qa = S[t].Us = S[t].Ua = z2;
     }
-    auto step = [&](Ring& g, const Coef& q, const double2& aT, const double2& aE, const double2& aB, const double2& aV,
+    auto step = [&](LegRing& g, Sums& s, const Coef& q, const double2& aT, const double2& aE, const double2& aB, const double2& aV,
                     bool first, bool even) {
       if (g.nsc < 0) return;
-      if (!first) {
-        const double nxt = g.x * g.lam * q.ra - g.lam_prev * q.rb;
-        g.lam_prev = g.lam;
-        g.lam = nxt;
-        if (g.nsc > 0 && fabs(g.lam) > kBig) {
-          g.lam *= kSmallStep;
-          g.lam_prev *= kSmallStep;
-          --g.nsc;
-        }
-      }
+      if (!first) leg_step(g, q.ra, q.rb);
       if (g.nsc == 0) {
-        double2& T = even ? g.Ts : g.Ta;
-        double2& V = even ? g.Vs : g.Va;
-        double2& Q1 = even ? g.Qs : g.Qa;
-        double2& Q2 = even ? g.Qa : g.Qs;
-        double2& U1 = even ? g.Us : g.Ua;
-        double2& U2 = even ? g.Ua : g.Us;
+        double2& T = even ? s.Ts : s.Ta;
+        double2& V = even ? s.Vs : s.Va;
+        double2& Q1 = even ? s.Qs : s.Qa;
+        double2& Q2 = even ? s.Qa : s.Qs;
+        double2& U1 = even ? s.Us : s.Ua;
+        double2& U2 = even ? s.Ua : s.Us;
         T.x = fma(aT.x, g.lam, T.x);
         T.y = fma(aT.y, g.lam, T.y);
         if (NPOL == 4) {
           V.x = fma(aV.x, g.lam, V.x);
           V.y = fma(aV.y, g.lam, V.y);
-          // l < 2: c1..c4 are zero, F1 = F2 = 0
-          const double F1 = fma(q.cd * g.xs2, g.lam_prev, -fma(q.c1, g.inv_s2, q.c2) * g.lam);
-          const double F2 = fma(q.c4 * g.inv_s2, g.lam_prev, -q.c3 * g.xs2 * g.lam);
+          double F1, F2;
+          leg_spin2(q, g.inv_s2, g.xs2, g.lam, g.lam_prev, F1, F2);
           Q1.x = fma(-aE.x, F1, Q1.x);   // Q: -(E F1 + i B F2)
           Q1.y = fma(-aE.y, F1, Q1.y);
           Q2.x = fma(aB.y, F2, Q2.x);    // -i*B*F2 = (B.y, -B.x) * F2
@@ -114,18 +169,18 @@ __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
     for (int k = 0; k < nl; k += 2) {
       Ops nxt = fetch(k + 1);
 #pragma unroll
-      for (int t = 0; t < NR; ++t) step(R[t], cur.q, cur.aT, cur.aE, cur.aB, cur.aV, k == 0, true);
+      for (int t = 0; t < NR; ++t) step(R[t], S[t], cur.q, cur.aT, cur.aE, cur.aB, cur.aV, k == 0, true);
       if (k + 1 >= nl) break;
       cur = fetch(k + 2);
 #pragma unroll
-      for (int t = 0; t < NR; ++t) step(R[t], nxt.q, nxt.aT, nxt.aE, nxt.aB, nxt.aV, false, false);
+      for (int t = 0; t < NR; ++t) step(R[t], S[t], nxt.q, nxt.aT, nxt.aE, nxt.aB, nxt.aV, false, false);
     }
 #pragma unroll
     for (int t = 0; t < NR; ++t) {
       const int r = r0 + t * kThreads + threadIdx.x;
       if (r >= npair) continue;
       const int rs = nring - 1 - r;  // southern mirror (== r on the equator)
-      const Ring& g = R[t];
+      const Sums& g = S[t];
       auto val = [&](double2 s, double2 an, double sgn) { return make_double2(s.x + sgn * an.x, s.y + sgn * an.y); };
       if (NPOL == 1) {
         p.b[((int64_t)f * nring + r) * mstride + m] = val(g.Ts, g.Ta, 1.0);
@@ -165,42 +220,53 @@ __global__ __launch_bounds__(kThreads, MINW) void k_leg_synth(LegParams p) {
 constexpr int kLegL = 8, kLegF = 4, kLegPitch = 72;
 static_assert(kLegF == kSynF, "a frequency group of the MFMA columns is one group of the synthesis scratch");
 
-// (the kernels' bodies take their block coordinates as arguments: one block per (m, ring chunk, frequency group))
-__device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, int by, int bz) {
-  typedef double v4d __attribute__((ext_vector_type(4)));
+// The tiles of one frequency of both MFMA synthesis forms -> ring coefficients: north = sym + anti, south = sym - anti;
+// D rows = rings (kq + 4 reg of the 16 from tile0(t)), D columns = this lane's column.  The lane's (T | V) and (Q | U)
+// values of one ring are slots 0 and 1 of component c & 1 of transform c >> 1 in the frequency-grouped scratch: one
+// 16-byte store, and the 64 lanes of a wave cover eight whole 128-byte lines.
+template <class TileRing>
+__device__ __forceinline__ void leg_store_syn4(const LegParams& p, int f, int m, const LegCol& col, int kq, const v4d (&acc)[4][4],
+                                               TileRing tile0) {
+  const int nring = p.g.nring, npair = (nring + 1) / 2, nm = p.g.mmax + 1;
+  double* bout = reinterpret_cast<double*>(p.b) + 2 * col.comp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int rr = tile0(t) + kq + 4 * reg;
+      if (rr >= npair) continue;
+      const int rs = nring - 1 - rr;
+      const double tv = acc[t][0][reg], tva = acc[t][1][reg], qu = acc[t][2][reg], qua = acc[t][3][reg];
+      *reinterpret_cast<double2*>(bout + syn4_at(f, m, rr, col.c >> 1, nring, nm)) = make_double2(tv + tva, qu + qua);
+      if (rs != rr) *reinterpret_cast<double2*>(bout + syn4_at(f, m, rs, col.c >> 1, nring, nm)) = make_double2(tv - tva, qu - qua);
+    }
+}
+
+// one block per (m, ring chunk, frequency group)
+__global__ __launch_bounds__(kThreads, 2) void k_leg_synth_mfma(LegParams p) {
   __shared__ double slab[kThreads / 64][3][kLegL][kLegPitch];
-  const int m = bx, rc = by, f0 = bz * kLegF;
+  const int m = blockIdx.x, rc = blockIdx.y, f0 = blockIdx.z * kLegF;
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nring = p.g.nring, npair = (nring + 1) / 2;
-  const int64_t mstride = p.g.mmax + 1;
   double(*sl)[kLegL][kLegPitch] = slab[wave];
 
   // generation state of this thread's ring pair
-  const int r = rc * kThreads + threadIdx.x;
-  double x = 0.0, inv_s2 = 0.0, xs2 = 0.0, lam = 0.0, lam_prev = 0.0;
-  int nsc = -1;
-  if (r < npair) {
-    const double sth = p.g.sth[r];
-    x = p.g.z[r];
-    inv_s2 = 1.0 / (sth * sth);
-    xs2 = x * inv_s2;
-    if (!ring_skips_m(m, lmax, sth)) lam_start(p.g.lfac[m], m, sth, lam, nsc);
-  }
-  const bool wave_live = __any(nsc >= 0);
+  LegRing R = leg_ring_start(p.g, m, rc * kThreads + threadIdx.x, (p.g.nring + 1) / 2);
+  const bool wave_live = __any(R.nsc >= 0);
 
   // MFMA operand coordinates of this lane
   const int li = lane & 15, kq = lane >> 4;
-  const int col = li, fi = col >> 2, c = col & 3, f = f0 + fi;
+  const LegCol col = leg_col(lane);
+  const int f = f0 + col.fi;
   const bool fok = f < p.nf;
   // B columns as (pointer to the real array of one a_lm column, sign)
   auto colptr = [&](int pol, int comp) {
     return reinterpret_cast<const double*>(p.alm + (((int64_t)(fok ? f : 0) * 4 + pol) * p.n_m + m) * (lmax + 1) + m) + comp;
   };
-  const double* pTV = colptr(c < 2 ? 0 : 3, c & 1);
-  const double* p1 = colptr(c < 2 ? 1 : 2, c & 1);
-  const double* p2 = colptr(c < 2 ? 2 : 1, (c & 1) ^ 1);
-  const double s2 = (c == 0 || c == 3) ? 1.0 : -1.0;
+  const double* pTV = colptr(col.polTV, col.comp);
+  const double* p1 = colptr(col.pol1, col.comp);
+  const double* p2 = colptr(col.pol2, col.comp ^ 1);
+  const double s2 = col.f2neg ? -1.0 : 1.0;
 
   v4d acc[4][4];  // [ring tile][TV sym, TV anti, QU sym, QU anti]
 #pragma unroll
@@ -216,11 +282,6 @@ __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, 
     auto fetch_rows = [&](int c0) {
       const int row = c0 + (lane >> 3);
       return cgv[8 * (int64_t)(row < nl ? row : nl - 1) + (lane & 7)];
-    };
-    auto bcast = [&](double v, int src) {
-      const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-      const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-      return __hiloint2double(hi, lo);
     };
     double cv = fetch_rows(0);
     for (int c0 = 0; c0 < nl; c0 += kLegL) {
@@ -241,29 +302,19 @@ __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, 
       for (int kk = 0; kk < kLegL; ++kk) {
         const int k = c0 + kk;
         Coef q;
-        q.ra = bcast(cv, 8 * kk + 0);
-        q.rb = bcast(cv, 8 * kk + 1);
-        q.c1 = bcast(cv, 8 * kk + 2);
-        q.c2 = bcast(cv, 8 * kk + 3);
-        q.cd = bcast(cv, 8 * kk + 4);
-        q.c3 = bcast(cv, 8 * kk + 5);
-        q.c4 = bcast(cv, 8 * kk + 6);
+        q.ra = bcast_lane(cv, 8 * kk + 0);
+        q.rb = bcast_lane(cv, 8 * kk + 1);
+        q.c1 = bcast_lane(cv, 8 * kk + 2);
+        q.c2 = bcast_lane(cv, 8 * kk + 3);
+        q.cd = bcast_lane(cv, 8 * kk + 4);
+        q.c3 = bcast_lane(cv, 8 * kk + 5);
+        q.c4 = bcast_lane(cv, 8 * kk + 6);
         double le = 0.0, F1 = 0.0, F2 = 0.0;
         if (k < nl) {
-          if (k > 0 && nsc >= 0) {
-            const double nxt = x * lam * q.ra - lam_prev * q.rb;
-            lam_prev = lam;
-            lam = nxt;
-            if (nsc > 0 && fabs(lam) > kBig) {
-              lam *= kSmallStep;
-              lam_prev *= kSmallStep;
-              --nsc;
-            }
-          }
-          if (nsc == 0) {
-            le = lam;
-            F1 = fma(q.cd * xs2, lam_prev, -fma(q.c1, inv_s2, q.c2) * lam);
-            F2 = fma(q.c4 * inv_s2, lam_prev, -q.c3 * xs2 * lam);
+          if (k > 0 && R.nsc >= 0) leg_step<true>(R, q.ra, q.rb);
+          if (R.nsc == 0) {
+            le = R.lam;
+            leg_spin2(q, R.inv_s2, R.xs2, R.lam, R.lam_prev, F1, F2);
           }
         }
         sl[0][kk][lane] = le;
@@ -290,29 +341,11 @@ __device__ __forceinline__ void leg_synth_mfma_body(const LegParams& p, int bx, 
       }
     }
   }
-  // ring coefficients: north = sym + anti, south = sym - anti; D rows = rings (kq + 4 reg), D columns = this lane's column.
-  // The lane's (T | V) and (Q | U) values of one ring are slots 0 and 1 of component c & 1 of transform c >> 1 in the
-  // frequency-grouped scratch: one 16-byte store, and the 64 lanes of a wave cover eight whole 128-byte lines.
-  if (!fok) return;
-  double* bout = reinterpret_cast<double*>(p.b) + 2 * (c & 1);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int rr = rc * kThreads + wave * 64 + 16 * t + kq + 4 * reg;
-      if (rr >= npair) continue;
-      const int rs = nring - 1 - rr;
-      const double tv = acc[t][0][reg], tva = acc[t][1][reg], qu = acc[t][2][reg], qua = acc[t][3][reg];
-      *reinterpret_cast<double2*>(bout + syn4_at(f, m, rr, c >> 1, nring, (int)mstride)) = make_double2(tv + tva, qu + qua);
-      if (rs != rr) *reinterpret_cast<double2*>(bout + syn4_at(f, m, rs, c >> 1, nring, (int)mstride)) = make_double2(tv - tva, qu - qua);
-    }
+  if (fok) leg_store_syn4(p, f, m, col, kq, acc, [&](int t) { return rc * kThreads + wave * 64 + 16 * t; });
 }
 
-__global__ __launch_bounds__(kThreads, 2) void k_leg_synth_mfma(LegParams p) { leg_synth_mfma_body(p, blockIdx.x, blockIdx.y, blockIdx.z); }
-
-
 // ---- synthesis on the matrix cores, second form (round 5; default, `sht_variant` bit 6 restores the one above).
-// What the counters and in-kernel stamps of the first form say (profiles/r01_sht_cfg3_pmc.txt, profiles/r05_sht_*): 17 vector
+// What the counters and in-kernel clocks of the first form said (profiles/r01_sht_cfg3_pmc.txt, profiles/r05_sht_*): 17 vector
 // instructions per MFMA, the matrix pipe busy 0.30 of the kernel -- and on this part an f64 VALU operation runs on the SAME
 // double-precision pipe as the f64 MFMA (profiles/r01_mfma_f64_probe.txt: 4 cycles each, never hidden, with one wave or four
 // per SIMD), so every f64 operation of the recurrence is matrix-pipe time, everything else is issue slots, and a second
@@ -335,60 +368,34 @@ __global__ __launch_bounds__(kThreads, 2) void k_leg_synth_mfma(LegParams p) { l
 // Same products, same summation order per accumulator as the first form; lambda_{l-1} of the step at which a ring's scale
 // reaches 1 is read as 0 (it is < 2^-60 of the ring's values there), as the analysis kernel has always done.
 constexpr int kLeg2Rows = kLegL + 1;  // row 0: lambda of the step before the chunk
-#ifndef PIPE_HINT
-#define PIPE_HINT 1
-#endif
 
+// NFG frequency groups per block: 2 (default), or 1 with two waves per SIMD (`sht_variant` bit 7, and wherever 8 frequencies
+// of a_lm span 4 GiB or more)
 template <int NFG>
-__device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx, int by, int bz, int ny) {
-  typedef double v4d __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(kThreads, 3 - NFG) void k_leg_synth_mfma2(LegParams p) {
   __shared__ double slab[kThreads / 64][2][kLeg2Rows][kLegPitch];
   __shared__ double ringf[kThreads / 64][2][64];
-  const int m = bx, rc = by, f0 = bz * (kLegF * NFG);
+  const int m = blockIdx.x, rc = blockIdx.y, f0 = blockIdx.z * (kLegF * NFG);
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nring = p.g.nring, npair = (nring + 1) / 2;
-  const int64_t mstride = p.g.mmax + 1;
   double(*sl)[kLeg2Rows][kLegPitch] = slab[wave];
-#ifdef LEG_STAMPS
-  unsigned long long st[6];
-  auto stamp = [&](int i) {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    st[i] = t;
-  };
-  stamp(0);
-#define LEG_STAMP(i) stamp(i)
-#else
-#define LEG_STAMP(i)
-#endif
 
   // Ring tiles (16 consecutive ring pairs) go round robin over the waves of ALL the blocks of this (m, frequency group):
   // wave W = 4 rc + wave owns the tiles W, W + NW, W + 2 NW, W + 3 NW, so every wave holds polar and equatorial rings alike
-  const int NW = ny * (kThreads / 64), W = rc * (kThreads / 64) + wave;
-  // generation state of this thread's ring pair
-  const int r = 16 * (W + (lane >> 4) * NW) + (lane & 15);
-  double x = 0.0, lam = 0.0, lam_prev = 0.0;
-  int nsc = -1;
-  {
-    double inv_s2 = 0.0, xs2 = 0.0;
-    if (r < npair) {
-      const double sth = p.g.sth[r];
-      x = p.g.z[r];
-      inv_s2 = 1.0 / (sth * sth);
-      xs2 = x * inv_s2;
-      if (!ring_skips_m(m, lmax, sth)) lam_start(p.g.lfac[m], m, sth, lam, nsc);
-    }
-    ringf[wave][0][lane] = xs2;
-    ringf[wave][1][lane] = inv_s2;
-  }
+  const int NW = gridDim.y * (kThreads / 64), W = rc * (kThreads / 64) + wave;
+  // generation state of this thread's ring pair; its 1 / sin^2 and x / sin^2 go to the lanes that build the A operands
+  const LegRing R0 = leg_ring_start(p.g, m, 16 * (W + (lane >> 4) * NW) + (lane & 15), (p.g.nring + 1) / 2);
+  const double x = R0.x;
+  double lam = R0.lam, lam_prev = 0.0;
+  int nsc = R0.nsc;
+  ringf[wave][0][lane] = R0.xs2;
+  ringf[wave][1][lane] = R0.inv_s2;
   const bool wave_live = __any(nsc >= 0);
 
   // MFMA operand coordinates of this lane
   const int li = lane & 15, kq = lane >> 4;
-  const int col = li, fi = col >> 2, c = col & 3;
+  const LegCol col = leg_col(lane);
+  const int fi = col.fi;
   int fq[NFG];
   bool fok[NFG];
 #pragma unroll
@@ -415,20 +422,15 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
     for (int h = 0; h < NFG; ++h) {
       const int fr = (fok[h] ? fq[h] : p.nf - 1) - f0;
       auto colofs = [&](int pol, int comp) { return (unsigned)((((int64_t)fr * 4 + pol) * p.n_m * (lmax + 1)) * 16 + comp * 8); };
-      oTV[h] = colofs(c < 2 ? 0 : 3, c & 1);
-      o1[h] = colofs(c < 2 ? 1 : 2, c & 1);
-      o2[h] = colofs(c < 2 ? 2 : 1, (c & 1) ^ 1);
+      oTV[h] = colofs(col.polTV, col.comp);
+      o1[h] = colofs(col.pol1, col.comp);
+      o2[h] = colofs(col.pol2, col.comp ^ 1);
     }
-    const unsigned s2x = (c == 0 || c == 3) ? 0u : 0x80000000u;  // sign of the F2 data column: xor on the high word
+    const unsigned s2x = col.f2neg ? 0x80000000u : 0u;  // sign of the F2 data column: xor on the high word
     const int nchunk = (nl + kLegL - 1) / kLegL;
     auto fetch_rr = [&](int c0) {  // (ra, rb) of a chunk's 8 rows: lanes 0..15, one double each
       const int row = c0 + ((lane >> 1) & 7);
       return *reinterpret_cast<const double*>(cbase + 64u * (unsigned)(row < nl ? row : nl - 1) + 8u * (lane & 1));
-    };
-    auto bcast = [&](double v, int src) {
-      const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-      const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-      return __hiloint2double(hi, lo);
     };
     // operands of the MFMA lanes for one chunk: the spin-2 factors of this lane's two l and its B values
     struct LaneOps {
@@ -468,9 +470,11 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
     double le_prev = 0.0;
     // one step of the recurrence of a chunk -> row kk + 1 of buffer nb.  PEND: some lane of the wave still carries 2^-800
     // blocks (wave-uniform, decided per chunk): the rescale test and the mask of the parked value, written WITHOUT branches
-    // -- the chunk body is one scheduling region, so that the compiler can place its non-f64 instructions under the MFMAs
+    // -- the chunk body is one scheduling region, so that the compiler can place its non-f64 instructions under the MFMAs.
+    // This select-and-multiply step is not leg_step's test-and-branch, and prep_build's (-F1, F2) below are not leg_spin2's
+    // association: different roundings on purpose (both are what the pipeline was tuned with), pinned bit for bit.
     auto rec_step = [&](int nb, int kk, double cvr, bool first, bool PEND) {
-      const double ra = bcast(cvr, 2 * kk), rb = bcast(cvr, 2 * kk + 1);
+      const double ra = bcast_lane(cvr, 2 * kk), rb = bcast_lane(cvr, 2 * kk + 1);
       // (no lane mask: a ring that takes no part carries lam = lam_prev = 0 and stays there; steps beyond lmax run on the
       // last coefficient row and stay finite -- their B operands are zero)
       if (!(first && kk == 0)) {
@@ -526,7 +530,6 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
       }
     };
 
-    LEG_STAMP(1);
     // prologue: chunk 0 into buffer 0
     double cvr = fetch_rr(0);
     double cvr_next = fetch_rr(kLegL < nl ? kLegL : 0);
@@ -551,7 +554,7 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
         issue(g & 3, g >> 2, ops);
         rec_step(nb, g, cvr, false, PEND);
         if (g + 1 < kLegL) prep_build((g + 1) >> 2, ops);
-        if (PIPE_HINT) pipeline();
+        pipeline();
         __builtin_amdgcn_sched_barrier(0);
       }
       prep_load(nb, 0, 0);
@@ -559,11 +562,9 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
       finish_ops(ops_next, c0n, ragged);
       ops = ops_next;
     };
-    LEG_STAMP(2);
     // (two loops, not a branch inside one: lanes only ever leave the pending state)
     int ch = 0;
     for (; ch + 1 < nchunk && __any(nsc > 0); ++ch) body(ch, true);
-    LEG_STAMP(3);
     for (; ch + 1 < nchunk; ++ch) body(ch, false);
     // last chunk: products only
     {
@@ -578,45 +579,10 @@ __device__ __forceinline__ void leg_synth_mfma2_body(const LegParams& p, int bx,
       }
     }
   }
-  LEG_STAMP(4);
-  // ring coefficients: north = sym + anti, south = sym - anti; D rows = rings (kq + 4 reg), D columns = this lane's column
-  // (the Q | U accumulators hold MINUS the F1 terms' sign convention of the first form folded into the A operand: same sums),
-  // stored as by the first form: one 16-byte (T | V, Q | U) pair per lane and ring, eight whole 128-byte lines per wave
-  double* bout = reinterpret_cast<double*>(p.b) + 2 * (c & 1);
+  // stored as by the first form (the minus of the F1 terms is folded into the A operand: same sums in the Q | U tiles)
 #pragma unroll
-  for (int h = 0; h < NFG; ++h) {
-    if (!fok[h]) continue;
-    const int f = fq[h];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int rr = 16 * (W + t * NW) + kq + 4 * reg;
-        if (rr >= npair) continue;
-        const int rs = nring - 1 - rr;
-        const double tv = acc[h][t][0][reg], tva = acc[h][t][1][reg], qu = acc[h][t][2][reg], qua = acc[h][t][3][reg];
-        *reinterpret_cast<double2*>(bout + syn4_at(f, m, rr, c >> 1, nring, (int)mstride)) = make_double2(tv + tva, qu + qua);
-        if (rs != rr) *reinterpret_cast<double2*>(bout + syn4_at(f, m, rs, c >> 1, nring, (int)mstride)) = make_double2(tv - tva, qu - qua);
-      }
-  }
-#ifdef LEG_STAMPS
-  stamp(5);
-  if (p.stamps && lane == 0) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    unsigned long long* o = p.stamps + 8 * ((((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + wave);
-    for (int i = 0; i < 6; ++i) o[i] = wave_live ? st[i] : (i == 0 || i == 5 ? st[i] : st[0]);
-    o[6] = ((unsigned long long)xcc << 32) | hw;
-    o[7] = m;
-  }
-#endif
-}
-
-template <int NFG>
-__global__ __launch_bounds__(kThreads, 3 - NFG) void k_leg_synth_mfma2(LegParams p) {
-  leg_synth_mfma2_body<NFG>(p, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
+  for (int h = 0; h < NFG; ++h)
+    if (fok[h]) leg_store_syn4(p, fq[h], m, col, kq, acc[h], [&](int t) { return 16 * (W + t * NW); });
 }
 
 // ---------------------------------------------------------------- analysis, stage 2'
@@ -625,8 +591,7 @@ __global__ __launch_bounds__(kThreads, 3 - NFG) void k_leg_synth_mfma2(LegParams
 // linear id, so with m = blockIdx.x the eight blocks that share a line sat on eight different L2s: every line was fetched
 // eight times over.  Here the blocks b, b + 8, ..., b + 56 of one XCD take eight consecutive m (groups of 64; a last partial
 // group keeps m = b).
-__device__ __forceinline__ int leg_m_of_block(int b, int n_m, int variant_identity) {
-  if (variant_identity) return b;
+__device__ __forceinline__ int leg_m_of_block(int b, int n_m) {
   const int q = b >> 6, r = b & 63;
   if (q * 64 + 64 > n_m) return b;
   return q * 64 + (r & 7) * 8 + (r >> 3);
@@ -638,7 +603,6 @@ struct LegAnalParams {
   const double2* b;   // [nf, npol, nring, mmax+1] ring coefficients g_m
   double2* alm;       // [nf, npol, n_m, lmax+1]
   int accumulate;     // 1: alm += result (Jacobi refinement)
-  int m_identity;     // 1: block b takes m = b (sht_variant bit 5)
 };
 
 // Sum NV per-lane values over the 64 lanes of a wave with a halving butterfly: at each of
@@ -692,40 +656,25 @@ __global__ __launch_bounds__(kThreads) void k_leg_anal(LegAnalParams p) {
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nring = p.g.nring, npair = (nring + 1) / 2;
-  const double lfac_m = p.g.lfac[m];
   const int64_t mstride = p.g.mmax + 1;
 
-  struct Ring {
-    double x, inv_s2, xs2, lam, lam_prev;
-    int nsc;       // pending 2^-800 blocks; < 0: ring takes no part (skipped or out of range)
-    double2 gs[NPOL], ga[NPOL];
-  };
   int buf = 0;
   for (int r0 = 0; r0 < npair; r0 += 2 * kThreads) {  // uniform trip count: barriers inside
-    Ring R[2];
+    LegRing R[2];
+    double2 gs[2][NPOL], ga[2][NPOL];  // sym / anti combinations of the north and south ring coefficients
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const int r = r0 + t * kThreads + threadIdx.x;
-      const bool live = r < npair;
-      const int rr = live ? r : 0;
-      const double x = p.g.z[rr], sth = p.g.sth[rr];
-      const int rs = nring - 1 - rr;
-      R[t].x = x;
-      R[t].inv_s2 = 1.0 / (sth * sth);
-      R[t].xs2 = x * R[t].inv_s2;
-      R[t].lam = R[t].lam_prev = 0.0;
-      R[t].nsc = -1;
-      if (live && !ring_skips_m(m, lmax, sth)) lam_start(lfac_m, m, sth, R[t].lam, R[t].nsc);
-      // sym / anti combinations of the north and south ring coefficients
+      const int r = r0 + t * kThreads + threadIdx.x, rs = nring - 1 - r;
+      R[t] = leg_ring_start(p.g, m, r, npair);
 #pragma unroll
       for (int q = 0; q < NPOL; ++q) {
         double2 n = {0, 0}, s = {0, 0};
-        if (live) {
-          n = p.b[(((int64_t)f * NPOL + q) * nring + rr) * mstride + m];
-          if (rs != rr) s = p.b[(((int64_t)f * NPOL + q) * nring + rs) * mstride + m];
+        if (r < npair) {
+          n = p.b[(((int64_t)f * NPOL + q) * nring + r) * mstride + m];
+          if (rs != r) s = p.b[(((int64_t)f * NPOL + q) * nring + rs) * mstride + m];
         }
-        R[t].gs[q] = make_double2(n.x + s.x, n.y + s.y);
-        R[t].ga[q] = make_double2(n.x - s.x, n.y - s.y);
+        gs[t][q] = make_double2(n.x + s.x, n.y + s.y);
+        ga[t][q] = make_double2(n.x - s.x, n.y - s.y);
       }
     }
     Coef qn = load_coef(coef);
@@ -743,32 +692,24 @@ __global__ __launch_bounds__(kThreads) void k_leg_anal(LegAnalParams p) {
         bool act = false;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          Ring& g = R[t];
-          if (k > 0 && g.nsc >= 0) {
-            const double nxt = g.x * g.lam * q.ra - g.lam_prev * q.rb;
-            g.lam_prev = g.lam;
-            g.lam = nxt;
-            if (g.nsc > 0 && fabs(g.lam) > kBig) {
-              g.lam *= kSmallStep;
-              g.lam_prev *= kSmallStep;
-              --g.nsc;
-            }
-          }
+          LegRing& g = R[t];
+          if (k > 0 && g.nsc >= 0) leg_step(g, q.ra, q.rb);
           if (g.nsc == 0) {
             act = true;
             const bool even = !(kk & 1);  // k0 is a multiple of the (even) batch: static per unrolled step
-            const double2 gT = even ? g.gs[0] : g.ga[0];
+            const double2 gT = even ? gs[t][0] : ga[t][0];
             v[0] = fma(gT.x, g.lam, v[0]);
             v[1] = fma(gT.y, g.lam, v[1]);
             if (NPOL == 4) {
-              const double2 gV = even ? g.gs[NPOL - 1] : g.ga[NPOL - 1];
+              const double2 gV = even ? gs[t][NPOL - 1] : ga[t][NPOL - 1];
               v[NV - 2] = fma(gV.x, g.lam, v[NV - 2]);
               v[NV - 1] = fma(gV.y, g.lam, v[NV - 1]);
-              const double F1 = fma(q.cd * g.xs2, g.lam_prev, -fma(q.c1, g.inv_s2, q.c2) * g.lam);
-              const double F2 = fma(q.c4 * g.inv_s2, g.lam_prev, -q.c3 * g.xs2 * g.lam);
+              double F1, F2;
+              leg_spin2(q, g.inv_s2, g.xs2, g.lam, g.lam_prev, F1, F2);
               // F1 pairs with the lambda-parity combination, F2 with the opposite one
-              const double2 Q1 = even ? g.gs[NPOL > 1 ? 1 : 0] : g.ga[NPOL > 1 ? 1 : 0], Q2 = even ? g.ga[NPOL > 1 ? 1 : 0] : g.gs[NPOL > 1 ? 1 : 0];
-              const double2 U1 = even ? g.gs[NPOL > 2 ? 2 : 0] : g.ga[NPOL > 2 ? 2 : 0], U2 = even ? g.ga[NPOL > 2 ? 2 : 0] : g.gs[NPOL > 2 ? 2 : 0];
+              constexpr int iQ = NPOL > 1 ? 1 : 0, iU = NPOL > 2 ? 2 : 0;
+              const double2 Q1 = even ? gs[t][iQ] : ga[t][iQ], Q2 = even ? ga[t][iQ] : gs[t][iQ];
+              const double2 U1 = even ? gs[t][iU] : ga[t][iU], U2 = even ? ga[t][iU] : gs[t][iU];
               // E = -(F1 gQ + i F2 gU),  B = -(F1 gU - i F2 gQ)
               v[NV > 2 ? 2 : 0] -= F1 * Q1.x - F2 * U2.y;
               v[NV > 2 ? 3 : 0] -= F1 * Q1.y + F2 * U2.x;
@@ -816,39 +757,28 @@ __global__ __launch_bounds__(kThreads) void k_leg_anal(LegAnalParams p) {
 
 // ---- analysis, stage 2' on the matrix cores (NPOL = 4).
 // a_lm = sum over ring pairs of {lambda, F1, F2}(ring, l) x ring data: for one m a product
-// (l x ring) . (ring x (frequency, component)).  A block owns one m and kLegF frequencies; each of its 8
+// (l x ring) . (ring x (frequency, component)).  A block owns one m and kLegF frequencies; each of its 4
 // waves owns 64 ring pairs: the lanes run the recurrences of their ring for kAnL = 32 steps and park lambda
 // in a wave-private LDS slab; the wave then contracts its rings, four per MFMA, against the ring data it
-// keeps in registers for the whole kernel:
+// keeps in registers for the whole pass:
 //   TV[q] += lambda x (T, V)_q            q = 0 / 1: the north+south / north-south combination
 //   EB[q] += F1 x (-Q, -U)_q  +  F2 x (U.y, -U.x, -Q.y, Q.x)_{1-q}
 // with M = the 16 l of parity q of the chunk (rows 2i + q of the slab: every row of every tile is used),
 // K = 4 rings, N = 16 = kLegF frequencies x 4 reals.  F1 / F2 are formed from lambda_l, lambda_{l-1} of the
 // slab and the lane's own l coefficients when the operand is built, so the slab holds lambda only.  The
 // F2 operand is the F1 operand with its four columns reversed and two signs flipped: one DPP move.
-// The 8 waves' tiles are parked in their (then free) slabs, summed in a fixed order once per chunk and
+// The waves' tiles are parked in their (then free) slabs, summed in a fixed order once per chunk and
 // added to a_lm.  Slab pitch 65: the 16 rows (stride 2) x 2 rings of a half wave fall on disjoint banks.
-constexpr int kAnL = 32, kAnPitch = 65, kAnThreads = 512;
-// NT = 256 (default): 4 waves, 69 KB of slabs -- two independent blocks per CU, the ring pairs in passes of 256, every
-// later pass adding to the a_lm of the one before (fixed summation order within a pass and across passes).
-// NT = kAnThreads = 512 (sht_variant bit 4, the form of rounds 1-3): one block of 8 waves per CU (137 KB), every ring pair
-// of nside <= 256 in one pass; two barriers per 32-l chunk hold eight waves instead of four.
+// 4 waves, 69 KB of slabs: two independent blocks per CU, the ring pairs in passes of 256, every later pass adding to
+// the a_lm of the one before (fixed summation order within a pass and across passes).  The (ra, rb) of a chunk's 32
+// steps are parked in LDS once per chunk and read back as one broadcast ds_read_b128 per step.
+constexpr int kAnL = 32, kAnPitch = 65, kAnWaves = kThreads / 64;
 
-// NFG = frequency groups (of kLegF = 4 frequencies: one MFMA B operand) per block.  NFG = 2 (round 5, `sht_variant` bit 9, an
-// A/B): the recurrence and the formation of the A operands -- nothing of which hides under an f64 MFMA on this part, DESIGN
-// 5.4 -- serve twice the products; the ring data of both groups stay in registers (512 per lane, one wave per SIMD: NT = 256
-// only) -- and come back from the AGPR half of the file through a copy per product: slower than NFG = 1.  The (ra, rb) of a
-// chunk's 32 steps are parked in LDS once per chunk and read back as one broadcast ds_read_b128 per step (round 4: four
-// v_readlane per step, ~10 cycles each).
-template <int NT, int NFG>
-__global__ __launch_bounds__(NT, NFG == 2 ? 1 : 512 / NT) void k_leg_anal_mfma(LegAnalParams p) {
-  constexpr int kAnWaves = NT / 64;
-  static_assert(NFG == 1 || NT == 256, "two frequency groups per block: the 4-wave form only");
-  typedef double v4d __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(kThreads, 2) void k_leg_anal_mfma(LegAnalParams p) {
   __shared__ double slab[kAnWaves][(kAnL + 1) * kAnPitch];  // row 0: lambda of the step before the chunk
   __shared__ double ringtab[kAnWaves][2][64];                // x / sin^2, 1 / sin^2 of the wave's rings
   __shared__ double2 rrtab[kAnWaves][kAnL];                  // (ra, rb) of the chunk's steps
-  const int m = leg_m_of_block(blockIdx.x, p.g.mmax + 1, p.m_identity), f0 = blockIdx.y * (kLegF * NFG);
+  const int m = leg_m_of_block(blockIdx.x, p.g.mmax + 1), f0 = blockIdx.y * kLegF;
   const int lmax = p.g.lmax, nl = lmax - m + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nring = p.g.nring, npair = (nring + 1) / 2;
@@ -858,63 +788,50 @@ __global__ __launch_bounds__(NT, NFG == 2 ? 1 : 512 / NT) void k_leg_anal_mfma(L
   double* alm_d = reinterpret_cast<double*>(p.alm);
 
   // structural zeros l < m
-  for (int idx = threadIdx.x; idx < kLegF * NFG * 4 * m; idx += NT) {
+  for (int idx = threadIdx.x; idx < kLegF * 4 * m; idx += kThreads) {
     const int fp = idx / m, l = idx - fp * m;
     const int f = f0 + (fp >> 2);
     if (f < p.nf) p.alm[(((int64_t)f * 4 + (fp & 3)) * p.n_m + m) * (lmax + 1) + l] = make_double2(0.0, 0.0);
   }
 
   const int li = lane & 15, kq = lane >> 4;
-  const int col = li, fi = col >> 2, c = col & 3;
+  const LegCol col = leg_col(lane);
+  const int f = f0 + col.fi;
+  const bool fok = f < p.nf;
   const double* bsrc = reinterpret_cast<const double*>(p.b);
 
-  for (int r0 = 0; r0 < npair; r0 += NT) {  // ring super-chunks of NT pairs
+  for (int r0 = 0; r0 < npair; r0 += kThreads) {  // ring passes of kThreads pairs
     // generation state of this thread's ring pair
-    const int r = r0 + threadIdx.x;
-    double x = 0.0, inv_s2 = 0.0, xs2 = 0.0, lam = 0.0, lam_prev = 0.0;
-    int nsc = -1;
-    if (r < npair) {
-      const double sth = p.g.sth[r];
-      x = p.g.z[r];
-      inv_s2 = 1.0 / (sth * sth);
-      xs2 = x * inv_s2;
-      if (!ring_skips_m(m, lmax, sth)) lam_start(p.g.lfac[m], m, sth, lam, nsc);
-    }
-    ringtab[wave][0][lane] = xs2;
-    ringtab[wave][1][lane] = inv_s2;
+    LegRing R = leg_ring_start(p.g, m, r0 + threadIdx.x, npair);
+    ringtab[wave][0][lane] = R.xs2;
+    ringtab[wave][1][lane] = R.inv_s2;
     sl[lane] = 0.0;
-    const bool wave_live = __any(nsc >= 0);
+    const bool wave_live = __any(R.nsc >= 0);
 
     // ring data of the wave's 64 pairs as MFMA B operands, kept for every l: per K step ks the lane holds
-    // column `col` of ring 4 ks + kq -- (T | V) and -(Q | U), north+south and north-south
-    double bTV[NFG][16][2], g1[NFG][16][2];
+    // its column of ring 4 ks + kq -- (T | V) and -(Q | U), north+south and north-south
+    double bTV[16][2], g1[16][2];
 #pragma unroll
-    for (int h = 0; h < NFG; ++h) {
-      const int f = f0 + kLegF * h + fi;
-      const bool fok = f < p.nf;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        const int rr = r0 + wave * 64 + 4 * ks + kq;
-        double tn = 0.0, ts = 0.0, qn = 0.0, qs = 0.0;
-        if (wave_live && fok && rr < npair) {
-          const int rs = nring - 1 - rr;
-          const int64_t on = (((int64_t)f * 4) * nring + rr) * mstride + m, os = (((int64_t)f * 4) * nring + rs) * mstride + m;
-          const int64_t pstride = (int64_t)nring * mstride;
-          const int polTV = c < 2 ? 0 : 3, pol1 = c < 2 ? 1 : 2, comp = c & 1;
-          tn = bsrc[(on + polTV * pstride) * 2 + comp];
-          qn = bsrc[(on + pol1 * pstride) * 2 + comp];
-          if (rs != rr) {
-            ts = bsrc[(os + polTV * pstride) * 2 + comp];
-            qs = bsrc[(os + pol1 * pstride) * 2 + comp];
-          }
+    for (int ks = 0; ks < 16; ++ks) {
+      const int rr = r0 + wave * 64 + 4 * ks + kq;
+      double tn = 0.0, ts = 0.0, qn = 0.0, qs = 0.0;
+      if (wave_live && fok && rr < npair) {
+        const int rs = nring - 1 - rr;
+        const int64_t on = (((int64_t)f * 4) * nring + rr) * mstride + m, os = (((int64_t)f * 4) * nring + rs) * mstride + m;
+        const int64_t pstride = (int64_t)nring * mstride;
+        tn = bsrc[(on + col.polTV * pstride) * 2 + col.comp];
+        qn = bsrc[(on + col.pol1 * pstride) * 2 + col.comp];
+        if (rs != rr) {
+          ts = bsrc[(os + col.polTV * pstride) * 2 + col.comp];
+          qs = bsrc[(os + col.pol1 * pstride) * 2 + col.comp];
         }
-        bTV[h][ks][0] = tn + ts;
-        bTV[h][ks][1] = tn - ts;
-        g1[h][ks][0] = -(qn + qs);
-        g1[h][ks][1] = -(qn - qs);
       }
+      bTV[ks][0] = tn + ts;
+      bTV[ks][1] = tn - ts;
+      g1[ks][0] = -(qn + qs);
+      g1[ks][1] = -(qn - qs);
     }
-    const double sg2 = (c == 0 || c == 3) ? -1.0 : 1.0;  // g2[c] = sg2 * g1[3 - c]
+    const double sg2 = col.f2neg ? 1.0 : -1.0;  // g2[c] = sg2 * g1[3 - c] (g1 carries a minus already)
 
     auto fetch_rr = [&](int row0) {  // (ra, rb) of the chunk's 32 rows: one double per lane
       const int row = row0 + (lane >> 1);
@@ -923,58 +840,44 @@ __global__ __launch_bounds__(NT, NFG == 2 ? 1 : 512 / NT) void k_leg_anal_mfma(L
     double cvr = fetch_rr(0);
 
     for (int c0 = 0; c0 < nl; c0 += kAnL) {
-      v4d acc[NFG][4];  // TV q=0, TV q=1, EB q=0, EB q=1
+      v4d acc[4];  // TV q=0, TV q=1, EB q=0, EB q=1
 #pragma unroll
-      for (int h = 0; h < NFG; ++h)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[h][t] = (v4d){0.0, 0.0, 0.0, 0.0};
+      for (int t = 0; t < 4; ++t) acc[t] = (v4d){0.0, 0.0, 0.0, 0.0};
       if (wave_live) {
         const double cvr_next = fetch_rr(c0 + kAnL < nl ? c0 + kAnL : c0);
         reinterpret_cast<double*>(rrtab[wave])[lane] = cvr;  // (wave-private: LDS operations of a wave complete in order)
         // this lane's two l (one per parity tile): the spin-2 factors of its A operands
-        double qc1[2], qc2[2], qcd[2], qc3[2], qc4[2];
+        Coef qc[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const int lrow = c0 + 2 * li + q < nl ? c0 + 2 * li + q : nl - 1;
           const double* cr = cgv + 8 * (int64_t)lrow;
-          qc1[q] = cr[2];
-          qc2[q] = cr[3];
-          qcd[q] = cr[4];
-          qc3[q] = cr[5];
-          qc4[q] = cr[6];
+          qc[q].c1 = cr[2];
+          qc[q].c2 = cr[3];
+          qc[q].cd = cr[4];
+          qc[q].c3 = cr[5];
+          qc[q].c4 = cr[6];
         }
         // kAnL steps of the recurrence -> slab rows 1..kAnL
-        if (c0 > 0 && !__any(nsc > 0)) {
+        if (c0 > 0 && !__any(R.nsc > 0)) {
           // no lane of the wave carries 2^-800 blocks any more (wave-uniform; lanes only ever leave that state): three f64
           // operations per step, no test, no select -- a ring that takes no part carries lam = lam_prev = 0 and stays
           // there, the steps beyond lmax run on the last coefficient row and their rows of a_lm are never written
 #pragma unroll
           for (int kk = 0; kk < kAnL; ++kk) {
             const double2 rr2 = rrtab[wave][kk];  // broadcast read
-            const double nxt = x * lam * rr2.x - lam_prev * rr2.y;
-            lam_prev = lam;
-            lam = nxt;
-            sl[(1 + kk) * kAnPitch + lane] = lam;
+            leg_advance(R, rr2.x, rr2.y);
+            sl[(1 + kk) * kAnPitch + lane] = R.lam;
           }
         } else {
 #pragma unroll
           for (int kk = 0; kk < kAnL; ++kk) {
             const int k = c0 + kk;
             const double2 rr2 = rrtab[wave][kk];  // broadcast read
-            const double ra = rr2.x, rb = rr2.y;
             double le = 0.0;
             if (k < nl) {
-              if (k > 0 && nsc >= 0) {
-                const double nxt = x * lam * ra - lam_prev * rb;
-                lam_prev = lam;
-                lam = nxt;
-                if (nsc > 0 && fabs(lam) > kBig) {
-                  lam *= kSmallStep;
-                  lam_prev *= kSmallStep;
-                  --nsc;
-                }
-              }
-              if (nsc == 0) le = lam;
+              if (k > 0 && R.nsc >= 0) leg_step<true>(R, rr2.x, rr2.y);
+              if (R.nsc == 0) le = R.lam;
             }
             sl[(1 + kk) * kAnPitch + lane] = le;
           }
@@ -987,56 +890,51 @@ __global__ __launch_bounds__(NT, NFG == 2 ? 1 : 512 / NT) void k_leg_anal_mfma(L
           // lambda at l - 1, l (parity 0 row), l + 1 (parity 1 row) of this lane's row pair
           const double l0 = sl[(2 * li) * kAnPitch + rk], l1 = sl[(2 * li + 1) * kAnPitch + rk], l2 = sl[(2 * li + 2) * kAnPitch + rk];
           const double rx = ringtab[wave][0][rk], ri = ringtab[wave][1][rk];
-          const double a1e = fma(qcd[0] * rx, l0, -fma(qc1[0], ri, qc2[0]) * l1);
-          const double a2e = fma(qc4[0] * ri, l0, -qc3[0] * rx * l1);
-          const double a1o = fma(qcd[1] * rx, l1, -fma(qc1[1], ri, qc2[1]) * l2);
-          const double a2o = fma(qc4[1] * ri, l1, -qc3[1] * rx * l2);
+          double a1e, a2e, a1o, a2o;
+          leg_spin2(qc[0], ri, rx, l1, l0, a1e, a2e);
+          leg_spin2(qc[1], ri, rx, l2, l1, a1o, a2o);
+          // F2 data: columns reversed within each frequency (quad_perm 3,2,1,0), signs (-,+,+,-)
+          double g2[2];
 #pragma unroll
-          for (int h = 0; h < NFG; ++h) {
-            // F2 data: columns reversed within each frequency (quad_perm 3,2,1,0), signs (-,+,+,-)
-            double g2[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const int lo = __builtin_amdgcn_mov_dpp(__double2loint(g1[h][ks][q]), 0x1b, 0xf, 0xf, true);
-              const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(g1[h][ks][q]), 0x1b, 0xf, 0xf, true);
-              g2[q] = sg2 * __hiloint2double(hi, lo);
-            }
-            acc[h][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(l1, bTV[h][ks][0], acc[h][0], 0, 0, 0);
-            acc[h][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(l2, bTV[h][ks][1], acc[h][1], 0, 0, 0);
-            acc[h][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1e, g1[h][ks][0], acc[h][2], 0, 0, 0);
-            acc[h][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1o, g1[h][ks][1], acc[h][3], 0, 0, 0);
-            acc[h][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2e, g2[1], acc[h][2], 0, 0, 0);
-            acc[h][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2o, g2[0], acc[h][3], 0, 0, 0);
+          for (int q = 0; q < 2; ++q) {
+            const int lo = __builtin_amdgcn_mov_dpp(__double2loint(g1[ks][q]), 0x1b, 0xf, 0xf, true);
+            const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(g1[ks][q]), 0x1b, 0xf, 0xf, true);
+            g2[q] = sg2 * __hiloint2double(hi, lo);
           }
+          acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(l1, bTV[ks][0], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(l2, bTV[ks][1], acc[1], 0, 0, 0);
+          acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1e, g1[ks][0], acc[2], 0, 0, 0);
+          acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1o, g1[ks][1], acc[3], 0, 0, 0);
+          acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2e, g2[1], acc[2], 0, 0, 0);
+          acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2o, g2[0], acc[3], 0, 0, 0);
         }
         sl[lane] = sl[kAnL * kAnPitch + lane];  // lambda of the last step: "l - 1" of the next chunk
       }
-      // park the tiles in the (now free) rows 1.. of the own slab as [group][TV | EB][l row 0..31][16 columns]:
+      // park the tiles in the (now free) rows 1.. of the own slab as [TV | EB][l row 0..31][16 columns]:
       // tile q row i = kq + 4 reg is l row 2 i + q
       double* out = sl + kAnPitch;
 #pragma unroll
-      for (int h = 0; h < NFG; ++h)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int i = kq + 4 * reg;
-          out[((2 * h + 0) * kAnL + 2 * i + 0) * 16 + li] = acc[h][0][reg];
-          out[((2 * h + 0) * kAnL + 2 * i + 1) * 16 + li] = acc[h][1][reg];
-          out[((2 * h + 1) * kAnL + 2 * i + 0) * 16 + li] = acc[h][2][reg];
-          out[((2 * h + 1) * kAnL + 2 * i + 1) * 16 + li] = acc[h][3][reg];
-        }
+      for (int reg = 0; reg < 4; ++reg) {
+        const int i = kq + 4 * reg;
+        out[(0 * kAnL + 2 * i + 0) * 16 + li] = acc[0][reg];
+        out[(0 * kAnL + 2 * i + 1) * 16 + li] = acc[1][reg];
+        out[(1 * kAnL + 2 * i + 0) * 16 + li] = acc[2][reg];
+        out[(1 * kAnL + 2 * i + 1) * 16 + li] = acc[3][reg];
+      }
       __syncthreads();
-      // 1024 NFG / NT values per thread: fixed-order sum over the waves, then into a_lm
+      // 1024 / kThreads values per thread: fixed-order sum over the waves, then into a_lm
 #pragma unroll
-      for (int hh = 0; hh < 1024 * NFG / NT; ++hh) {
-        const int idx = threadIdx.x + hh * NT;  // [group][tile][row][col]
-        const int h = idx >> 10, tile = (idx >> 9) & 1, row = (idx >> 4) & 31, oc = idx & 15;
+      for (int hh = 0; hh < 1024 / kThreads; ++hh) {
+        const int idx = threadIdx.x + hh * kThreads;  // [tile][row][col]
+        const int tile = idx >> 9, row = (idx >> 4) & 31;
+        const LegCol oc = leg_col(idx);
         double sum = 0.0;
 #pragma unroll
         for (int w = 0; w < kAnWaves; ++w) sum += slab[w][kAnPitch + idx];
-        const int k = c0 + row, of = f0 + kLegF * h + (oc >> 2), cc = oc & 3;
+        const int k = c0 + row, of = f0 + oc.fi;
         if (k < nl && of < p.nf) {
-          const int pol = tile == 0 ? (cc < 2 ? 0 : 3) : (cc < 2 ? 1 : 2);
-          double* dst = alm_d + ((((int64_t)of * 4 + pol) * p.n_m + m) * (lmax + 1) + m + k) * 2 + (cc & 1);
+          const int pol = tile == 0 ? oc.polTV : oc.pol1;
+          double* dst = alm_d + ((((int64_t)of * 4 + pol) * p.n_m + m) * (lmax + 1) + m + k) * 2 + oc.comp;
           *dst = (p.accumulate || r0 > 0) ? *dst + sum : sum;
         }
       }
@@ -1044,6 +942,5 @@ __global__ __launch_bounds__(NT, NFG == 2 ? 1 : 512 / NT) void k_leg_anal_mfma(L
     }
   }
 }
-
 
 }  // namespace

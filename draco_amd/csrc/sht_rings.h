@@ -14,7 +14,6 @@ struct RingParams {
   int64_t npix;
   const double* map_ref;  // analysis only, or nullptr: the field analysed is map_ref - map (the residual of a Jacobi iteration of
                           // map2alm, formed on the way in instead of by a pass of its own over the maps)
-  int radix8;             // 1 (default): the in-LDS transforms with three stages per pass (fft_dif8 / fft_dit8); 0: two (sht_variant bit 11)
   int stage_all;          // synthesis: 1 = every ring stages the rotated coefficients of a pass in LDS (k_ring_synth_fft), 0 = the aliased ones
 };
 
@@ -158,13 +157,12 @@ __global__ void k_fill_ring_tables(const double* phi0, int nring, int mmax, doub
 }
 
 // forward DFT_N of the NROW rows in l.buf (natural order, already multiplied by the chirp and
-// zero-padded to M when BLUE).  Afterwards X_k is ring_dft_at(l, r, k).
+// zero-padded to M when BLUE).  Afterwards X_k is ring_dft_at(l, r, k).  (The transforms with three stages per pass.)
 template <int NROW, bool BLUE>
-__device__ __forceinline__ void ring_dft(const RingLds& l, const double2* bfilt, int M, int logM, bool radix8 = false) {
+__device__ __forceinline__ void ring_dft(const RingLds& l, const double2* bfilt, int M, int logM) {
   const int P = M + 1;
-  if (BLUE) dmm_fft::bluestein_convolve<double, kFftThreads>(l.buf, l.tw, bfilt, NROW, M, logM, P, radix8);
-  else if (radix8) dmm_fft::fft_dif8<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
-  else dmm_fft::fft_dif<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
+  if (BLUE) dmm_fft::bluestein_convolve<double, kFftThreads>(l.buf, l.tw, bfilt, NROW, M, logM, P, true);
+  else dmm_fft::fft_dif8<double, kFftThreads>(l.buf, l.tw, NROW, M, logM, P);
 }
 
 template <bool BLUE>
@@ -303,7 +301,7 @@ __global__ __launch_bounds__(kFftThreads) void k_ring_synth_fft(RingParams p, Ri
       }
     }
     __syncthreads();
-    ring_dft<NB, BLUE>(l, bfilt, M, rc.logM, p.radix8 != 0);
+    ring_dft<NB, BLUE>(l, bfilt, M, rc.logM);
     for (int j = threadIdx.x; j < n; j += kFftThreads) {
 #pragma unroll
       for (int jj = 0; jj < NB; ++jj) {
@@ -391,7 +389,7 @@ __global__ __launch_bounds__(kFftThreads) void k_ring_anal_fft(RingParams p, Rin
   }
   __syncthreads();
   const double2* bfilt = BLUE ? p.g.bfilt + p.g.bf_off[rc.belt ? 0 : rc.r_lo + ((int)blockIdx.x >> 1)] : nullptr;
-  ring_dft<NROW, BLUE>(l, bfilt, M, rc.logM, p.radix8 != 0);
+  ring_dft<NROW, BLUE>(l, bfilt, M, rc.logM);
   const int nm = p.g.mmax + 1;
   const double2* phase = p.g.phase + (int64_t)ring * nm;
   const double w = 4.0 * M_PI / (double)p.npix;

@@ -85,10 +85,10 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *    held; for an a_lm that only dmm_alm2map reads, which loads l >= m alone: same maps, half the a_lm bytes written; every
  *    other entry always writes them),
  *    "project_variant", "ringmap_variant" (1 three-kernel
- *    form, 2 eight elevations per block), "sht_variant" (bits: 0-1 vector-ALU synthesis form, 2 direct ring sums,
- *    3 vector-ALU Legendre kernels, 4 eight-wave analysis block, 5 m = blockIdx.x in the analysis, 6 first MFMA synthesis form,
- *    7 pipelined synthesis with 4 frequencies per block, 11 radix-4 ring FFTs), "sht_synth_form" (1: first MFMA form);
- *  "profile" (1: HIP-event timing of the dense solvers' kernel classes, sums cleared; 0 off). */
+ *    form, 2 eight elevations per block), "sht_variant" (bits: 2 direct ring sums, 3 vector-ALU Legendre kernels,
+ *    6 first MFMA synthesis form, 7 pipelined synthesis with 4 frequencies per block), "sht_synth_form" (1: first MFMA form);
+ *  "profile" (1: HIP-event timing of the dense solvers' kernel classes, sums cleared; 0 off).
+ * Bits of "sht_variant" other than 2, 3, 6 and 7 selected A/B forms that are gone: setting them is accepted and ignored. */
 int dmm_ctx_set_option(dmm_ctx* ctx, const char* name, int64_t value);
 /* diagnostics counters, cumulative per context ("opt_sht_synth_form": that option's current value): "ml_tiles_direct" (tiles whose pseudo-inverse was
  * certified to cut no mode and solved by Cholesky), "ml_tiles_eigen" (tiles eigen-decomposed), "ml_tiles_null" (tiles answered with zero by the null certificate: every

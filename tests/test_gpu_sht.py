@@ -164,6 +164,41 @@ def test_legendre_synthesis_kernels_agree(nside, lmax, nf):
         assert np.abs(ref - osht.sphtrans_inv_sky(alm, nside)).max() < 1e-10 * scale
 
 
+@pytest.mark.parametrize("nside,lmax,nf", [(16, 40, 3), (128, 300, 5), (256, 300, 2)])
+def test_legendre_analysis_kernels_agree(nside, lmax, nf):
+    """The two forms of the Legendre analysis at NPOL = 4 -- the MFMA kernel (default) and the vector-ALU kernel
+    (sht_variant bit 3) -- evaluate the same sums: 1e-12 of max|a_lm| apart, the project's figure for two evaluations of
+    the same sums, without and with one Jacobi iteration (the `accumulate` path).  Shapes: one ring pass with a ragged
+    frequency group and lmax + 1 - m ragged against the 32-step chunk (also pinned to the oracle); 256 ring pairs, exactly
+    one pass, with the rescaling path at high m near the poles; 512 pairs, two passes (the second adds into the a_lm of
+    the first).  Entries l < m must be exact zeros in both forms."""
+    from draco_amd import _lib
+    from draco_amd.device import Context
+
+    ctx = Context.get()
+    rng = np.random.default_rng(1000 * nside + nf)
+    maps = rng.standard_normal((nf, 4, 12 * nside * nside))
+    upper = np.triu(np.ones((lmax + 1, lmax + 1), bool), 1)  # [l, m] with l < m
+    for niter in (0, 1):
+        alm = {}
+        try:
+            for variant in (0, 8):
+                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+                alm[variant] = _map2alm_gpu(maps, lmax, lmax, niter)
+        finally:
+            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
+        scale = np.abs(alm[8]).max()
+        diff = np.abs(alm[0] - alm[8]).max() / scale
+        print(f"legendre analysis forms nside={nside} lmax={lmax} nf={nf} niter={niter}: {diff:.3e} of max|alm|")
+        for variant in (0, 8):
+            assert np.all(alm[variant][..., upper] == 0), (variant, niter)
+        assert diff < 1e-12, (niter, diff)
+        if nside <= 16:
+            ref = osht.sphtrans_sky(maps, lmax, niter)
+            for variant in (0, 8):
+                assert np.abs(alm[variant] - ref).max() < 1e-10 * np.abs(ref).max(), (variant, niter)
+
+
 def _tel(nfreq, lmax, ncyl=1, nfeed_cyl=3):
     from draco_amd.core.products import TransitTelescope
 
