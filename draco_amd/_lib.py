@@ -28,6 +28,8 @@ DMM_B_FULL, DMM_B_PACKED = 0, 1
 DMM_E_ARG, DMM_E_UNSUPPORTED, DMM_E_NOMEM, DMM_E_STATE, DMM_E_COMM = -1, -2, -3, -4, -5
 DMM_MAX_NRA = 8192
 DMM_STACK_UNIFORM, DMM_STACK_INVERSE_VARIANCE = 0, 1
+DMM_DAYENU_F32, DMM_DAYENU_F64 = 0, 1
+DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
 
 
 class DmmError(RuntimeError):
@@ -44,6 +46,10 @@ class dmm_tile(C.Structure):
 
 class dmm_gemv_desc(C.Structure):
     _fields_ = [("a_off", C.c_int64), ("x_off", C.c_int64), ("y_off", C.c_int64), ("nrow", C.c_int32), ("ncol", C.c_int32)]
+
+
+class dmm_dayenu_side(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("ncol", C.c_int64), ("stride_freq", C.c_int64), ("stride_col", C.c_int64), ("stride_inner", C.c_int64), ("stride_outer", C.c_int64)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -114,6 +120,9 @@ _SIGS = {
     "dmm_regrid_band_wiener": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmm_sidereal_stack_add": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
     "dmm_sidereal_stack_finish": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i64]),
+    "dmm_dayenu_build": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_dayenu_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
+    "dmm_dayenu_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, C.POINTER(dmm_dayenu_side), C.POINTER(dmm_dayenu_side)]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -479,6 +479,43 @@ int dmm_sidereal_stack_add(dmm_ctx* ctx, int mode, int with_variance, const void
 int dmm_sidereal_stack_finish(dmm_ctx* ctx, int mode, int with_variance, float* stack_weight, const uint16_t* stack_nsample,
                               const float* sum_coeff_sq, float* sample_variance, int64_t n);
 
+/* DAYENU delay filter (draco/analysis/dayenu.py:20-193, 776-975, 1125-1232), csrc/dayenu.hip.
+ *
+ * dmm_dayenu_build: nmat filters of order nfreq (1 ... 1024) at once.  freq [nfreq] float64 (MHz), bands
+ * [nmat][nband][2] float64 = (half width tw in micro-seconds, eps) of each stop band (centre 0), mask [nmat][nfreq]
+ * bytes (non-zero: channel kept), all [dev].  Per matrix: C = I + sum_k sinc(2 tw_k (nu_f - nu_f')) / eps_k on the kept
+ * channels (1 on the diagonal of the others), Cholesky-factored and inverted in float64, nf [nmat][nfreq][nfreq] =
+ * C^-1 o (mask x mask) [dev].  status [nmat] int32 [dev]: 0, or 1 where a pivot was not positive (that matrix is
+ * left zero, nothing else is touched).  One more nfreq^2 float64 per matrix comes from the context's scratch.
+ *
+ * A container side (dmm_dayenu_side) describes one dataset as seen by the filter, in ELEMENTS of the real dtype: the
+ * value of frequency f, column c of item (outer o, inner i) is ptr[o stride_outer + i stride_inner + c stride_col +
+ * f stride_freq]; ncol columns per item.  A complex dataset is a real one with twice the columns.  layout:
+ * DMM_DAYENU_COLS = the columns of an item are contiguous (stride_col 1: vis [freq, stack, ra]), DMM_DAYENU_ITEMS =
+ * the inner items are (stride_inner 1: map [beam, pol, freq, ra, el], items el, columns ra).
+ *
+ * dmm_dayenu_mask: flag [nouter][ninner][nfreq] bytes [dev] = all_c(weight > 0), and weight *= flag in the same pass.
+ *
+ * dmm_dayenu_apply (in place): data <- NF data and weight <- inz((NF o NF) inz(weight)) for every item, NF =
+ * nf[item_matrix[item]], on the f64 matrix cores, rounded once to dtype on the store.  item_matrix [nouter][ninner]
+ * int32 [dev]: -1 = leave the item alone, -2 = leave its data alone and zero its weight (a failed build).  atten
+ * [nmat][nfreq] bytes [dev] or NULL: where zero, the weight of that frequency is stored as 0.  units [nunit] int32
+ * [dev] or NULL: the units the launch covers (NULL: unit u = u, nunit of them) -- an item o ninner + i for
+ * DMM_DAYENU_COLS, a group of adjacent items o ngroup + g for DMM_DAYENU_ITEMS (groups of 32 for DMM_DAYENU_F32, of 16
+ * for DMM_DAYENU_F64; ngroup = ceil(ninner / group)).  data or weight may be NULL (that side is skipped). */
+enum { DMM_DAYENU_F32 = 0, DMM_DAYENU_F64 = 1 };
+enum { DMM_DAYENU_COLS = 0, DMM_DAYENU_ITEMS = 1 };
+typedef struct dmm_dayenu_side {
+  void* ptr;
+  int64_t ncol, stride_freq, stride_col, stride_inner, stride_outer;
+} dmm_dayenu_side;
+int dmm_dayenu_build(dmm_ctx* ctx, int nfreq, int nmat, int nband, const double* freq, const double* bands, const uint8_t* mask,
+                     double* nf, int32_t* status);
+int dmm_dayenu_mask(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner, int nouter, const dmm_dayenu_side* weight, uint8_t* flag);
+int dmm_dayenu_apply(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner, int nouter, const double* nf, int nmat,
+                     const int32_t* item_matrix, const uint8_t* atten, const int32_t* units, int64_t nunit,
+                     const dmm_dayenu_side* data, const dmm_dayenu_side* weight);
+
 #ifdef __cplusplus
 }
 #endif
