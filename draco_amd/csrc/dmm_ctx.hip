@@ -57,6 +57,16 @@ hipError_t dmm_ticket(dmm_ctx* ctx, unsigned long long** out) {
   return hipSuccess;
 }
 
+template <typename T2>
+static void free_tables(std::map<int, dmm_fft_tables<T2>>& m) {
+  for (auto& kv : m) {
+    if (kv.second.tw) (void)hipFree(kv.second.tw);
+    if (kv.second.chirp) (void)hipFree(kv.second.chirp);
+    if (kv.second.bfilt) (void)hipFree(kv.second.bfilt);
+  }
+  m.clear();
+}
+
 extern "C" {
 
 int dmm_version(void) { return DMM_VERSION; }
@@ -81,20 +91,11 @@ int dmm_ctx_create(int device, dmm_ctx** out) {
   return DMM_OK;
 }
 
-static void free_tables(std::map<int, dmm_fft_tables>& m) {
-  for (auto& kv : m) {
-    if (kv.second.tw) (void)hipFree(kv.second.tw);
-    if (kv.second.chirp) (void)hipFree(kv.second.chirp);
-    if (kv.second.bfilt) (void)hipFree(kv.second.bfilt);
-  }
-  m.clear();
-}
-
 int dmm_ctx_destroy(dmm_ctx* c) {
   if (!c) return DMM_OK;
   (void)hipSetDevice(c->device);
-  free_tables(c->fft);
-  free_tables(c->ifft);
+  free_tables(c->fft_f32);
+  free_tables(c->fft_f64);
   for (auto& kv : c->sht)
     if (kv.second) (void)hipFree(kv.second);
   prof_collect(c);

@@ -8,12 +8,13 @@
 
 #include "draco_amd.h"
 
+template <typename T2>           // float2 / double2
 struct dmm_fft_tables {          // per transform length, built on first use
   int n = 0;                     // nra
   int M = 0;                     // FFT length actually run (n if power of two, else Bluestein length)
-  float2* tw = nullptr;          // [M/2] exp(-2 pi i k / M)
-  float2* chirp = nullptr;       // [n]   exp(-i pi k^2 / n)              (Bluestein only)
-  float2* bfilt = nullptr;       // [M]   FFT_M(conj chirp, wrapped)/M, bit-reversed order (Bluestein only)
+  T2* tw = nullptr;              // [M/2] exp(-2 pi i k / M)
+  T2* chirp = nullptr;           // [n]   exp(-i pi k^2 / n)              (Bluestein only)
+  T2* bfilt = nullptr;           // [M]   FFT_M(conj chirp, wrapped)/M, bit-reversed order (Bluestein only)
 };
 
 // Kernel classes of the dense solvers that bench.py times live (HIP events on the stream a class is launched on;
@@ -34,8 +35,8 @@ struct dmm_ctx {
   int* aux_pinned = nullptr;               // pinned host words for flags read back on the second stream
   size_t aux_pinned_n = 0;
   int num_cu = 256;
-  std::map<int, dmm_fft_tables> fft;       // forward tables by nra
-  std::map<int, dmm_fft_tables> ifft;      // inverse tables by nra
+  std::map<int, dmm_fft_tables<float2>> fft_f32;   // row-FFT tables by nra: the single-precision forward m-mode transform
+  std::map<int, dmm_fft_tables<double2>> fft_f64;  // the float64 transforms (inverse m-mode, analytic beam, ring map)
   std::map<int64_t, void*> sht;            // SHT geometry caches keyed by (nside,lmax,mmax)
   int opt_dirty_variant = 0;               // tuning knobs, see dmm_ctx_set_option
   int opt_grid_mult = 0;
@@ -171,7 +172,33 @@ int dmm_set_error(int code, const char* fmt, ...);
     if (!(cond)) return dmm_set_error(DMM_E_ARG, __VA_ARGS__); \
   } while (0)
 
-int dmm_fft_tables_f64(dmm_ctx* ctx, int n, dmm_fft_tables** out);  // mfft.hip
+// mfft.hip: the plan of `ntrans` row transforms of length nra in precision T (float / double) -- tables fetched or built,
+// rows per block and LDS bytes chosen: RB = rb_max halved until the rows and the twiddles fit lds_target (and, `shrink_rb`,
+// while half as many rows still hold the whole batch); the twiddles are staged in LDS if and only if one row and they
+// fit lds_limit, and without them the plan exists only where `tw_fallback` lets the passes read them from memory.
+// *fits = false: no plan (one row does not fit; *lds = what it would take).
+namespace dmm_fft {
+template <typename T>
+struct RowFft;
+}
+struct dmm_fft_sizing {
+  int rb_max;
+  size_t lds_target, lds_limit;
+  bool tw_fallback, shrink_rb;
+};
+// (the sizing alone, a pure function of the FFT length M and the element size)
+void dmm_row_fft_sizes(int M, size_t elem, int64_t ntrans, const dmm_fft_sizing& sz, int* RB, int* P, int* tw_lds, size_t* lds, bool* fits);
+template <typename T>
+int dmm_row_fft_plan(dmm_ctx* ctx, int nra, int64_t ntrans, const dmm_fft_sizing& sz, dmm_fft::RowFft<T>* q, size_t* lds, bool* fits);
+// One block per RB rows: grid range check, dynamic-LDS attribute, launch, launch error.
+template <typename... P, typename... A>
+int dmm_launch_blocks(const char* who, void (*kern)(P...), int64_t nblk, int threads, size_t lds, hipStream_t stream, A... args) {
+  DMM_REQUIRE(nblk <= 0x7fffffff, "%s: too many rows", who);
+  DMM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(threads), lds, stream, args...);
+  DMM_HIP(hipGetLastError());
+  return DMM_OK;
+}
 // solve_dirty.hip, for the dense solvers: the Dirty kernel over a compact list of the plan's tiles.  `tiles_d` / `work_d` are
 // device arrays of nmat tiles and the nmat + 1 prefix sums of their column-block tasks (nwork = the last of them), as
 // dmm_dirty_tile_list fills them on the host from the tile numbers `ids`.

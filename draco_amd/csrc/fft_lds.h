@@ -1,9 +1,39 @@
-// Block-cooperative in-LDS FFT building blocks shared by the m-mode transform (mfft.hip)
-// and the SHT ring stage (sht.hip).  NT = threads of the calling block.
+// Block-cooperative in-LDS row FFTs shared by the m-mode transform (mfft.hip), the ring-map maker (ringmap.hip) and the
+// SHT ring stage (sht.hip).  What this file holds:
+//   RowFft<T>        the description of one batched row transform, filled on the host by dmm_row_fft_plan (mfft.hip);
+//   fft_dif / fft_dit, fft_dif8 / fft_dit8, bluestein_convolve   the passes over RB rows in LDS;
+//   stage_twiddles, row_fft_forward / row_fft_inverse, spectrum_at, inverse_slot   what a kernel does with a RowFft:
+//                    bring the twiddles in, run the transform, read bin k of a forward transform in natural order,
+//                    place input bin k of an inverse transform.
+// kThreads = threads of the calling block.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace dmm_fft {
+
+template <typename T>
+struct Vec2;
+template <>
+struct Vec2<float> {
+  using type = float2;
+};
+template <>
+struct Vec2<double> {
+  using type = double2;
+};
+
+// One batched row transform of length N in precision T: a block holds RB rows of pitch P in LDS (and, when `tw_lds`,
+// the M / 2 twiddles behind them) and runs an M-point FFT on each -- M = N for powers of two, else Bluestein's
+// chirp-z with M the power of two >= 2 N - 1 (`chirp` != nullptr says which).
+template <typename T>
+struct RowFft {
+  using T2 = typename Vec2<T>::type;
+  int N, M, logM, RB, P;
+  int tw_lds;       // twiddles staged in LDS (0: the passes read them from the table in memory)
+  const T2* tw;     // [M/2] exp(-2 pi i k / M)
+  const T2* chirp;  // [N]   exp(-i pi k^2 / N)                                  (Bluestein) or null
+  const T2* bfilt;  // [M]   FFT_M(conj chirp, wrapped) / M, bit-reversed order  (Bluestein) or null
+};
 
 template <typename T>
 struct C {
@@ -18,8 +48,41 @@ __device__ __forceinline__ C<T> cmulc(C<T> a, C<T> b) {  // a * conj(b)
   return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y};
 }
 
-
 // ---- block-cooperative in-LDS transforms over RB rows of length M (pitch P)
+// The span-1 stage (twiddle = 1): the last of a DIF, the first of a DIT with an odd number of stages left over.
+template <typename T, int kThreads>
+__device__ __forceinline__ void pass_span1(C<T>* buf, int RB, int M, int P) {
+  const int halfM = M >> 1;
+  for (int b = threadIdx.x; b < RB * halfM; b += kThreads) {
+    const int r = b / halfM, k = b - r * halfM;
+    C<T>* p = buf + r * P + 2 * k;
+    const C<T> a = p[0], c = p[1];
+    p[0] = {a.x + c.x, a.y + c.y};
+    p[1] = {a.x - c.x, a.y - c.y};
+  }
+  __syncthreads();
+}
+// The spans 2 and 1 as one radix-4 pass over groups of four: the last two stages of a DIF, or (DIT) the first two of a DIT --
+// the same butterfly with elements 1 and 2 of the group changing places on the way in and out (the 4-point bit reversal).
+template <typename T, bool DIT, bool CONJ, int kThreads>
+__device__ __forceinline__ void pass_span21(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int P) {
+  constexpr int i1 = DIT ? 2 : 1, i2 = DIT ? 1 : 2;
+  const int nq = M >> 2;
+  for (int b = threadIdx.x; b < RB * nq; b += kThreads) {
+    const int r = b / nq, q = b - r * nq;
+    C<T>* p = buf + r * P + 4 * q;
+    const C<T> e0 = p[0], e1 = p[i1], e2 = p[i2], e3 = p[3];
+    const C<T> wa1 = tw[1 << (logM - 2)];  // exp(-2 pi i / 4): the one non-trivial twiddle of the span-2 stage
+    const C<T> d = {e1.x - e3.x, e1.y - e3.y};
+    const C<T> a0 = {e0.x + e2.x, e0.y + e2.y}, a1 = {e1.x + e3.x, e1.y + e3.y};
+    const C<T> a2 = {e0.x - e2.x, e0.y - e2.y}, a3 = CONJ ? cmulc<T>(d, wa1) : cmul<T>(d, wa1);
+    p[0] = {a0.x + a1.x, a0.y + a1.y};
+    p[i1] = {a0.x - a1.x, a0.y - a1.y};
+    p[i2] = {a2.x + a3.x, a2.y + a3.y};
+    p[3] = {a2.x - a3.x, a2.y - a3.y};
+  }
+  __syncthreads();
+}
 // DIF: natural order in, bit-reversed order out, forward sign (tw = exp(-2 pi i k/M)).
 // Two radix-2 stages are fused per pass (4 elements in registers): half the LDS traffic and
 // half the barriers of a plain radix-2 loop, same data flow, so the output stays bit-reversed.
@@ -46,15 +109,7 @@ __device__ void fft_dif(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int 
     __syncthreads();
   }
   if (s == 0) {  // odd number of stages: last span-1 stage (twiddle = 1)
-    const int halfM = M >> 1;
-    for (int b = threadIdx.x; b < RB * halfM; b += kThreads) {
-      const int r = b / halfM, k = b - r * halfM;
-      C<T>* p = buf + r * P + 2 * k;
-      const C<T> a = p[0], c = p[1];
-      p[0] = {a.x + c.x, a.y + c.y};
-      p[1] = {a.x - c.x, a.y - c.y};
-    }
-    __syncthreads();
+    pass_span1<T, kThreads>(buf, RB, M, P);
   }
 }
 // DIT: bit-reversed order in, natural order out; CONJ selects exp(+2 pi i k/M).  Same pairing.
@@ -62,15 +117,7 @@ template <typename T, bool CONJ, int kThreads>
 __device__ void fft_dit(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int P) {
   int s = 0;
   if (logM & 1) {  // odd number of stages: first span-1 stage alone (twiddle = 1)
-    const int halfM = M >> 1;
-    for (int b = threadIdx.x; b < RB * halfM; b += kThreads) {
-      const int r = b / halfM, k = b - r * halfM;
-      C<T>* p = buf + r * P + 2 * k;
-      const C<T> a = p[0], c = p[1];
-      p[0] = {a.x + c.x, a.y + c.y};
-      p[1] = {a.x - c.x, a.y - c.y};
-    }
-    __syncthreads();
+    pass_span1<T, kThreads>(buf, RB, M, P);
     s = 1;
   }
   for (; s + 1 < logM; s += 2) {  // stages s (span quarter) then s+1 (span half)
@@ -147,30 +194,9 @@ __device__ void fft_dif8(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int
     __syncthreads();
   }
   if (s == 1) {  // two stages left (spans 2 and 1): one radix-4 pass
-    const int nq = M >> 2;
-    for (int b = threadIdx.x; b < RB * nq; b += kThreads) {
-      const int r = b / nq, q = b - r * nq;
-      C<T>* p = buf + r * P + 4 * q;
-      const C<T> e0 = p[0], e1 = p[1], e2 = p[2], e3 = p[3];
-      const C<T> wa1 = tw[1 << (logM - 2)];  // exp(-2 pi i / 4): the one non-trivial twiddle of the span-2 stage
-      const C<T> a0 = {e0.x + e2.x, e0.y + e2.y}, a1 = {e1.x + e3.x, e1.y + e3.y};
-      const C<T> a2 = {e0.x - e2.x, e0.y - e2.y}, a3 = cmul<T>({e1.x - e3.x, e1.y - e3.y}, wa1);
-      p[0] = {a0.x + a1.x, a0.y + a1.y};
-      p[1] = {a0.x - a1.x, a0.y - a1.y};
-      p[2] = {a2.x + a3.x, a2.y + a3.y};
-      p[3] = {a2.x - a3.x, a2.y - a3.y};
-    }
-    __syncthreads();
+    pass_span21<T, false, false, kThreads>(buf, tw, RB, M, logM, P);
   } else if (s == 0) {  // one stage left (span 1, twiddle 1)
-    const int halfM = M >> 1;
-    for (int b = threadIdx.x; b < RB * halfM; b += kThreads) {
-      const int r = b / halfM, k = b - r * halfM;
-      C<T>* p = buf + r * P + 2 * k;
-      const C<T> a = p[0], c = p[1];
-      p[0] = {a.x + c.x, a.y + c.y};
-      p[1] = {a.x - c.x, a.y - c.y};
-    }
-    __syncthreads();
+    pass_span1<T, kThreads>(buf, RB, M, P);
   }
 }
 
@@ -180,32 +206,10 @@ __device__ void fft_dit8(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int
   int s = 0;
   const int rem = logM % 3;
   if (rem == 1) {  // first the span-1 stage alone (twiddle 1)
-    const int halfM = M >> 1;
-    for (int b = threadIdx.x; b < RB * halfM; b += kThreads) {
-      const int r = b / halfM, k = b - r * halfM;
-      C<T>* p = buf + r * P + 2 * k;
-      const C<T> a = p[0], c = p[1];
-      p[0] = {a.x + c.x, a.y + c.y};
-      p[1] = {a.x - c.x, a.y - c.y};
-    }
-    __syncthreads();
+    pass_span1<T, kThreads>(buf, RB, M, P);
     s = 1;
   } else if (rem == 2) {  // first the spans 1 and 2 as one radix-4 pass
-    const int nq = M >> 2;
-    for (int b = threadIdx.x; b < RB * nq; b += kThreads) {
-      const int r = b / nq, q = b - r * nq;
-      C<T>* p = buf + r * P + 4 * q;
-      const C<T> e0 = p[0], e1 = p[1], e2 = p[2], e3 = p[3];
-      const C<T> wa1 = tw[1 << (logM - 2)];
-      const C<T> a0 = {e0.x + e1.x, e0.y + e1.y}, a1 = {e0.x - e1.x, e0.y - e1.y};
-      const C<T> a2 = {e2.x + e3.x, e2.y + e3.y}, a3 = {e2.x - e3.x, e2.y - e3.y};
-      const C<T> d3 = mul(a3, wa1);
-      p[0] = {a0.x + a2.x, a0.y + a2.y};
-      p[2] = {a0.x - a2.x, a0.y - a2.y};
-      p[1] = {a1.x + d3.x, a1.y + d3.y};
-      p[3] = {a1.x - d3.x, a1.y - d3.y};
-    }
-    __syncthreads();
+    pass_span21<T, true, CONJ, kThreads>(buf, tw, RB, M, logM, P);
     s = 2;
   }
   for (; s + 2 < logM; s += 3) {  // stages s (span e), s+1 (2 e), s+2 (4 e)
@@ -273,5 +277,42 @@ __device__ __forceinline__ void bluestein_convolve(C<T>* buf, const C<T>* tw, co
   else fft_dit<T, true, kThreads>(buf, tw, RB, M, logM, P);
 }
 
+// ---- a kernel's use of a RowFft.  The LDS image is q.RB rows of pitch q.P at `buf`, the staged twiddles at `tw_s` behind them.
+// `blue` is q.chirp != nullptr, handed in so that a kernel instantiated per kind passes its template constant.
+// Twiddles: staged in LDS (barrier left to the caller: every kernel fills its rows next), or the table in memory where the
+// plan says they do not fit.  FALLBACK = false for a kernel whose plan never reads them from memory: its passes then
+// address the LDS directly instead of through a pointer that may be either.
+template <typename T, int kThreads, bool FALLBACK>
+__device__ __forceinline__ const C<T>* stage_twiddles(const RowFft<T>& q, C<T>* tw_s) {
+  if (FALLBACK && !q.tw_lds) return reinterpret_cast<const C<T>*>(q.tw);
+  for (int k = threadIdx.x; k < (q.M >> 1); k += kThreads) {
+    const typename RowFft<T>::T2 w = q.tw[k];
+    tw_s[k] = {w.x, w.y};
+  }
+  return tw_s;
+}
+// Forward DFT_N of rows in natural order (Bluestein: already times the chirp, zero-padded to M); read with spectrum_at.
+template <typename T, int kThreads>
+__device__ __forceinline__ void row_fft_forward(const RowFft<T>& q, bool blue, C<T>* buf, const C<T>* tw) {
+  if (blue) bluestein_convolve<T, kThreads>(buf, tw, q.bfilt, q.RB, q.M, q.logM, q.P);
+  else fft_dif<T, kThreads>(buf, tw, q.RB, q.M, q.logM, q.P);
+}
+// The same sum over rows whose bin k was stored at inverse_slot(k) (Bluestein: times the chirp); natural order out, the
+// Bluestein result still to be multiplied by the chirp.  An inverse transform is conj(this(conj X)).
+template <typename T, int kThreads>
+__device__ __forceinline__ void row_fft_inverse(const RowFft<T>& q, bool blue, C<T>* buf, const C<T>* tw) {
+  if (blue) bluestein_convolve<T, kThreads>(buf, tw, q.bfilt, q.RB, q.M, q.logM, q.P);
+  else fft_dit<T, false, kThreads>(buf, tw, q.RB, q.M, q.logM, q.P);
+}
+__device__ __forceinline__ int inverse_slot(bool blue, int k, int logM) { return blue ? k : bitrev(k, logM); }
+// Bin k of a forward transform's row, natural order (`chirp`: the table in memory or a copy in LDS)
+template <typename T, typename TC>
+__device__ __forceinline__ C<T> spectrum_at(const C<T>* row, const TC* chirp, bool blue, int k, int logM) {
+  if (blue) {
+    const TC c = chirp[k];
+    return cmul<T>(row[k], {c.x, c.y});
+  }
+  return row[bitrev(k, logM)];
+}
 
 }  // namespace dmm_fft

@@ -1,5 +1,7 @@
-// m-mode transform kernels: batched sidereal-time <-> m FFT fused with the +/-m
-// pack / unpack, plus the noise-weight reduction.
+// m-mode transform kernels: batched sidereal-time <-> m FFT fused with the +/-m pack / unpack (k_mfft_pack,
+// k_mifft_unpack), the analytic transit beam generated into the same forward transform (k_beam_mfft), the noise-weight
+// reduction (k_mmode_weight) -- and the host side of every in-LDS row FFT of the library: the twiddle / chirp / filter
+// tables and the planner dmm_row_fft_plan (ringmap.hip plans its transforms through it too; the passes are in fft_lds.h).
 //
 // Replaces (reference radiocosmology/draco):
 //   _make_marray            draco/analysis/transform.py:644-705  -> k_mfft_pack
@@ -27,48 +29,54 @@
 
 namespace {
 
-using dmm_fft::bitrev;
 using dmm_fft::C;
 using dmm_fft::cmul;
-using dmm_fft::cmulc;
+using dmm_fft::RowFft;
 
 constexpr int kThreads = 1024;
+
+// The +/-m pack of a forward transform (transform.py:678-703): out[m, s, row], s = 0 the +m side, s = 1 the conjugated -m side
+struct PmPack {
+  int mmax, mlim, mlim_neg;  // slots m <= mmax; bins kept: +m up to mlim, -m up to mlim_neg (pm_pack_limits)
+};
+// Slot (m, s) of a row: bin k = m or N - m of its spectrum times inv_n (and mscale[m]), the -m side conjugated; zero in every slot the
+// reference leaves at its :623 zero fill.
 template <typename T>
-__device__ __forceinline__ void fft_dif(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int P) {
-  dmm_fft::fft_dif<T, kThreads>(buf, tw, RB, M, logM, P);
-}
-template <typename T, bool CONJ>
-__device__ __forceinline__ void fft_dit(C<T>* buf, const C<T>* tw, int RB, int M, int logM, int P) {
-  dmm_fft::fft_dit<T, CONJ, kThreads>(buf, tw, RB, M, logM, P);
+__device__ __forceinline__ void pm_pack_value(const RowFft<T>& q, bool blue, const dmm_fft::C<T>* row, const PmPack& pk, int m, int s,
+                                              double inv_n, const double* mscale, double& re, double& im) {
+  re = im = 0.0;
+  int k = -1;
+  if (s == 0 && m <= pk.mlim) k = m;
+  if (s == 1 && m >= 1 && m <= pk.mlim_neg) k = q.N - m;
+  if (k >= 0) {
+    const C<T> v = dmm_fft::spectrum_at<T>(row, q.chirp, blue, k, q.logM);
+    double sc = inv_n;
+    if (mscale) sc *= mscale[m];
+    re = (double)v.x * sc;
+    im = (s ? -(double)v.y : (double)v.y) * sc;
+  }
 }
 
 struct MfftParams {
   const float2* ts;
   int64_t nrow;
-  int N, M, logM, RB, P;
-  const float2* tw;     // [M/2]
-  const float2* chirp;  // [N]  (Bluestein) or null
-  const float2* bfilt;  // [M]  (Bluestein) or null
+  RowFft<float> fft;
   void* out;
   int out_c128;
-  int mmax, mlim, mlim_neg;
+  PmPack pk;
   const double* mscale;
 };
 
-// Forward: FFT RB rows in LDS, then pack +/-m (transform.py:678-703) straight into
-// out[m, s, row] with zeros in every slot the reference leaves at its :623 zero fill.
+// Forward: FFT RB rows in LDS, then pack +/-m straight into out[m, s, row].
 template <bool BLUESTEIN>
 __global__ __launch_bounds__(kThreads) void k_mfft_pack(MfftParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   C<float>* buf = reinterpret_cast<C<float>*>(smem);
-  C<float>* tw = buf + (size_t)p.RB * p.P;
-  const int N = p.N, M = p.M, RB = p.RB, P = p.P;
+  const RowFft<float>& q = p.fft;
+  const int N = q.N, M = q.M, RB = q.RB, P = q.P;
   const int64_t r0 = (int64_t)blockIdx.x * RB;
 
-  for (int k = threadIdx.x; k < (M >> 1); k += kThreads) {
-    const float2 w = p.tw[k];
-    tw[k] = {w.x, w.y};
-  }
+  const C<float>* tw = dmm_fft::stage_twiddles<float, kThreads, false>(q, buf + (size_t)RB * P);
   // coalesced row loads; rows past the end of the batch are zero
   if (!BLUESTEIN && (N & 1) == 0) {  // power of two: 16 bytes per lane
     const int n2 = N >> 1;
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_mfft_pack(MfftParams p) {
         const float2 x = p.ts[(r0 + r) * (int64_t)N + k];
         v = {x.x, x.y};
         if (BLUESTEIN) {
-          const float2 c = p.chirp[k];
+          const float2 c = q.chirp[k];
           v = cmul<float>(v, {c.x, c.y});
         }
       }
@@ -95,34 +103,17 @@ __global__ __launch_bounds__(kThreads) void k_mfft_pack(MfftParams p) {
     }
   }
   __syncthreads();
-  if (BLUESTEIN) dmm_fft::bluestein_convolve<float, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
-  else fft_dif<float>(buf, tw, RB, M, p.logM, P);
+  dmm_fft::row_fft_forward<float, kThreads>(q, BLUESTEIN, buf, tw);
 
   // pack: consecutive threads -> consecutive rows, so each (m, s) slot is one
   // RB*elem-byte contiguous store segment
   const double inv_n = 1.0 / (double)N;
-  const int nslot = (p.mmax + 1) * 2;
+  const int nslot = (p.pk.mmax + 1) * 2;
   for (int idx = threadIdx.x; idx < nslot * RB; idx += kThreads) {
     const int r = idx % RB, ms = idx / RB;
-    const int s = ms & 1, m = ms >> 1;
     if (r0 + r >= p.nrow) continue;
-    double re = 0.0, im = 0.0;
-    int k = -1;
-    if (s == 0 && m <= p.mlim) k = m;
-    if (s == 1 && m >= 1 && m <= p.mlim_neg) k = N - m;
-    if (k >= 0) {
-      C<float> v;
-      if (BLUESTEIN) {
-        const float2 c = p.chirp[k];
-        v = cmul<float>(buf[r * P + k], {c.x, c.y});
-      } else {
-        v = buf[r * P + bitrev(k, p.logM)];
-      }
-      double sc = inv_n;
-      if (p.mscale) sc *= p.mscale[m];
-      re = (double)v.x * sc;
-      im = (s ? -(double)v.y : (double)v.y) * sc;
-    }
+    double re, im;
+    pm_pack_value<float>(q, BLUESTEIN, buf + r * P, p.pk, ms >> 1, ms & 1, inv_n, p.mscale, re, im);
     const int64_t o = (int64_t)ms * p.nrow + r0 + r;
     if (p.out_c128) {  // written once, read by a later kernel
       __builtin_nontemporal_store(re, reinterpret_cast<double*>(p.out) + 2 * o);
@@ -136,18 +127,14 @@ __global__ __launch_bounds__(kThreads) void k_mfft_pack(MfftParams p) {
 struct BeamParams {
   int npol, nfreq, n_ew, nel;
   int64_t nrow;
-  int N, M, logM, RB, P;
-  const double2* tw;
-  const double2* chirp;
-  const double2* bfilt;
+  RowFft<double> fft;
   const double* freq;    // [nfreq] MHz
   const double* ew;      // [n_ew] m
   const double* dec;     // [nel] rad
   const double* coef_a;  // [npol] beam-width coefficient of the first / second feed of the pol pair
   const double* coef_b;
   float2* out;  // [mmax+1, 2, nrow]
-  int mmax, mlim, mlim_neg;
-  int tw_lds;
+  PmPack pk;
 };
 
 // Analytic transit beam (ringmapmaker.py:1019-1025,1046-1064), conjugated (:1066), generated straight into the LDS
@@ -156,17 +143,12 @@ template <bool BLUESTEIN>
 __global__ __launch_bounds__(kThreads) void k_beam_mfft(BeamParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   C<double>* buf = reinterpret_cast<C<double>*>(smem);
-  C<double>* tw_s = buf + (size_t)p.RB * p.P;
-  const C<double>* tw = p.tw_lds ? tw_s : reinterpret_cast<const C<double>*>(p.tw);
   __shared__ double s_u[16], s_is2[16];
-  const int N = p.N, M = p.M, RB = p.RB, P = p.P;
+  const RowFft<double>& q = p.fft;
+  const int N = q.N, M = q.M, RB = q.RB, P = q.P;
   const int64_t r0 = (int64_t)blockIdx.x * RB;
 
-  if (p.tw_lds)
-    for (int k = threadIdx.x; k < (M >> 1); k += kThreads) {
-      const double2 w = p.tw[k];
-      tw_s[k] = {w.x, w.y};
-    }
+  const C<double>* tw = dmm_fft::stage_twiddles<double, kThreads, true>(q, buf + (size_t)RB * P);
   if (threadIdx.x < RB && r0 + threadIdx.x < p.nrow) {
     int64_t r = r0 + threadIdx.x;
     const int el = (int)(r % p.nel);
@@ -195,36 +177,21 @@ __global__ __launch_bounds__(kThreads) void k_beam_mfft(BeamParams p) {
       sincos(2.0 * M_PI * s_u[r] * sin(phi), &sn, &cs);
       v = {amp * cs, -amp * sn};
       if (BLUESTEIN) {
-        const double2 c = p.chirp[k];
+        const double2 c = q.chirp[k];
         v = cmul<double>(v, {c.x, c.y});
       }
     }
     buf[r * P + k] = v;
   }
   __syncthreads();
-  if (BLUESTEIN) dmm_fft::bluestein_convolve<double, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
-  else fft_dif<double>(buf, tw, RB, M, p.logM, P);
+  dmm_fft::row_fft_forward<double, kThreads>(q, BLUESTEIN, buf, tw);
   const double inv_n = 1.0 / (double)N;
-  const int nslot = (p.mmax + 1) * 2;
+  const int nslot = (p.pk.mmax + 1) * 2;
   for (int idx = threadIdx.x; idx < nslot * RB; idx += kThreads) {
     const int r = idx % RB, ms = idx / RB;
-    const int s = ms & 1, m = ms >> 1;
     if (r0 + r >= p.nrow) continue;
-    double re = 0.0, im = 0.0;
-    int k = -1;
-    if (s == 0 && m <= p.mlim) k = m;
-    if (s == 1 && m >= 1 && m <= p.mlim_neg) k = N - m;
-    if (k >= 0) {
-      C<double> v;
-      if (BLUESTEIN) {
-        const double2 c = p.chirp[k];
-        v = cmul<double>(buf[r * P + k], {c.x, c.y});
-      } else {
-        v = buf[r * P + bitrev(k, p.logM)];
-      }
-      re = v.x * inv_n;
-      im = (s ? -v.y : v.y) * inv_n;
-    }
+    double re, im;
+    pm_pack_value<double>(q, BLUESTEIN, buf + r * P, p.pk, ms >> 1, ms & 1, inv_n, nullptr, re, im);
     p.out[(int64_t)ms * p.nrow + r0 + r] = make_float2((float)re, (float)im);
   }
 }
@@ -232,14 +199,10 @@ __global__ __launch_bounds__(kThreads) void k_beam_mfft(BeamParams p) {
 struct MifftParams {
   const double2* mvis;  // [n_m, 2, nrow]
   int64_t nrow;
-  int N, M, logM, RB, P;
-  const double2* tw;
-  const double2* chirp;
-  const double2* bfilt;
+  RowFft<double> fft;
   int mmax_plus, mmax_minus;
   const double* mscale;
   float2* out;  // [nrow, N]
-  int tw_lds;   // twiddles staged in LDS (0: read from the table in memory)
 };
 
 // Inverse: gather the +/-m slots into FFT order (transform.py:838-849), run
@@ -249,16 +212,11 @@ template <bool BLUESTEIN>
 __global__ __launch_bounds__(kThreads) void k_mifft_unpack(MifftParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   C<double>* buf = reinterpret_cast<C<double>*>(smem);
-  C<double>* tw_s = buf + (size_t)p.RB * p.P;
-  const C<double>* tw = p.tw_lds ? tw_s : reinterpret_cast<const C<double>*>(p.tw);
-  const int N = p.N, M = p.M, RB = p.RB, P = p.P;
+  const RowFft<double>& q = p.fft;
+  const int N = q.N, M = q.M, RB = q.RB, P = q.P;
   const int64_t r0 = (int64_t)blockIdx.x * RB;
 
-  if (p.tw_lds)
-    for (int k = threadIdx.x; k < (M >> 1); k += kThreads) {
-      const double2 w = p.tw[k];
-      tw_s[k] = {w.x, w.y};
-    }
+  const C<double>* tw = dmm_fft::stage_twiddles<double, kThreads, true>(q, buf + (size_t)RB * P);
   // transposed gather: consecutive threads -> consecutive rows of one (m, s) slot
   for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
     const int r = idx % RB, k = idx / RB;
@@ -280,22 +238,21 @@ __global__ __launch_bounds__(kThreads) void k_mifft_unpack(MifftParams p) {
         // X[k] = +m value, or conj(-m value); we load conj(X[k])
         v = {x.x * sc, (s ? x.y : -x.y) * sc};
         if (BLUESTEIN) {
-          const double2 c = p.chirp[k];
+          const double2 c = q.chirp[k];
           v = cmul<double>(v, {c.x, c.y});
         }
       }
     }
-    buf[r * P + (BLUESTEIN ? k : bitrev(k, p.logM))] = v;
+    buf[r * P + dmm_fft::inverse_slot(BLUESTEIN, k, q.logM)] = v;
   }
   __syncthreads();
-  if (BLUESTEIN) dmm_fft::bluestein_convolve<double, kThreads>(buf, tw, p.bfilt, RB, M, p.logM, P);
-  else fft_dit<double, false>(buf, tw, RB, M, p.logM, P);
+  dmm_fft::row_fft_inverse<double, kThreads>(q, BLUESTEIN, buf, tw);
   for (int idx = threadIdx.x; idx < RB * N; idx += kThreads) {
     const int r = idx / N, n = idx - r * N;
     if (r0 + r >= p.nrow) continue;
     C<double> v = buf[r * P + n];
     if (BLUESTEIN) {
-      const double2 c = p.chirp[n];
+      const double2 c = q.chirp[n];
       v = cmul<double>(v, {c.x, c.y});
     }
     p.out[(r0 + r) * (int64_t)N + n] = make_float2((float)v.x, (float)(-v.y));
@@ -373,11 +330,16 @@ int upload(const std::vector<T2>& h, T2** d) {
   return DMM_OK;
 }
 
+int host_bitrev(int i, int logM) {
+  int j = 0;
+  for (int b = 0; b < logM; ++b) j |= ((i >> b) & 1) << (logM - 1 - b);
+  return j;
+}
+
 void host_fft(std::vector<double>& re, std::vector<double>& im) {  // in-place radix-2, forward
   const int M = (int)re.size(), logM = ilog2(M);
   for (int i = 0; i < M; ++i) {
-    int j = 0;
-    for (int b = 0; b < logM; ++b) j |= ((i >> b) & 1) << (logM - 1 - b);
+    const int j = host_bitrev(i, logM);
     if (j > i) {
       std::swap(re[i], re[j]);
       std::swap(im[i], im[j]);
@@ -397,15 +359,19 @@ void host_fft(std::vector<double>& re, std::vector<double>& im) {  // in-place r
       }
 }
 
-// Build (or fetch) the tables for length n.  T2 = float2 (forward) / double2 (inverse).
-template <typename T2, typename T>
-int get_tables(std::map<int, dmm_fft_tables>& cache, int n, dmm_fft_tables** out) {
+std::map<int, dmm_fft_tables<float2>>& table_cache(dmm_ctx* ctx, float) { return ctx->fft_f32; }
+std::map<int, dmm_fft_tables<double2>>& table_cache(dmm_ctx* ctx, double) { return ctx->fft_f64; }
+
+// Build (or fetch) the tables for length n in precision T.
+template <typename T, typename T2 = typename dmm_fft::Vec2<T>::type>
+int get_tables(dmm_ctx* ctx, int n, const dmm_fft_tables<T2>** out) {
+  auto& cache = table_cache(ctx, T());
   auto it = cache.find(n);
   if (it != cache.end()) {
     *out = &it->second;
     return DMM_OK;
   }
-  dmm_fft_tables t;
+  dmm_fft_tables<T2> t;
   t.n = n;
   const bool pow2 = dmm_is_pow2(n);
   t.M = pow2 ? n : (1 << ilog2(2 * n - 1));
@@ -416,7 +382,7 @@ int get_tables(std::map<int, dmm_fft_tables>& cache, int n, dmm_fft_tables** out
     tw[k].x = (T)cos(a);
     tw[k].y = (T)sin(a);
   }
-  int rc = upload<T2>(tw, reinterpret_cast<T2**>(&t.tw));
+  int rc = upload<T2>(tw, &t.tw);
   if (rc) return rc;
   if (!pow2) {
     std::vector<T2> chirp(n);
@@ -436,14 +402,13 @@ int get_tables(std::map<int, dmm_fft_tables>& cache, int n, dmm_fft_tables** out
     host_fft(br, bi);
     std::vector<T2> bf(M);
     for (int pidx = 0; pidx < M; ++pidx) {
-      int j = 0;
-      for (int b = 0; b < logM; ++b) j |= ((pidx >> b) & 1) << (logM - 1 - b);
+      const int j = host_bitrev(pidx, logM);
       bf[pidx].x = (T)(br[j] / (double)M);
       bf[pidx].y = (T)(bi[j] / (double)M);
     }
-    rc = upload<T2>(chirp, reinterpret_cast<T2**>(&t.chirp));
+    rc = upload<T2>(chirp, &t.chirp);
     if (rc) return rc;
-    rc = upload<T2>(bf, reinterpret_cast<T2**>(&t.bfilt));
+    rc = upload<T2>(bf, &t.bfilt);
     if (rc) return rc;
   }
   auto ins = cache.emplace(n, t);
@@ -451,29 +416,51 @@ int get_tables(std::map<int, dmm_fft_tables>& cache, int n, dmm_fft_tables** out
   return DMM_OK;
 }
 
-// rows per block and LDS bytes for an M-point transform with elem-byte elements
-// tw_lds (optional): set to 0 when only the row fits the LDS and the twiddles have to be read from memory instead
-// (double-precision Bluestein transforms of 2049 ... 4096 points: M = 8192)
-bool choose_rb(int M, size_t elem, int64_t nrow, int* RB, int* P, size_t* lds, int* tw_lds = nullptr) {
-  const size_t tw = (size_t)(M / 2) * elem;
-  *P = M + 1;
-  int rb = 16;
-  while (rb > 1 && (size_t)rb * (*P) * elem + tw > 80 * 1024) rb >>= 1;
-  while (rb > 1 && rb / 2 >= nrow) rb >>= 1;
-  *lds = (size_t)rb * (*P) * elem + tw;
-  *RB = rb;
-  if (tw_lds) *tw_lds = 1;
-  if (*lds > 160 * 1024 && tw_lds && rb == 1 && (size_t)(*P) * elem <= 160 * 1024) {
-    *tw_lds = 0;
-    *lds = (size_t)(*P) * elem;
-  }
-  return *lds <= 160 * 1024;
+// Sizing of the m-mode transforms: up to 16 rows per block in about half the LDS, fewer for a batch that small
+constexpr size_t kLdsTarget = 80 * 1024, kLdsLimit = 160 * 1024;
+constexpr dmm_fft_sizing kSizeF32 = {16, kLdsTarget, kLdsLimit, false, true};
+// (the twiddles are read from memory by the double-precision Bluestein transforms of 2049 ... 4096 points: M = 8192)
+constexpr dmm_fft_sizing kSizeF64 = {16, kLdsTarget, kLdsLimit, true, true};
+
+PmPack pm_pack_limits(int nra, int mmax) {
+  PmPack pk;
+  pk.mmax = mmax;
+  pk.mlim = nra / 2 < mmax ? nra / 2 : mmax;                       // transform.py:678
+  pk.mlim_neg = (mmax >= nra / 2) ? nra / 2 - 1 + nra % 2 : mmax;  // transform.py:679
+  return pk;
 }
 
 }  // namespace
 
-// internal: double-precision tables (twiddles; chirp + filter for non powers of two) for length n
-int dmm_fft_tables_f64(dmm_ctx* ctx, int n, dmm_fft_tables** out) { return get_tables<double2, double>(ctx->ifft, n, out); }
+void dmm_row_fft_sizes(int M, size_t elem, int64_t ntrans, const dmm_fft_sizing& sz, int* RB, int* P, int* tw_lds, size_t* lds, bool* fits) {
+  *P = M + 1;
+  const size_t row = (size_t)(*P) * elem, tw = (size_t)(M / 2) * elem;
+  int rb = sz.rb_max;
+  while (rb > 1 && (size_t)rb * row + tw > sz.lds_target) rb >>= 1;
+  if (sz.shrink_rb)
+    while (rb > 1 && rb / 2 >= ntrans) rb >>= 1;
+  *RB = rb;
+  *tw_lds = row + tw <= sz.lds_limit;  // (if not, rb is 1: the target is below the limit)
+  *fits = *tw_lds || (sz.tw_fallback && row <= sz.lds_limit);
+  *lds = (size_t)rb * row + (*tw_lds || !*fits ? tw : 0);
+}
+
+template <typename T>
+int dmm_row_fft_plan(dmm_ctx* ctx, int nra, int64_t ntrans, const dmm_fft_sizing& sz, RowFft<T>* q, size_t* lds, bool* fits) {
+  const dmm_fft_tables<typename RowFft<T>::T2>* t = nullptr;
+  const int rc = get_tables<T>(ctx, nra, &t);
+  if (rc) return rc;
+  q->N = nra;
+  q->M = t->M;
+  q->logM = ilog2(t->M);
+  q->tw = t->tw;
+  q->chirp = t->chirp;
+  q->bfilt = t->bfilt;
+  dmm_row_fft_sizes(q->M, sizeof(typename RowFft<T>::T2), ntrans, sz, &q->RB, &q->P, &q->tw_lds, lds, fits);
+  return DMM_OK;
+}
+template int dmm_row_fft_plan<float>(dmm_ctx*, int, int64_t, const dmm_fft_sizing&, RowFft<float>*, size_t*, bool*);
+template int dmm_row_fft_plan<double>(dmm_ctx*, int, int64_t, const dmm_fft_sizing&, RowFft<double>*, size_t*, bool*);
 
 extern "C" {
 
@@ -486,37 +473,21 @@ int dmm_mfft_pack(dmm_ctx* ctx, const void* ts, int64_t nrow, int nra, void* out
               (long long)nrow, nra, mmax);
   DMM_REQUIRE(out_dtype == DMM_C64 || out_dtype == DMM_C128, "dmm_mfft_pack: bad out_dtype %d", out_dtype);
   if (nra > DMM_MAX_NRA) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mfft_pack: nra=%d > %d", nra, DMM_MAX_NRA);
-  if (nrow == 0) return DMM_OK;
   DMM_HIP(hipSetDevice(ctx->device));
-  dmm_fft_tables* t = nullptr;
-  int rc = get_tables<float2, float>(ctx->fft, nra, &t);
-  if (rc) return rc;
   MfftParams p;
+  size_t lds = 0;
+  bool fits = false;
+  const int rc = dmm_row_fft_plan<float>(ctx, nra, nrow, kSizeF32, &p.fft, &lds, &fits);
+  if (rc) return rc;
+  if (!fits) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mfft_pack: nra=%d needs %zu B of LDS", nra, lds);
   p.ts = (const float2*)ts;
   p.nrow = nrow;
-  p.N = nra;
-  p.M = t->M;
-  p.logM = ilog2(t->M);
-  size_t lds = 0;
-  if (!choose_rb(p.M, sizeof(float2), nrow, &p.RB, &p.P, &lds))
-    return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mfft_pack: nra=%d needs %zu B of LDS", nra, lds);
-  p.tw = t->tw;
-  p.chirp = t->chirp;
-  p.bfilt = t->bfilt;
   p.out = out;
   p.out_c128 = out_dtype == DMM_C128;
-  p.mmax = mmax;
-  p.mlim = nra / 2 < mmax ? nra / 2 : mmax;                         // transform.py:678
-  p.mlim_neg = (mmax >= nra / 2) ? nra / 2 - 1 + nra % 2 : mmax;    // transform.py:679
+  p.pk = pm_pack_limits(nra, mmax);
   p.mscale = mscale;
-  const int64_t nblk = (nrow + p.RB - 1) / p.RB;
-  DMM_REQUIRE(nblk <= 0x7fffffff, "dmm_mfft_pack: too many rows");
-  const bool blue = t->chirp != nullptr;
-  auto kern = blue ? k_mfft_pack<true> : k_mfft_pack<false>;
-  DMM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds, ctx->stream, p);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
+  return dmm_launch_blocks("dmm_mfft_pack", p.fft.chirp ? k_mfft_pack<true> : k_mfft_pack<false>, (nrow + p.fft.RB - 1) / p.fft.RB,
+                           kThreads, lds, ctx->stream, p);
 }
 
 int dmm_analytic_beam_mmodes(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int nra, int mmax, const double* freq,
@@ -529,33 +500,19 @@ int dmm_analytic_beam_mmodes(dmm_ctx* ctx, int npol, int nfreq, int new_, int ne
   DMM_REQUIRE(freq && ew && dec && coef_a && coef_b && out, "dmm_analytic_beam_mmodes: NULL argument");
   if (nra > DMM_MAX_NRA) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_analytic_beam_mmodes: nra=%d > %d", nra, DMM_MAX_NRA);
   DMM_HIP(hipSetDevice(ctx->device));
-  dmm_fft_tables* t = nullptr;
-  int rc = get_tables<double2, double>(ctx->ifft, nra, &t);
-  if (rc) return rc;
   BeamParams p;
+  size_t lds = 0;
+  bool fits = false;
+  const int rc = dmm_row_fft_plan<double>(ctx, nra, nrow, kSizeF64, &p.fft, &lds, &fits);
+  if (rc) return rc;
+  if (!fits) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_analytic_beam_mmodes: nra=%d needs %zu B of LDS", nra, lds);
   p.npol = npol, p.nfreq = nfreq, p.n_ew = new_, p.nel = nel;
   p.nrow = nrow;
-  p.N = nra;
-  p.M = t->M;
-  p.logM = ilog2(t->M);
-  size_t lds = 0;
-  if (!choose_rb(p.M, sizeof(double2), nrow, &p.RB, &p.P, &lds, &p.tw_lds))
-    return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_analytic_beam_mmodes: nra=%d needs %zu B of LDS", nra, lds);
-  p.tw = (const double2*)t->tw;
-  p.chirp = (const double2*)t->chirp;
-  p.bfilt = (const double2*)t->bfilt;
   p.freq = freq, p.ew = ew, p.dec = dec, p.coef_a = coef_a, p.coef_b = coef_b;
   p.out = (float2*)out;
-  p.mmax = mmax;
-  p.mlim = nra / 2 < mmax ? nra / 2 : mmax;
-  p.mlim_neg = (mmax >= nra / 2) ? nra / 2 - 1 + nra % 2 : mmax;
-  const int64_t nblk = (nrow + p.RB - 1) / p.RB;
-  DMM_REQUIRE(nblk <= 0x7fffffff, "dmm_analytic_beam_mmodes: too many rows");
-  auto kern = t->chirp ? k_beam_mfft<true> : k_beam_mfft<false>;
-  DMM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds, ctx->stream, p);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
+  p.pk = pm_pack_limits(nra, mmax);
+  return dmm_launch_blocks("dmm_analytic_beam_mmodes", p.fft.chirp ? k_beam_mfft<true> : k_beam_mfft<false>,
+                           (nrow + p.fft.RB - 1) / p.fft.RB, kThreads, lds, ctx->stream, p);
 }
 
 int dmm_mmode_weight(dmm_ctx* ctx, const float* weight, int64_t nrow, int nra, double* out, int mmax,
@@ -564,7 +521,6 @@ int dmm_mmode_weight(dmm_ctx* ctx, const float* weight, int64_t nrow, int nra, d
   if (nrow == 0) return DMM_OK;
   DMM_REQUIRE(weight && out, "dmm_mmode_weight: NULL argument");
   DMM_REQUIRE(nrow >= 0 && nra >= 1 && mmax >= 0, "dmm_mmode_weight: bad sizes");
-  if (nrow == 0) return DMM_OK;
   DMM_HIP(hipSetDevice(ctx->device));
   const int64_t nblk = (nrow + kWRows - 1) / kWRows;
   DMM_REQUIRE(nblk <= 0x7fffffff, "dmm_mmode_weight: too many rows");
@@ -587,35 +543,21 @@ int dmm_mifft_unpack(dmm_ctx* ctx, const void* mvis, int n_m, int64_t nrow, int 
   if (nra > DMM_MAX_NRA / 2 && !dmm_is_pow2(nra))
     return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mifft_unpack: non power-of-two nra=%d > %d", nra, DMM_MAX_NRA / 2);
   if (nra > DMM_MAX_NRA) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mifft_unpack: nra=%d > %d", nra, DMM_MAX_NRA);
-  if (nrow == 0) return DMM_OK;
   DMM_HIP(hipSetDevice(ctx->device));
-  dmm_fft_tables* t = nullptr;
-  int rc = get_tables<double2, double>(ctx->ifft, nra, &t);
-  if (rc) return rc;
   MifftParams p;
+  size_t lds = 0;
+  bool fits = false;
+  const int rc = dmm_row_fft_plan<double>(ctx, nra, nrow, kSizeF64, &p.fft, &lds, &fits);
+  if (rc) return rc;
+  if (!fits) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mifft_unpack: nra=%d needs %zu B of LDS", nra, lds);
   p.mvis = (const double2*)mvis;
   p.nrow = nrow;
-  p.N = nra;
-  p.M = t->M;
-  p.logM = ilog2(t->M);
-  size_t lds = 0;
-  if (!choose_rb(p.M, sizeof(double2), nrow, &p.RB, &p.P, &lds, &p.tw_lds))
-    return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_mifft_unpack: nra=%d needs %zu B of LDS", nra, lds);
-  p.tw = (const double2*)t->tw;
-  p.chirp = (const double2*)t->chirp;
-  p.bfilt = (const double2*)t->bfilt;
   p.mmax_plus = mmax_plus;
   p.mmax_minus = mmax_minus;
   p.mscale = mscale;
   p.out = (float2*)vis_out;
-  const int64_t nblk = (nrow + p.RB - 1) / p.RB;
-  DMM_REQUIRE(nblk <= 0x7fffffff, "dmm_mifft_unpack: too many rows");
-  const bool blue = t->chirp != nullptr;
-  auto kern = blue ? k_mifft_unpack<true> : k_mifft_unpack<false>;
-  DMM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds, ctx->stream, p);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
+  return dmm_launch_blocks("dmm_mifft_unpack", p.fft.chirp ? k_mifft_unpack<true> : k_mifft_unpack<false>,
+                           (nrow + p.fft.RB - 1) / p.fft.RB, kThreads, lds, ctx->stream, p);
 }
 
 int dmm_mrow_is_zero(dmm_ctx* ctx, const void* mvis, int n_m, int64_t nrow, int m, int sign, int* is_zero) {
@@ -641,135 +583,3 @@ int dmm_mrow_is_zero(dmm_ctx* ctx, const void* mvis, int n_m, int64_t nrow, int 
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------ MaskMModeData
-// Zero m-mode noise weights ahead of map-making (reference draco/analysis/flagging.py:113-173):
-// auto-correlations, m = 0, one sign of m, m below a threshold.  weight [n_m, 2, nfreq, nstack].
-namespace {
-__global__ void k_mask_mmode(double* __restrict__ w, int n_m, int64_t nfreq, int nstack,
-                             const unsigned char* __restrict__ is_auto, int m_zero, int positive_m, int negative_m,
-                             int mask_low_m) {
-  const int64_t per_ms = nfreq * nstack, total = (int64_t)n_m * 2 * per_ms;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t ms = i / per_ms;
-    const int m = (int)(ms >> 1), s = (int)(ms & 1);
-    const int p = (int)(i % nstack);
-    bool kill = false;
-    if (is_auto && is_auto[p]) kill = true;
-    if (!m_zero && m == 0) kill = true;
-    if (!positive_m && m >= 1 && s == 0) kill = true;
-    if (!negative_m && m >= 1 && s == 1) kill = true;
-    if (m < mask_low_m) kill = true;
-    if (kill) w[i] = 0.0;
-  }
-}
-}  // namespace
-
-extern "C" int dmm_mask_mmode_weight(dmm_ctx* ctx, double* mweight, int n_m, int64_t nfreq, int nstack,
-                                     const unsigned char* is_auto, int m_zero, int positive_m, int negative_m,
-                                     int mask_low_m) {
-  DMM_REQUIRE(ctx != nullptr, "dmm_mask_mmode_weight: ctx is NULL");
-  DMM_REQUIRE(n_m >= 0 && nfreq >= 0 && nstack >= 0 && mask_low_m >= 0, "dmm_mask_mmode_weight: bad sizes");
-  const int64_t total = (int64_t)n_m * 2 * nfreq * nstack;
-  if (total == 0) return DMM_OK;
-  DMM_REQUIRE(mweight != nullptr, "dmm_mask_mmode_weight: NULL argument");
-  DMM_HIP(hipSetDevice(ctx->device));
-  int64_t nb = (total + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(k_mask_mmode, dim3((unsigned)nb), dim3(256), 0, ctx->stream, mweight, n_m, nfreq, nstack, is_auto,
-                     m_zero, positive_m, negative_m, mask_low_m);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
-}
-
-// ------------------------------------------------------------------ CollateProducts
-// Weighted stacking of correlation products into the telescope's unique baselines
-// (reference draco/analysis/transform.py:277-320).  The reference scatters product by product
-// into the output; here the host inverts the map once (CSR: output baseline -> contributing
-// input products) so every output sample is one thread's deterministic gather, no atomics.
-namespace {
-__global__ void k_collate(const float2* __restrict__ ssv, const float* __restrict__ ssw, int nprod_in, int nt,
-                          int nf_out, const int* __restrict__ freq_ind, int nstack_out,
-                          const int* __restrict__ csr_ptr, const int* __restrict__ csr_src,
-                          const unsigned char* __restrict__ csr_conj, const float* __restrict__ red,
-                          float2* __restrict__ out_vis, float* __restrict__ out_w) {
-  const int64_t total = (int64_t)nf_out * nstack_out * nt;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int t = (int)(i % nt);
-    const int sp = (int)((i / nt) % nstack_out);
-    const int fo = (int)(i / ((int64_t)nt * nstack_out));
-    const int64_t fbase = (int64_t)freq_ind[fo] * nprod_in;
-    double vr = 0.0, vi = 0.0, var = 0.0, cnt = 0.0;
-    for (int e = csr_ptr[sp]; e < csr_ptr[sp + 1]; ++e) {
-      const int pi = csr_src[e];
-      const int64_t o = (fbase + pi) * nt + t;
-      const double w = (double)ssw[o];
-      const double wss = red ? (w > 0.0 ? (double)red[(int64_t)pi * nt + t] : 0.0) : w;  // transform.py:297-301
-      const float2 v = ssv[o];
-      vr += wss * (double)v.x;
-      vi += wss * (csr_conj[e] ? -(double)v.y : (double)v.y);
-      var += w != 0.0 ? wss * wss / w : 0.0;
-      cnt += wss;
-    }
-    const double ic = cnt != 0.0 ? 1.0 / cnt : 0.0;
-    out_vis[i] = make_float2((float)(vr * ic), (float)(vi * ic));
-    out_w[i] = (float)(var != 0.0 ? cnt * cnt / var : 0.0);
-  }
-}
-
-// ExpandProducts (reference synthesis/stream.py:228-244): out[f, p, t] = (conj?) in[f, src[p], t], weight 1; products
-// of a masked pair (src < 0) stay zero with zero weight.  One thread per output sample, t fastest.
-__global__ void k_expand(const float2* __restrict__ in, int nstack, int nt, int nprod, const int* __restrict__ src,
-                         const unsigned char* __restrict__ cj, float2* __restrict__ out, float* __restrict__ out_w,
-                         int64_t total) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int t = (int)(i % nt);
-    const int64_t fp = i / nt;
-    const int p = (int)(fp % nprod);
-    const int64_t f = fp / nprod;
-    const int sp = src[p];
-    float2 v = make_float2(0.f, 0.f);
-    if (sp >= 0) {
-      v = in[(f * nstack + sp) * nt + t];
-      if (cj[p]) v.y = -v.y;
-    }
-    out[i] = v;
-    out_w[i] = sp >= 0 ? 1.f : 0.f;
-  }
-}
-}  // namespace
-
-extern "C" int dmm_collate_products(dmm_ctx* ctx, const void* ssv, const float* ssw, int nf_in, int nprod_in, int nt,
-                                    int nf_out, const int* freq_ind, int nstack_out, const int* csr_ptr,
-                                    const int* csr_src, const unsigned char* csr_conj, const float* red,
-                                    void* out_vis, float* out_w) {
-  DMM_REQUIRE(ctx != nullptr, "dmm_collate_products: ctx is NULL");
-  DMM_REQUIRE(nf_in >= 0 && nprod_in >= 0 && nt >= 0 && nf_out >= 0 && nstack_out >= 0, "dmm_collate_products: bad sizes");
-  const int64_t total = (int64_t)nf_out * nstack_out * nt;
-  if (total == 0) return DMM_OK;
-  DMM_REQUIRE(ssv && ssw && freq_ind && csr_ptr && out_vis && out_w, "dmm_collate_products: NULL argument");
-  DMM_HIP(hipSetDevice(ctx->device));
-  int64_t nb = (total + 255) / 256;
-  if (nb > 16384) nb = 16384;
-  hipLaunchKernelGGL(k_collate, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const float2*)ssv, ssw, nprod_in, nt, nf_out,
-                     freq_ind, nstack_out, csr_ptr, csr_src, csr_conj, red, (float2*)out_vis, out_w);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
-}
-
-extern "C" int dmm_expand_products(dmm_ctx* ctx, const void* vis_in, int nfreq, int nstack, int nt, int nprod,
-                                   const int* src, const unsigned char* conj, void* out_vis, float* out_w) {
-  DMM_REQUIRE(ctx != nullptr, "dmm_expand_products: ctx is NULL");
-  DMM_REQUIRE(nfreq >= 0 && nstack >= 0 && nt >= 0 && nprod >= 0, "dmm_expand_products: bad sizes");
-  const int64_t total = (int64_t)nfreq * nprod * nt;
-  if (total == 0) return DMM_OK;
-  DMM_REQUIRE(vis_in && src && conj && out_vis && out_w, "dmm_expand_products: NULL argument");
-  DMM_HIP(hipSetDevice(ctx->device));
-  int64_t nb = (total + 255) / 256;
-  if (nb > 16384) nb = 16384;
-  hipLaunchKernelGGL(k_expand, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const float2*)vis_in, nstack, nt, nprod, src, conj,
-                     (float2*)out_vis, out_w, total);
-  DMM_HIP(hipGetLastError());
-  return DMM_OK;
-}

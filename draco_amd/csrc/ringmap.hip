@@ -217,12 +217,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
   }
 }
 
-struct RmFft {
-  int M, logM, RB, P, blue, tw_in_lds;
-  const double2* tw;
-  const double2* chirp;
-  const double2* bfilt;
-};
+using RmFft = dmm_fft::RowFft<double>;  // the inverse transform of length nra (dmm_row_fft_plan)
 
 // Hermitian extension to N bins of a row's map modes (complex) or dirty-beam modes (real, `d` only): what
 // np.fft.irfft(x, n=N) transforms.  Bins 1..half are plain, N/2 (even N) is the real Nyquist bin.
@@ -246,13 +241,11 @@ template <int PAIR>
 __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   extern __shared__ __align__(16) unsigned char smem[];
   C<double>* buf = reinterpret_cast<C<double>*>(smem);
-  C<double>* twl = buf + (size_t)q.RB * q.P;
-  const C<double>* tw = q.tw_in_lds ? twl : reinterpret_cast<const C<double>*>(q.tw);
+  const bool blue = q.chirp != nullptr;
   const int N = p.nra, M = q.M, RB = q.RB, P = q.P;
   const int64_t nrow = (int64_t)p.npol * p.nfreq * p.nel;
   const int64_t t0 = (int64_t)blockIdx.x * RB;  // first transform of the block; transform t holds rows PAIR t (, +1)
-  if (q.tw_in_lds)
-    for (int k = threadIdx.x; k < (M >> 1); k += kThreads) twl[k] = {q.tw[k].x, q.tw[k].y};
+  const C<double>* tw = dmm_fft::stage_twiddles<double, kThreads, true>(q, buf + (size_t)RB * P);
   const int half = (N - 1) / 2;
   for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
     const int r = idx / M, k = idx - r * M;
@@ -268,12 +261,12 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
       }
       // z = A + i B = (ar - bi) + i (ai + br); we load conj(z)
       v = {ar - bi, -(ai + br)};
-      if (q.blue) v = dmm_fft::cmul<double>(v, {q.chirp[k].x, q.chirp[k].y});
+      if (blue) v = dmm_fft::cmul<double>(v, {q.chirp[k].x, q.chirp[k].y});
     }
-    buf[r * P + (q.blue ? k : dmm_fft::bitrev(k, q.logM))] = v;
+    buf[r * P + dmm_fft::inverse_slot(blue, k, q.logM)] = v;
   }
   __syncthreads();
-  if (q.blue) {
+  if (blue) {
     // (not dmm_fft::bluestein_convolve: spelt this way the compiler fuses the OTHER product of the filter multiply's
     // imaginary part -- fma(a.y, f.x, a.x f.y), the helper's call sites fma(f.y, a.x, f.x a.y) -- and moving over would
     // change the last bit of every Bluestein ring map)
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
     __syncthreads();
     dmm_fft::fft_dit<double, true, kThreads>(buf, tw, RB, M, q.logM, P);
   } else {
-    dmm_fft::fft_dit<double, false, kThreads>(buf, tw, RB, M, q.logM, P);
+    dmm_fft::row_fft_inverse<double, kThreads>(q, false, buf, tw);
   }
   // finish: y = conj(result) / N; first output = Re y, second = Im y, each times its row's normalisation
   __shared__ double red[kThreads];
@@ -322,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
     double pw = 0.0;
     for (int n = threadIdx.x; n < N; n += kThreads) {
       C<double> v = buf[r * P + n];
-      if (q.blue) v = dmm_fft::cmul<double>(v, {q.chirp[n].x, q.chirp[n].y});
+      if (blue) v = dmm_fft::cmul<double>(v, {q.chirp[n].x, q.chirp[n].y});
       p.tmp_map[row0 * N + n] = v.x * sc0;
       if (PAIR == 2) {
         if (row0 + 1 < nrow) p.tmp_map[(row0 + 1) * N + n] = -v.y * sc1;
@@ -400,6 +393,7 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, in
   const int el = el0 + eli;
   const bool el_ok = el < p.nel;
   const int elc = el_ok ? el : p.nel - 1;
+  // (not dmm_fft::stage_twiddles: with it the allocator takes <16, true> from 117 registers to 128 and 12 bytes of scratch)
   for (int k = threadIdx.x; k < (M >> 1); k += kFuThreads) twl[k] = {q.tw[k].x, q.tw[k].y};
   const int nterm = 2 * p.new_;
   double acc_d = 0.0, acc_q = 0.0, acc_p = 0.0;
@@ -588,24 +582,16 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   DMM_REQUIRE(weight_mode >= 0 && weight_mode <= 2, "dmm_ringmap_deconvolve: bad weight_mode %d", weight_mode);
   DMM_REQUIRE(!skip_deconvolution || (iref >= 0 && iref < nel), "dmm_ringmap_deconvolve: iref out of range");
   DMM_HIP(hipSetDevice(ctx->device));
-  dmm_fft_tables* t = nullptr;
-  int rc = dmm_fft_tables_f64(ctx, nra, &t);
-  if (rc) return rc;
+  // the three-kernel form's transforms: up to 8 per block in 72 KB of LDS, twiddles from memory where a row leaves no room
+  constexpr size_t kLdsLimit = 150 * 1024;
+  const int64_t nrow = (int64_t)npol * nfreq * nel, ntrans = dirty_beam ? nrow : (nrow + 1) / 2;  // (two rows per transform)
   RmFft q;
-  q.M = t->M;
-  q.logM = ilog2(t->M);
-  q.blue = t->chirp != nullptr;
-  q.tw = (const double2*)t->tw;
-  q.chirp = (const double2*)t->chirp;
-  q.bfilt = (const double2*)t->bfilt;
-  q.P = q.M + 1;
-  const size_t row_b = (size_t)q.P * sizeof(double2), tw_b = (size_t)(q.M / 2) * sizeof(double2);
-  q.tw_in_lds = row_b + tw_b <= 150 * 1024;
-  if (row_b > 150 * 1024) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_ringmap_deconvolve: nra=%d too long for the in-LDS FFT", nra);
-  int rb = 8;
-  while (rb > 1 && rb * row_b + (q.tw_in_lds ? tw_b : 0) > 72 * 1024) rb >>= 1;
-  q.RB = rb;
-  const size_t lds = rb * row_b + (q.tw_in_lds ? tw_b : 0);
+  size_t lds = 0;
+  bool fits = false;
+  int rc = dmm_row_fft_plan<double>(ctx, nra, ntrans, {8, 72 * 1024, kLdsLimit, true, false}, &q, &lds, &fits);
+  if (rc) return rc;
+  if (!fits) return dmm_set_error(DMM_E_UNSUPPORTED, "dmm_ringmap_deconvolve: nra=%d too long for the in-LDS FFT", nra);
+  const size_t tw_b = (size_t)(q.M / 2) * sizeof(double2);
 
   RmParams p;
   p.nm = nm;
@@ -634,8 +620,8 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   const size_t lds16 = (size_t)8 * q.P * sizeof(double2) + tw_b;  // all sixteen elevations' image in the LDS?
   const int64_t ntile16 = (int64_t)((nel + 15) / 16) * npol * nfreq;
   const size_t park_bytes = (size_t)ntile16 * 4 * nra * sizeof(double2);
-  const bool single_ok = !dirty_beam && !skip_deconvolution && !q.blue && nra >= 8 && fused_lds <= 150 * 1024;
-  const RmForm form = single_ok ? rm_single_pass_form(lds16 <= 150 * 1024, park_bytes, ctx->opt_ringmap_variant) : kRmThreeKernel;
+  const bool single_ok = !dirty_beam && !skip_deconvolution && !q.chirp && nra >= 8 && fused_lds <= kLdsLimit;
+  const RmForm form = single_ok ? rm_single_pass_form(lds16 <= kLdsLimit, park_bytes, ctx->opt_ringmap_variant) : kRmThreeKernel;
   if (form != kRmThreeKernel) {
     const int el_blk = form == kRmSingle8 ? 8 : 16;
     const int ntile_el = (nel + el_blk - 1) / el_blk;
@@ -643,24 +629,18 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
     void* park = nullptr;
     switch (form) {
       case kRmSingle8:  // (the grid in whole groups of 16 ids: the XCD pairing of the tiles)
-        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-        hipLaunchKernelGGL((k_rm_fused<8, false>), dim3((unsigned)((ntile + 15) / 16 * 16)), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el, (double2*)nullptr);
-        break;
+        return dmm_launch_blocks("dmm_ringmap_deconvolve", k_rm_fused<8, false>, (ntile + 15) / 16 * 16, kFuThreads, fused_lds, ctx->stream, p, q,
+                                 ntile_el, (double2*)nullptr);
       case kRmSingle16:
-        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-        hipLaunchKernelGGL((k_rm_fused<16, false>), dim3((unsigned)ntile), dim3(kFuThreads), lds16, ctx->stream, p, q, ntile_el, (double2*)nullptr);
-        break;
+        return dmm_launch_blocks("dmm_ringmap_deconvolve", k_rm_fused<16, false>, ntile, kFuThreads, lds16, ctx->stream, p, q, ntile_el,
+                                 (double2*)nullptr);
       default:  // kRmSingle16Parked
         rc = dmm_get_scratch(ctx, park_bytes + 256, &park);
         if (rc) return rc;
-        DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fused<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-        hipLaunchKernelGGL((k_rm_fused<16, true>), dim3((unsigned)ntile), dim3(kFuThreads), fused_lds, ctx->stream, p, q, ntile_el, (double2*)park);
-        break;
+        return dmm_launch_blocks("dmm_ringmap_deconvolve", k_rm_fused<16, true>, ntile, kFuThreads, fused_lds, ctx->stream, p, q, ntile_el,
+                                 (double2*)park);
     }
-    DMM_HIP(hipGetLastError());
-    return DMM_OK;
   }
-  const int64_t nrow = (int64_t)npol * nfreq * nel;
   const int nchunk = (nm + MT - 1) / MT;
   const size_t b_map = (size_t)nrow * nm * sizeof(double2);
   const size_t b_dirty = ((size_t)nrow * nm * sizeof(double) + 255) / 256 * 256;
@@ -687,14 +667,9 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   // (two elevations per lane with 16-byte loads were tried: 715 instead of 630 us for this kernel at the CHIME-like
   // shape -- half as many resident waves; the kernel is latency bound on its 16 loads per m)
   hipLaunchKernelGGL(k_rm_reduce<1>, dim3((nel + 63) / 64, nchunk, npol * nfreq), dim3(kThreads), 0, ctx->stream, p);
-  if (dirty_beam) {
-    DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fft<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_rm_fft<1>, dim3((unsigned)((nrow + rb - 1) / rb)), dim3(kThreads), lds, ctx->stream, p, q);
-  } else {
-    const int64_t ntrans = (nrow + 1) / 2;
-    DMM_HIP(hipFuncSetAttribute((const void*)k_rm_fft<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_rm_fft<2>, dim3((unsigned)((ntrans + rb - 1) / rb)), dim3(kThreads), lds, ctx->stream, p, q);
-  }
+  rc = dmm_launch_blocks("dmm_ringmap_deconvolve", dirty_beam ? k_rm_fft<1> : k_rm_fft<2>, (ntrans + q.RB - 1) / q.RB, kThreads, lds,
+                         ctx->stream, p, q);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_rm_store, dim3((nra + 31) / 32, (nel + 31) / 32, npol * nfreq), dim3(kThreads), 0, ctx->stream, p);
   DMM_HIP(hipGetLastError());
   return DMM_OK;

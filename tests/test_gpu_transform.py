@@ -256,3 +256,25 @@ def test_weight_reduction_all_load_store_forms(nrow, nra, mmax, window):
     assert out.shape == ref.shape
     np.testing.assert_allclose(out, ref, rtol=1e-13, atol=0)
     assert np.all(out[:, :, nrow // 2] == 0)
+
+
+@pytest.mark.parametrize("N,mmax,nrow,window", [(64, 32, 37, True), (15, 7, 21, True), (127, 80, 7, False), (8, 4, 1, False)])
+def test_forward_complex64_store_is_complex128_rounded_once(N, mmax, nrow, window):
+    """`k_mfft_pack` forms every (m, +/-) value in float64 (bin / N, times the window's scale) and stores it as two doubles or
+    rounds it to ``float2``: the complex64 output is bit for bit the complex128 output rounded once.  Both transform kinds
+    (radix passes, Bluestein), a partial last block, a one-row batch, ``mmax`` past N / 2, and the window's scale on the
+    complex64 store.  Tolerance zero by construction."""
+    import torch
+
+    from draco_amd.analysis.transform import mmode_forward
+    from draco_amd.device import Context
+
+    ctx = Context.get()
+    rng = np.random.default_rng(N * 1009 + nrow)
+    vis = (rng.standard_normal((nrow, N)) + 1j * rng.standard_normal((nrow, N))).astype(np.complex64)
+    vis_d = torch.from_numpy(vis).to(ctx.device)
+    mv128, _ = mmode_forward(ctx, vis_d, None, mmax, remove_integration_window=window, vis_dtype=np.complex128)
+    mv64, _ = mmode_forward(ctx, vis_d, None, mmax, remove_integration_window=window, vis_dtype=np.complex64)
+    assert mv128.dtype == torch.complex128 and mv64.dtype == torch.complex64
+    assert mv64.shape == mv128.shape == (mmax + 1, 2, nrow)
+    assert torch.equal(mv64, mv128.to(torch.complex64))
