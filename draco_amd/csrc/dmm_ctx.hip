@@ -173,6 +173,7 @@ int dmm_ctx_get_counter(dmm_ctx* c, const char* name, int64_t* value) {
     *value = 0;
 #endif
   }
+  else if (!strcmp(name, "opt_ml_eigen")) *value = c->opt_ml_eigen;  // (the option's current value: a run never changes it)
   else if (!strcmp(name, "opt_sht_synth_form")) *value = c->opt_sht_synth_form;  // (the option's current value: callers that set it around a call restore it)
   else if (!strncmp(name, "prof_", 5)) {
     const size_t len = strlen(name);

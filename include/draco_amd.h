@@ -90,7 +90,7 @@ int dmm_ctx_sync(dmm_ctx* ctx);
  *  "profile" (1: HIP-event timing of the dense solvers' kernel classes, sums cleared; 0 off).
  * Bits of "sht_variant" other than 2, 3, 6 and 7 selected A/B forms that are gone: setting them is accepted and ignored. */
 int dmm_ctx_set_option(dmm_ctx* ctx, const char* name, int64_t value);
-/* diagnostics counters, cumulative per context ("opt_sht_synth_form": that option's current value): "ml_tiles_direct" (tiles whose pseudo-inverse was
+/* diagnostics counters, cumulative per context ("opt_sht_synth_form", "opt_ml_eigen": that option's current value): "ml_tiles_direct" (tiles whose pseudo-inverse was
  * certified to cut no mode and solved by Cholesky), "ml_tiles_eigen" (tiles eigen-decomposed), "ml_tiles_null" (tiles answered with zero by the null certificate: every
  * singular value at or below acond), "ml_tiles_stopped" / "ml_stop_cols" (eigen-decomposed tiles whose reduction the rank stop cut off,
  * and the sum of their effective orders), "ml_gram_flops" / "ml_band_bytes" (useful flops 4 k^2 K of the

@@ -181,21 +181,21 @@ def _counter(ctx, name):
     return int(v.value)
 
 
-def test_ml_certified_shortcut_vs_eigen_path():
-    """ML: the certified full-rank shortcut (Cholesky on the smaller Gram matrix, telescope or sky side)
-    against the eigen-decomposition path on the same tiles, and both against the oracle.
+_SHORTCUT_CASE = {}
+
+
+def _shortcut_case():
+    """Telescope, tiles, m-modes and the oracle's solution of `test_ml_certified_shortcut_vs_eigen_path` (built once).
 
     ntel = 86, nsky_m = 4 (61 - m): m <= 39 solve on the telescope side, m >= 40 on the sky side;
     10 % of the weights are zero (pinned rows) and two (m, f) have a rank-deficient B (equal rows,
     equal columns, a zero column) so that their certificates must fail and the eigen path run.
     """
-    from draco_amd import _lib
-    from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
+    if _SHORTCUT_CASE:
+        return _SHORTCUT_CASE
     from draco_amd.core import containers
     from draco_amd.core.products import ArrayProvider
-    from draco_amd.device import Context
 
-    ctx = Context.get()
     nfreq, lmax = 2, 60
     tel = _tel(nfreq, lmax, 2, 4)
     assert 2 * tel.npairs == 86
@@ -210,7 +210,6 @@ def test_ml_certified_shortcut_vs_eigen_path():
             b[:, :, :, m + 2] = b[:, :, :, m + 3]
         return b
 
-    bt = ArrayProvider(tel, beam)
     rng = np.random.default_rng(9)
     mv = rng.standard_normal((lmax + 1, 2, nfreq, tel.npairs)) + 1j * rng.standard_normal((lmax + 1, 2, nfreq, tel.npairs))
     mw = rng.uniform(0.5, 1.5, mv.shape) * 30.0
@@ -219,6 +218,20 @@ def test_ml_certified_shortcut_vs_eigen_path():
     mm.vis[:] = mv
     mm.weight[:] = mw
     ref = omm.solve_alm("ml", beam, mv, mw, lmax, tel.mmax, list(range(nfreq)))
+    _SHORTCUT_CASE.update(nfreq=nfreq, lmax=lmax, tel=tel, bt=ArrayProvider(tel, beam), mm=mm, ref=ref)
+    return _SHORTCUT_CASE
+
+
+def test_ml_certified_shortcut_vs_eigen_path():
+    """ML: the certified full-rank shortcut (Cholesky on the smaller Gram matrix, telescope or sky side)
+    against the eigen-decomposition path on the same tiles, and both against the oracle (`_shortcut_case`)."""
+    from draco_amd import _lib
+    from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
+    from draco_amd.device import Context
+
+    ctx = Context.get()
+    case = _shortcut_case()
+    nfreq, lmax, bt, mm, ref = case["nfreq"], case["lmax"], case["bt"], case["mm"], case["ref"]
     out = {}
     stats = {}
     try:
@@ -238,6 +251,57 @@ def test_ml_certified_shortcut_vs_eigen_path():
     for mode in (0, 2, 3):
         assert _rel(out[mode], ref) < 1e-8, (mode, stats[mode])
     assert _rel(out[0], out[2]) < 1e-9
+
+
+@pytest.mark.parametrize("eigen", [4, 3])
+def test_ml_pipelined_pass_reuses_its_slots_at_a_small_order(eigen, monkeypatch):
+    """The pipelined eigen pass with many chunks per slot at order 128: every tile of `_shortcut_case` decomposed
+    (`ml_shortcut` = 2) out of a workspace of 4 to 8 matrices, so each of the two chunk slots -- its matrix regions, its
+    range of the work array, its device lists -- is reused some twenty times.  `ml_eigen` = 3 makes QL give up on every
+    other matrix of a chunk: those are collected when the chunk retires and go through the synchronous Jacobi batches
+    at the end of the pass, which must leave the caller's `ml_eigen` alone."""
+    from draco_amd import _lib
+    from draco_amd.analysis._solve import SolveEngine
+    from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
+    from draco_amd.device import Context
+
+    ctx = Context.get()
+    case = _shortcut_case()
+    nfreq, lmax, tel = case["nfreq"], case["lmax"], case["tel"]
+    ntile = nfreq * (lmax + 1)
+    mib, asked = 6, []
+    workspace = SolveEngine._workspace
+    monkeypatch.setattr(SolveEngine, "_offer_workspace", lambda self, option, cap_mib: _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, option, mib)))
+    monkeypatch.setattr(SolveEngine, "_workspace", lambda self, nbytes: (asked.append(nbytes), workspace(self, nbytes))[1])
+    names = (b"ml_tiles_eigen", b"ml_tiles_direct", b"ml_tiles_ql_failed")
+    try:
+        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
+        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", eigen))
+        c0 = [_counter(ctx, n) for n in names]
+        task = MaximumLikelihoodMapMaker()
+        task.setup(case["bt"])
+        out = task.alm_square(task.make_alm(case["mm"]))
+        grew = [_counter(ctx, n) - v for n, v in zip(names, c0)]
+        eigen_after = _counter(ctx, b"opt_ml_eigen")
+    finally:
+        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
+        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
+        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_workspace_mib", 0))
+    # capacity from what dmm_ml_workspace_bytes asked for: header + cap matrices + 1024 (the layout of the dense solvers:
+    # A and two more matrices of the padded order, the right-hand side, 64 x 64 blocks and a few words per matrix)
+    n, npad = 2 * tel.npairs, 128
+    per_mat = 3 * npad * npad * 16 + n * 16 + (npad // 64) * (64 * 64 * 16 + 4) + 96
+    pitch = (4 * (lmax + 1) + 15) // 16 * 16
+    header = ((lmax + 1) * 8 + 255) // 256 * 256 + ((lmax + 1) * pitch * 8 + 255) // 256 * 256
+    assert len(set(asked)) == 1 and (asked[0] - header - 1024) % per_mat == 0, asked
+    cap = (asked[0] - header - 1024) // per_mat
+    assert 4 <= cap <= 8 and cap == (mib << 20) // per_mat, cap
+    print("cap", cap, "grew", grew, "rel", _rel(out, case["ref"]))
+    assert grew[0] == ntile and grew[1] == 0, grew
+    if eigen == 3:
+        assert grew[2] > 0, grew
+    assert eigen_after == eigen
+    assert _rel(out, case["ref"]) < 1e-8, (eigen, grew)
 
 
 def test_wiener_sky_side_vs_telescope_side():
