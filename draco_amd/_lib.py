@@ -30,6 +30,8 @@ DMM_MAX_NRA = 8192
 DMM_STACK_UNIFORM, DMM_STACK_INVERSE_VARIANCE = 0, 1
 DMM_DAYENU_F32, DMM_DAYENU_F64 = 0, 1
 DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
+DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
+DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
 
 
 class DmmError(RuntimeError):
@@ -50,6 +52,10 @@ class dmm_gemv_desc(C.Structure):
 
 class dmm_dayenu_side(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("ncol", C.c_int64), ("stride_freq", C.c_int64), ("stride_col", C.c_int64), ("stride_inner", C.c_int64), ("stride_outer", C.c_int64)]
+
+
+class dmm_delay_view(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("stride_sample", C.c_int64), ("stride_freq", C.c_int64), ("stride_fold", C.c_int64 * 4)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -123,6 +129,11 @@ _SIGS = {
     "dmm_dayenu_build": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_dayenu_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
     "dmm_dayenu_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, C.POINTER(dmm_dayenu_side), C.POINTER(dmm_dayenu_side)]),
+    "dmm_delay_fourier": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "dmm_delay_prepare": (_i, [_vp, _i, _i, _i, _i, _i64, _i, C.POINTER(_i64), C.POINTER(dmm_delay_view), C.POINTER(dmm_delay_view), _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_delay_project": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmm_delay_solve": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmm_delay_store": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

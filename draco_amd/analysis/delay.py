@@ -1,0 +1,538 @@
+"""Delay spectrum estimation on the GPU: inverse-FFT and Wiener-filter delay transforms.
+
+Drop-in for the frequency-to-delay transforms of ``draco/analysis/delay.py``:
+
+* :func:`delay_spectrum_fft`, :func:`delay_spectrum_wiener_filter`                      ``delay.py:2102-2201``
+* :func:`fourier_matrix_r2c`, :func:`fourier_matrix_c2r`, :func:`fourier_matrix_c2c`, :func:`fourier_matrix`   ``delay.py:1480-1613``
+* :class:`DelaySpectrumFFT`, :class:`DelaySpectrumWienerFilter`, :class:`DelaySpectrumWienerFilterIteratePS`   ``delay.py:347-1053``
+* :class:`DelaySpectrumToPowerSpectrum`                                                  ``delay.py:1061-1106``
+
+Same names, config attributes, defaults and ``setup`` / ``process`` signatures.  The arithmetic runs in
+``libdraco_amd.so`` (``csrc/delay.hip``), batched over baselines: a prepare pass (the ``time_frac`` / ``freq_frac``
+masks, the mean over the retained samples, the averaged weights), a projection onto one Fourier matrix shared by every
+baseline on the f64 matrix cores, a blocked float64 Cholesky solve of the Wiener matrix, and a store that applies the
+task's ``fftshift``.  The input datasets are read through strides where they lie (on the device if they are already
+there) and are not modified; the output ``spectrum`` stays on the device.
+
+``F^T N^-1 F`` is circulant (2 x 2 block circulant in the complex time domain), so the Wiener matrix is filled from
+one cosine (and one sine) sequence that the projection delivers as one more right-hand side; a cut channel is a zero
+coefficient, not a smaller matrix.  The order of the solve, ``ndelay`` (real time domain) or ``2 ndelay`` (complex),
+may be 1 ... 2048.
+
+The transform needs the whole band in one process: frequency sharding does not apply to these tasks.
+
+Out of scope (``NotImplementedError`` where a parameter asks for it): ``use_average_weights=False`` (the reference's
+Wiener function cannot take per-sample weights either) and ``scale_freq=True``; not provided: the Gibbs, NRML and
+cross-spectrum estimators, ``DelayFilter`` / ``DelayFilterBase`` and ``DelayTransformOperator``.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..core import containers
+from ..core.task import ContainerTask
+from ..device import Context, ptr
+from ..util import tools
+from .transform import _dev_dataset
+
+MAX_ORDER = 2048
+_WINDOWS = ("uniform", "hann", "hanning", "hamming", "blackman", "nuttall", "blackman_nuttall", "blackman_harris")
+_DTYPE = {
+    np.dtype(np.float32): _lib.DMM_DELAY_F32,
+    np.dtype(np.float64): _lib.DMM_DELAY_F64,
+    np.dtype(np.complex64): _lib.DMM_DELAY_C64,
+    np.dtype(np.complex128): _lib.DMM_DELAY_C128,
+}
+_TORCH2NP = {torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}
+
+
+# ---- Fourier matrices
+
+
+def _channels(fsel, count):
+    return np.arange(count) if fsel is None else np.asarray(fsel)
+
+
+def _host_trig(N, chan):
+    """``cos`` and ``sin`` of the phase ``2 pi f t / N`` of channel ``f`` at time sample ``t``, ``[nsel, N]``, in
+    NumPy.  The phase is taken as the plain float64 product (the host forms agree with the reference's values to
+    1e-15; the device forms reduce ``f t`` modulo ``N`` in integers and are the accurate ones)."""
+    phase = np.multiply.outer(chan, 2 * np.pi * np.arange(N)) / N
+    return np.cos(phase), np.sin(phase)
+
+
+def _fourier_device(N, chan, complex_td):
+    ctx = Context.get()
+    chan = np.ascontiguousarray(chan, dtype=np.int32)
+    if chan.ndim != 1 or chan.size == 0 or N < 1 or np.any(chan < 0):
+        raise ValueError("fourier matrix: N must be positive and fsel a non-empty 1-D list of non-negative channel indices")
+    chan_d = ctx.to_device(chan)
+    F = ctx.empty((2 * chan.size, 2 * N if complex_td else N), np.float64)
+    _lib.check(_lib.lib.dmm_delay_fourier(ctx.handle, int(N), int(chan.size), int(complex_td), ptr(chan_d), ptr(F)))
+    ctx.uses(chan_d)
+    return F
+
+
+def fourier_matrix_r2c(N, fsel=None, device=True):
+    """Fourier matrix of a real to complex FFT: ``[2 nsel, N]``, a (cos, -sin) pair of rows per channel (the real and
+    the imaginary part of that channel).  ``fsel`` defaults to the ``N // 2 + 1`` channels of an even ``N``.  On the
+    device (a float64 tensor, arguments reduced exactly); with ``device=False`` a NumPy array."""
+    chan = _channels(fsel, N // 2 + 1)
+    if device:
+        return _fourier_device(N, chan, False)
+    c, s = _host_trig(N, chan)
+    return np.stack([c, -s], axis=1).reshape(2 * len(chan), N)
+
+
+def fourier_matrix_c2r(N, fsel=None, device=True):
+    """Fourier matrix of a complex to real FFT: ``[N, 2 nsel]``, the transpose of :func:`fourier_matrix_r2c` with every
+    channel weighted ``2 / N``, or ``1 / N`` for the strictly real channels 0 and ``N / 2``."""
+    chan = _channels(fsel, N // 2 + 1)
+    c, s = _host_trig(N, chan)
+    share = np.where((chan == 0) | (chan == N // 2), 1.0, 2.0) / N
+    F = np.stack([c * share[:, np.newaxis], -s * share[:, np.newaxis]], axis=1).reshape(2 * len(chan), N).T.copy()
+    return Context.get().to_device(F) if device else F
+
+
+def fourier_matrix_c2c(N, fsel=None, device=True):
+    """Fourier matrix of a complex to complex FFT in ``numpy.fft.fft``'s sign convention: ``[2 nsel, 2 N]``, input and
+    output as alternating real and imaginary elements, so each (channel, sample) entry is the rotation
+    ``[[cos, sin], [-sin, cos]]``."""
+    chan = _channels(fsel, N)
+    if device:
+        return _fourier_device(N, chan, True)
+    c, s = _host_trig(N, chan)
+    rot = np.stack([np.stack([c, s], axis=-1), np.stack([-s, c], axis=-1)], axis=1)  # [nsel, 2, N, 2]
+    return rot.reshape(2 * len(chan), 2 * N)
+
+
+def fourier_matrix(N, fsel=None, device=True):
+    """The complex Fourier matrix ``exp(-2 pi i f t / N)``: ``[nsel, N]`` complex128."""
+    c, s = _host_trig(N, _channels(fsel, N))
+    F = c - 1j * s
+    return Context.get().to_device(F) if device else F
+
+
+# ---- the batched pipeline
+
+
+def _view(t, dtype_code, s_sample, s_freq, s_fold=()):
+    fold = (C.c_int64 * 4)(*([int(s) for s in s_fold] + [0] * (4 - len(s_fold))))
+    return _lib.dmm_delay_view(C.c_void_p(t.data_ptr()), int(dtype_code), int(s_sample), int(s_freq), fold)
+
+
+def _shifted_inverse(ps, complex_td):
+    """``Si`` of the solve from prior rows ``ps [..., ndelay]`` as the task holds them: the reference passes
+    ``fftshift`` of the row, inverts where non-zero, and doubles and repeats per component in the complex case."""
+    si = tools.invert_no_zero(np.fft.fftshift(np.asarray(ps, dtype=np.float64), axes=-1))
+    if complex_td:
+        si = 2.0 * np.repeat(si, 2, axis=-1)
+    return np.ascontiguousarray(si)
+
+
+def _transform(ctx, data_v, weight_v, fold_n, nbase, nsample, channel_ind, ndelay, complex_td, coef, si, *, remove_mean, time_frac, freq_frac, weight_boost, spectrum, mask=None,
+               workspace_mib=1024, what="baseline"):
+    """Run prepare / project / (solve) / store over ``nbase`` baselines in batches; ``si [nbase, order]`` (host) selects
+    the Wiener filter, ``None`` the inverse FFT.  Returns the status words (host)."""
+    wiener = si is not None
+    nchan = int(len(channel_ind))
+    order = 2 * ndelay if complex_td else ndelay
+    if nsample > 65535:
+        raise ValueError(f"delay transform: {nsample} samples, the kernels take at most 65535")
+    nrow = nsample + (1 if wiener else 0)
+    chan_d = ctx.to_device(np.ascontiguousarray(channel_ind, dtype=np.int32))
+    coef_d = ctx.to_device(np.ascontiguousarray(coef, dtype=np.float64))
+    F = ctx.empty((2 * nchan, order), np.float64)
+    _lib.check(_lib.lib.dmm_delay_fourier(ctx.handle, ndelay, nchan, int(complex_td), ptr(chan_d), ptr(F)))
+    fold = (C.c_int64 * max(1, len(fold_n)))(*[int(x) for x in fold_n])
+    per_bytes = 8 * (nrow * 2 * nchan + nrow * order + (order * order if wiener else 0)) + nsample + 64
+    per = max(1, min(65535, (int(workspace_mib) << 20) // per_bytes))
+    status_all = np.zeros(nbase, dtype=np.int32)
+    for b0 in range(0, nbase, per):
+        nb = min(per, nbase - b0)
+        X = ctx.empty((nb, nrow, 2 * nchan), np.float64)
+        Y = ctx.empty((nb, nrow, order), np.float64)
+        nzt = ctx.empty((nb, nsample), np.uint8)
+        status = ctx.empty((nb,), np.int32)
+        _lib.check(
+            _lib.lib.dmm_delay_prepare(
+                ctx.handle, ndelay, nchan, nsample, nb, b0, len(fold_n), fold, C.byref(data_v), C.byref(weight_v), int(complex_td), int(wiener), int(bool(remove_mean)),
+                float(time_frac), float(freq_frac), float(weight_boost), ptr(coef_d), ptr(chan_d), ptr(X), ptr(nzt), ptr(status),
+            )
+        )
+        _lib.check(_lib.lib.dmm_delay_project(ctx.handle, order, nchan, nrow, nb, ptr(X), ptr(F), ptr(Y), ptr(status)))
+        si_d = G = None
+        if wiener:
+            si_d = ctx.to_device(np.ascontiguousarray(si[b0 : b0 + nb]))
+            G = ctx.empty((nb, order, order), np.float64)
+            _lib.check(_lib.lib.dmm_delay_solve(ctx.handle, order, int(complex_td), nsample, nb, ptr(Y), ptr(si_d), ptr(G), ptr(status)))
+        _lib.check(
+            _lib.lib.dmm_delay_store(ctx.handle, ndelay, int(complex_td), nsample, nrow, nb, ptr(Y), ptr(nzt), ptr(status), ptr(spectrum[b0 : b0 + nb]), ptr(mask[b0 : b0 + nb]) if mask is not None else None)
+        )
+        status_all[b0 : b0 + nb] = status.cpu().numpy()
+        ctx.uses(X, Y, nzt, status, si_d, G)
+        bad = np.flatnonzero(status_all[b0 : b0 + nb] == _lib.DMM_DELAY_NOT_POSDEF)
+        if bad.size:
+            raise np.linalg.LinAlgError(f"delay transform: the Wiener matrix of {what} {b0 + int(bad[0])} is not positive definite")
+        cut = np.flatnonzero(status_all[b0 : b0 + nb] == _lib.DMM_DELAY_CUT)
+        if cut.size:
+            raise ValueError(f"delay transform: {what} {b0 + int(cut[0])} has cut channels; the FFT estimator needs every one of the {ndelay} channels")
+    ctx.uses(chan_d, coef_d, F)
+    return status_all
+
+
+def _check_order(order):
+    if not 1 <= order <= MAX_ORDER:
+        raise ValueError(f"delay transform: a solve of order {order}, the kernels take 1 ... {MAX_ORDER}")
+
+
+def _sample_block(data, what):
+    """A ``[nsample, nfreq]`` array as a contiguous device tensor of a dtype the kernels read."""
+    ctx = Context.get()
+    if isinstance(data, torch.Tensor):
+        t = data.to(ctx.device)
+        if t.dtype not in _TORCH2NP:
+            t = t.to(torch.complex128 if t.is_complex() else torch.float64)
+        t = t.contiguous()
+    else:
+        a = np.asarray(data)
+        if a.dtype not in _DTYPE:
+            a = a.astype(np.complex128 if a.dtype.kind == "c" else np.float64)
+        t = ctx.to_device(a)
+    if t.ndim != 2:
+        raise ValueError(f"{what}: data must be [nsample, freq], not {tuple(t.shape)}")
+    return ctx, t
+
+
+def _window_coef(x, window):
+    return np.ones(len(x)) if window is None else np.asarray(tools.window_generalised(np.asarray(x, dtype=np.float64), window=window), dtype=np.float64)
+
+
+def delay_spectrum_fft(data, N, window="nuttall"):
+    """Estimate the delay transform of ``data [nsample, N]`` by inverse FFT (``delay.py:2102-2129``).
+
+    The window is evaluated at ``arange(N) / N``.  Returns ``[nsample, N]`` complex128 **on the device** (not shifted);
+    ``data`` is not modified.  Only a complex time domain with every channel present has ``N`` channels: any other
+    width raises ``ValueError``.
+    """
+    ctx, t = _sample_block(data, "delay_spectrum_fft")
+    nsample, nfreq = (int(s) for s in t.shape)
+    if nfreq != int(N):
+        raise ValueError(f"delay_spectrum_fft: {nfreq} channels cannot be transformed to {N} delays")
+    coef = _window_coef(np.arange(N) / N, window) / N
+    ones = ctx.to_device(np.ones(nfreq, dtype=np.float64))
+    spec = ctx.empty((1, nsample, N), np.complex128)
+    _transform(ctx, _view(t, _DTYPE[np.dtype(_TORCH2NP[t.dtype])], nfreq, 1), _view(ones, _lib.DMM_DELAY_F64, 0, 1), (), 1, nsample, np.arange(N), int(N), True, coef, None,
+               remove_mean=False, time_frac=-1.0, freq_frac=0.0, weight_boost=1.0, spectrum=spec)
+    ctx.uses(t, ones)
+    return torch.fft.ifftshift(spec[0], dim=-1)
+
+
+def delay_spectrum_wiener_filter(delay_PS, data, N, Ni, window="nuttall", fsel=None, complex_timedomain=False):
+    """Estimate the delay spectrum of ``data [nsample, freq]`` by Wiener filtering (``delay.py:2132-2201``).
+
+    ``delay_PS [N]`` is the signal power spectrum, ``Ni [freq]`` the inverse noise variance, ``fsel`` the indices of
+    the channels present among the ``N // 2 + 1`` (real time domain) or ``N`` (complex) of the full set; the window is
+    evaluated at ``fsel / total``.  Returns ``[nsample, N]`` **on the device**, float64 in the real time domain and
+    complex128 otherwise.  A matrix that is not positive definite raises ``numpy.linalg.LinAlgError``.
+    """
+    ctx, t = _sample_block(data, "delay_spectrum_wiener_filter")
+    N = int(N)
+    total = N if complex_timedomain else N // 2 + 1
+    fsel = np.arange(total) if fsel is None else np.asarray(fsel)
+    nsample, nfreq = (int(s) for s in t.shape)
+    ni = np.ascontiguousarray(Ni, dtype=np.float64)
+    if ni.shape != (nfreq,) or fsel.shape != (nfreq,):
+        raise ValueError(f"delay_spectrum_wiener_filter: {nfreq} channels of data, Ni {ni.shape}, fsel {fsel.shape}")
+    ps = np.asarray(delay_PS, dtype=np.float64)
+    if ps.shape != (N,):
+        raise ValueError(f"delay_spectrum_wiener_filter: delay_PS {ps.shape} for {N} delays")
+    _check_order(2 * N if complex_timedomain else N)
+    coef = _window_coef(fsel / total, window) ** 2
+    si = tools.invert_no_zero(ps)
+    si = (2.0 * np.repeat(si, 2) if complex_timedomain else si)[np.newaxis, :]
+    ni_d = ctx.to_device(ni)
+    spec = ctx.empty((1, nsample, N), np.complex128)
+    _transform(ctx, _view(t, _DTYPE[np.dtype(_TORCH2NP[t.dtype])], nfreq, 1), _view(ni_d, _lib.DMM_DELAY_F64, 0, 1), (), 1, nsample, fsel, N, bool(complex_timedomain), coef, si,
+               remove_mean=False, time_frac=-1.0, freq_frac=0.0, weight_boost=1.0, spectrum=spec, what="matrix")
+    ctx.uses(t, ni_d)
+    out = torch.fft.ifftshift(spec[0], dim=-1)
+    return out if complex_timedomain else out.real.contiguous()
+
+
+# ---- tasks
+
+
+class DelayTransformBase(ContainerTask):
+    """What the delay transforms share (``delay.py:347-866``): the delay grid, the view of the input as ``[baseline,
+    sample, freq]``, the output container.
+
+    Attributes
+    ----------
+    freq_zero : float, optional
+        The physical frequency (MHz) of the zero (DC) channel of the F-engine.  Default: the first frequency.
+    freq_spacing : float, optional
+        The spacing between the underlying channels (MHz).  Default: the smallest gap found between channels.
+    nfreq : int, optional
+        The number of channels in the full set.  Default: the last included frequency is the last of the full set (the
+        penultimate with ``skip_nyquist``).
+    skip_nyquist : bool
+        Whether the Nyquist frequency is missing from the data.  Default True.
+    apply_window : bool
+        Whether to apodise the frequency axis.  Default True.
+    window : str
+        One of the cosine-sum windows of :func:`draco_amd.util.tools.window_generalised`.  Default 'nuttall'.
+    complex_timedomain : bool
+        Whether the channelised time samples were complex; then ``freq_zero``, ``nfreq`` and ``skip_nyquist`` are
+        ignored.  Default False.
+    use_average_weights : bool
+        Use noise weights averaged over the samples.  Default True; ``False`` raises ``NotImplementedError``.
+    weight_boost : float
+        Multiply the weights by this factor.  Default 1.0.
+    freq_frac, time_frac : float
+        A channel (a sample) is retained if its share of unmasked samples (channels) is strictly above this.  Default
+        0.0 for both.
+    remove_mean : bool
+        Subtract the mean over the retained samples of each channel.  Default True.
+    scale_freq : bool
+        Default False; ``True`` raises ``NotImplementedError``.
+    dataset : str, optional
+        The dataset to transform.  Default: the container's main dataset (``vis``, or ``map`` of a ring map).
+    sample_axis : str
+        Every sample along this axis is drawn from the same power spectrum; all axes other than this one and ``freq``
+        are folded into ``baseline``, slowest first.
+    save_spectrum_mask : bool
+        Add ``spectrum_mask [baseline, sample]``, set where a baseline was skipped or a sample dropped.  Default False.
+    workspace_mib : int
+        Device memory the scratch of one batch of baselines may take.  Default 1024.
+
+    The whole band must be in this process.  The input datasets are not modified.
+    """
+
+    _config_names = (
+        "freq_zero", "freq_spacing", "nfreq", "skip_nyquist", "apply_window", "window", "complex_timedomain", "use_average_weights", "weight_boost", "freq_frac", "time_frac",
+        "remove_mean", "scale_freq", "dataset", "sample_axis", "save_spectrum_mask", "workspace_mib",
+    )
+    freq_zero = None
+    freq_spacing = None
+    nfreq = None
+    skip_nyquist = True
+    apply_window = True
+    window = "nuttall"
+    complex_timedomain = False
+    use_average_weights = True
+    weight_boost = 1.0
+    freq_frac = 0.0
+    time_frac = 0.0
+    remove_mean = True
+    scale_freq = False
+    dataset = None
+    sample_axis = None
+    save_spectrum_mask = False
+    workspace_mib = 1024
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.window not in _WINDOWS:
+            raise ValueError(f"window must be one of {_WINDOWS}, not {self.window!r}")
+
+    def _check(self):
+        if not self.use_average_weights:
+            raise NotImplementedError(f"{type(self).__name__}: use_average_weights=False (weights per sample) is not on the GPU path")
+        if self.scale_freq:
+            raise NotImplementedError(f"{type(self).__name__}: scale_freq=True is not on the GPU path")
+
+    def _calculate_delays(self, ss):
+        """``(delays, channel_ind)``: the delay grid in micro-seconds, ascending through zero, and the index of every
+        channel of the data in the full set of the F-engine.
+
+        Complex time domain: the data's channels are the full set, one delay per channel.  Real time domain: a channel's
+        index is its distance from ``freq_zero`` in units of the spacing, rounded down; the full set has ``nfreq``
+        channels (by default it ends at the data's last channel, or one beyond it with ``skip_nyquist``) and belongs
+        to frames of ``2 (nfreq - 1)`` real samples.  ``ss`` is a container with ``freq``, or a list of them."""
+        first = ss if hasattr(ss, "freq") else (ss[0] if len(ss) > 0 else None)
+        if first is None:
+            raise TypeError("Could not find a frequency axis in the input.")
+        freq = np.asarray(first.freq)
+        spacing = np.abs(np.diff(freq)).min() if self.freq_spacing is None else self.freq_spacing
+        if self.complex_timedomain:
+            channel_ind = np.arange(len(freq))
+            ndelay = len(freq)
+        else:
+            origin = freq[0] if self.freq_zero is None else self.freq_zero
+            channel_ind = np.floor(np.abs(freq - origin) / spacing).astype(np.int64)
+            full = self.nfreq if self.nfreq is not None else channel_ind[-1] + (2 if self.skip_nyquist else 1)
+            ndelay = 2 * (full - 1)
+        step = 1.0 / (ndelay * spacing)  # numpy.fft.fftfreq's own scaling, so the grid equals fftshift(fftfreq(...))
+        return (np.arange(ndelay) - ndelay // 2) * step, channel_ind
+
+    def _resolve(self, ss):
+        """The dataset to transform, its axes, the axes of the weights and the axes folded into ``baseline``
+        (``delay.py:696-741``); ``ValueError`` for an unknown dataset or sample axis."""
+        if self.dataset is not None:
+            if self.dataset not in ss.datasets:
+                raise ValueError(f"{type(self).__name__}: {type(ss).__name__} has no dataset {self.dataset!r}")
+            name = self.dataset
+        else:
+            name = next((n for n in ("vis", "map") if n in ss.datasets), None)
+            if name is None:
+                raise ValueError(f"{type(self).__name__}: {type(ss).__name__} has neither `vis` nor `map`; name the dataset")
+        axes = list(ss.datasets[name].attrs["axis"])
+        if self.sample_axis not in ss.index_map or self.sample_axis not in axes:
+            raise ValueError(f"{type(self).__name__}: dataset {name!r} of {type(ss).__name__} has no sample axis {self.sample_axis!r}")
+        if "freq" not in axes:
+            raise ValueError(f"Dataset {name} of {type(ss)} has no freq axis.")
+        waxes = list(ss.weight.attrs["axis"])
+        if self.sample_axis not in waxes or "freq" not in waxes or any(ax not in axes for ax in waxes):
+            raise ValueError(f"The weight axes {waxes} of {type(ss)} cannot be matched to the axes {axes} of {name}.")
+        fold = [ax for ax in axes if ax not in (self.sample_axis, "freq")]
+        if len(fold) > 4:
+            raise NotImplementedError(f"{type(self).__name__}: {len(fold)} axes to fold into baseline, the kernels take at most 4")
+        return name, axes, waxes, fold
+
+    def _prepare_inputs(self, ss, ctx, name, axes, waxes, fold):
+        """Device tensors of the data and the weights and their views as ``[baseline, sample, freq]`` (``delay.py:2238-2302``;
+        a weight dataset that lacks a folded axis is broadcast: stride 0)."""
+        data_ds, weight_ds = ss.datasets[name], ss.weight
+        ddt = np.dtype(data_ds.dtype)
+        wdt = np.dtype(weight_ds.dtype)
+        data = _dev_dataset(data_ds, ctx, ddt.type if ddt in _DTYPE else (np.complex128 if ddt.kind == "c" else np.float64))
+        weight = _dev_dataset(weight_ds, ctx, wdt.type if wdt in (np.dtype(np.float32), np.dtype(np.float64)) else np.float64)
+        ds_, ws_ = data.stride(), weight.stride()
+        data_v = _view(data, _DTYPE[np.dtype(_TORCH2NP[data.dtype])], ds_[axes.index(self.sample_axis)], ds_[axes.index("freq")], [ds_[axes.index(ax)] for ax in fold])
+        weight_v = _view(weight, _DTYPE[np.dtype(_TORCH2NP[weight.dtype])], ws_[waxes.index(self.sample_axis)], ws_[waxes.index("freq")], [ws_[waxes.index(ax)] if ax in waxes else 0 for ax in fold])
+        return data, weight, data_v, weight_v, [int(data.shape[axes.index(ax)]) for ax in fold]
+
+
+class DelaySpectrumBase(DelayTransformBase):
+    """Delay spectrum estimation into a :class:`~draco_amd.core.containers.DelayTransform` (``delay.py:821-957``)."""
+
+    _wiener = False
+
+    def _create_output(self, ss, delays, coord_axes, nbase, nsample, ctx):
+        out = containers.DelayTransform(baseline=nbase, sample=ss.index_map[self.sample_axis], delay=delays, attrs_from=ss, weight_boost=self.weight_boost, allocate=False)
+        for ax in coord_axes:
+            out.create_index_map(ax, ss.index_map[ax])
+        out.attrs["baseline_axes"] = coord_axes
+        out.attrs["freq"] = np.asarray(ss.freq)
+        out.attrs["window_los"] = self.window if self.apply_window else "None"
+        return out
+
+    def process(self, ss):
+        """Estimate the delay spectrum of every baseline of ``ss``; returns a ``DelayTransform`` whose ``spectrum``
+        is on the device."""
+        self._check()
+        delays, channel_ind = self._calculate_delays(ss)
+        ndelay, nchan = len(delays), len(channel_ind)
+        ss.redistribute("freq")
+        name, axes, waxes, fold = self._resolve(ss)
+        fold_n = [len(ss.index_map[ax]) for ax in fold]
+        nbase = int(np.prod(fold_n)) if fold_n else 1
+        nsample = len(ss.index_map[self.sample_axis])
+        complex_td = bool(self.complex_timedomain)
+        total = ndelay if complex_td else ndelay // 2 + 1
+        if self._wiener:
+            _check_order(2 * ndelay if complex_td else ndelay)
+            coef = _window_coef(channel_ind / total, self.window if self.apply_window else None) ** 2
+            si = self._get_prior(nbase, ndelay, complex_td)
+        else:
+            if not complex_td or nchan != ndelay:
+                raise ValueError(f"{type(self).__name__}: {nchan} channels cannot be transformed to {ndelay} delays by inverse FFT; it takes the complex time domain and the whole band")
+            coef = _window_coef(np.arange(ndelay) / ndelay, self.window if self.apply_window else None) / ndelay
+            si = None
+        ctx = Context.get()
+        data, weight, data_v, weight_v, fold_n = self._prepare_inputs(ss, ctx, name, axes, waxes, fold)
+        out = self._create_output(ss, delays, fold, nbase, nsample, ctx)
+        spectrum = ctx.empty((nbase, nsample, ndelay), np.complex128)
+        mask = ctx.empty((nbase, nsample), np.uint8) if self.save_spectrum_mask else None
+        _transform(ctx, data_v, weight_v, fold_n, nbase, nsample, channel_ind, ndelay, complex_td, coef, si, remove_mean=self.remove_mean, time_frac=self.time_frac, freq_frac=self.freq_frac,
+                   weight_boost=self.weight_boost, spectrum=spectrum, mask=mask, workspace_mib=self.workspace_mib)
+        ctx.uses(data, weight)
+        out.attach("spectrum", spectrum)
+        if mask is not None:
+            out.add_dataset("spectrum_mask", allocate=False)
+            out.datasets["spectrum_mask"] = containers.Dataset(host=mask.cpu().numpy().astype(bool), attrs={"axis": ["baseline", "sample"]})
+        return out
+
+
+class DelaySpectrumFFT(DelaySpectrumBase):
+    """Measure the delay spectrum of a general container by inverse FFT (``delay.py:960-979``).  Only a band of the
+    complex time domain without cut channels can be transformed: anything else raises ``ValueError``."""
+
+
+class DelaySpectrumWienerFilter(DelaySpectrumBase):
+    """Measure the delay spectrum of a general container by Wiener filtering (``delay.py:982-1024``,
+    https://arxiv.org/abs/2202.01242 Eq. A6): the signal covariance is a delay power spectrum, the noise covariance
+    comes from the weights of the input.  A Wiener matrix that is not positive definite raises
+    ``numpy.linalg.LinAlgError`` naming the baseline."""
+
+    _wiener = True
+    dps = None
+
+    def setup(self, dps=None):
+        """Set the delay power spectrum (a ``DelaySpectrum``) to use as the signal covariance."""
+        self.dps = dps
+
+    def _get_prior(self, nbase, ndelay, complex_td):
+        if self.dps is None:
+            raise ValueError(f"{type(self).__name__}: no delay power spectrum given")
+        ps = np.asarray(self.dps.spectrum[:], dtype=np.float64)
+        if ps.shape != (nbase, ndelay):
+            raise ValueError(f"{type(self).__name__}: the delay power spectrum is {ps.shape}, the data need {(nbase, ndelay)}")
+        return _shifted_inverse(ps, complex_td)
+
+
+class DelaySpectrumWienerFilterIteratePS(DelaySpectrumWienerFilter):
+    """:class:`DelaySpectrumWienerFilter` whose delay power spectrum comes with every ``process`` call
+    (``delay.py:1027-1053``)."""
+
+    def process(self, ss, dps):
+        """Estimate the delay spectrum of ``ss`` with ``dps`` as the signal covariance."""
+        self.dps = dps
+        return super().process(ss)
+
+
+class DelaySpectrumToPowerSpectrum(ContainerTask):
+    """Compute a delay power spectrum from a delay spectrum (``delay.py:1061-1106``): the variance over the sample
+    axis, restricted to the unmasked samples.  A baseline with every sample masked gives zero and is flagged in the
+    output's ``spectrum_mask``."""
+
+    def process(self, dspec):
+        dspec.redistribute("baseline")
+        ctx = Context.get()
+        pspec = containers.DelaySpectrum(attrs_from=dspec, axes_from=dspec, allocate=False)
+        ds = _dev_dataset(dspec.spectrum, ctx, np.complex128)
+        if "spectrum_mask" in dspec.datasets:
+            w = ~ctx.to_device(np.asarray(dspec.datasets["spectrum_mask"][:]).astype(np.uint8)).bool()[:, :, None]
+        else:
+            w = torch.ones((ds.shape[0], ds.shape[1], 1), dtype=torch.bool, device=ctx.device)
+        cnt = w.sum(dim=1).to(torch.float64)
+        mean = (ds * w).sum(dim=1) / cnt
+        ps = (((ds - mean[:, None, :]).abs() ** 2) * w).sum(dim=1) / cnt
+        nans = torch.isnan(ps)
+        ps = torch.where(nans, torch.zeros_like(ps), ps).contiguous()
+        pspec.attach("spectrum", ps)
+        if "spectrum_mask" in dspec.datasets:
+            pspec.add_dataset("spectrum_mask", allocate=False)
+            pspec.datasets["spectrum_mask"] = containers.Dataset(host=nans.any(dim=-1).cpu().numpy(), attrs={"axis": ["baseline"]})
+        return pspec
+
+
+__all__ = [
+    "DelaySpectrumFFT",
+    "DelaySpectrumToPowerSpectrum",
+    "DelaySpectrumWienerFilter",
+    "DelaySpectrumWienerFilterIteratePS",
+    "DelayTransformBase",
+    "delay_spectrum_fft",
+    "delay_spectrum_wiener_filter",
+    "fourier_matrix",
+    "fourier_matrix_c2c",
+    "fourier_matrix_c2r",
+    "fourier_matrix_r2c",
+]

@@ -592,6 +592,76 @@ class Map(ContainerBase, _FreqMixin):
         return int(round((len(self.index_map["pixel"]) // 12) ** 0.5))
 
 
+class DelayContainer(ContainerBase):
+    """A container with a ``delay`` axis, in micro-seconds (``containers.py:2038-2046``)."""
+
+    _axes = ("delay",)
+
+    def __init__(self, weight_boost=1.0, **kwargs):
+        self._dataset_spec = dict(type(self)._dataset_spec)
+        super().__init__(**kwargs)
+        self.attrs["weight_boost"] = weight_boost
+
+    def add_dataset(self, name, allocate=True):
+        self._dataset_spec[name] = self._optional_spec[name]
+        if allocate:
+            self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=self._optional_spec[name]["dtype"]), attrs={"axis": self._optional_spec[name]["axes"]})
+
+    def create_index_map(self, name, values):
+        """Carry the index map of an axis that was folded into ``baseline``."""
+        self.index_map[name] = np.asarray(values)
+        self.index_attrs.setdefault(name, {})
+
+    @property
+    def delay(self):
+        return self.index_map["delay"]
+
+    @property
+    def spectrum(self):
+        return self.datasets["spectrum"]
+
+    @property
+    def weight_boost(self):
+        """The factor the weights were multiplied by when the spectrum was computed."""
+        return self.attrs["weight_boost"]
+
+    @property
+    def freq(self):
+        """The frequency axis of the input data (kept as an attribute)."""
+        return self.attrs["freq"]
+
+
+class DelaySpectrum(DelayContainer):
+    """A delay POWER spectrum: ``spectrum [baseline, delay]`` float64; optional ``spectrum_samples [sample, baseline,
+    delay]`` float64 and ``spectrum_mask [baseline]`` bool (``containers.py:2049-2110``)."""
+
+    _axes = ("baseline", "sample", "delay")
+    _dataset_spec = {"spectrum": {"axes": ["baseline", "delay"], "dtype": np.float64}}
+    _optional_spec = {
+        "spectrum_samples": {"axes": ["sample", "baseline", "delay"], "dtype": np.float64},
+        "spectrum_mask": {"axes": ["baseline"], "dtype": np.bool_},
+    }
+
+    def __init__(self, weight_boost=1.0, sample=1, **kwargs):
+        super().__init__(weight_boost=weight_boost, sample=sample, **kwargs)
+
+
+class DelayTransform(DelayContainer):
+    """A delay spectrum: ``spectrum [baseline, sample, delay]`` complex128; optional ``weight`` float32 of the same
+    shape and ``spectrum_mask [baseline, sample]`` bool (``containers.py:2113-2182``)."""
+
+    _axes = ("baseline", "sample", "delay")
+    _dataset_spec = {"spectrum": {"axes": ["baseline", "sample", "delay"], "dtype": np.complex128}}
+    _optional_spec = {
+        "weight": {"axes": ["baseline", "sample", "delay"], "dtype": np.float32},
+        "spectrum_mask": {"axes": ["baseline", "sample"], "dtype": np.bool_},
+    }
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+
 def _all_containers():
     found, todo = [], [ContainerBase]
     while todo:

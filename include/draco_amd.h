@@ -516,6 +516,54 @@ int dmm_dayenu_apply(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner,
                      const int32_t* item_matrix, const uint8_t* atten, const int32_t* units, int64_t nunit,
                      const dmm_dayenu_side* data, const dmm_dayenu_side* weight);
 
+/* Delay spectrum estimators (draco/analysis/delay.py:347-1106, 2102-2201), csrc/delay.hip.  All arrays [dev] unless
+ * noted, everything float64.  ndelay = N; order = N in the real time domain, 2 N (alternating real and imaginary) in
+ * the complex one; nchan channels with indices chan [nchan] int32 in the full set; baselines are batched, at most
+ * 65535 per call.
+ *
+ * dmm_delay_fourier: F [2 nchan][order], rows 2 f and 2 f + 1 the real and imaginary row of channel chan[f]
+ * (fourier_matrix_r2c / fourier_matrix_c2c); the arguments are reduced as (chan t) mod N in integers.
+ *
+ * A view (dmm_delay_view) describes a dataset as [baseline, sample, freq] in ELEMENTS of its dtype (a complex element
+ * is one element): baseline base0 + b is split over the nfold folded axes of lengths fold_n [host], slowest first, and
+ * lies at sum_q index_q stride_fold[q]; a weight dataset that lacks a folded axis has stride 0 there.
+ *
+ * dmm_delay_prepare: per baseline the sample mask nzt [nbase][nsample] bytes (share of channels with weight > 0 above
+ * time_frac), the channel mask over the retained samples (above freq_frac), status [nbase] int32 (DMM_DELAY_SKIPPED:
+ * no positive weight, nothing retained, or all-zero data after mean removal; DMM_DELAY_CUT: a channel is cut and
+ * wiener = 0), and X [nbase][nrow][2 nchan] = c o (d - mean) on the retained samples, zero rows elsewhere.  wiener = 1:
+ * nrow = nsample + 1, c = coef[f] x (average weight x weight_boost) x (1 on the real row and 0 on the imaginary row of
+ * channels 0 and N / 2 in the real time domain, 2 elsewhere), zero on cut channels, and the last row of X is c on the
+ * real rows; wiener = 0: nrow = nsample, c = coef[f].  The inputs are not modified.
+ *
+ * dmm_delay_project: Y [nbase][nrow][order] = X F on the f64 matrix cores.
+ *
+ * dmm_delay_solve (order 1 ... 2048): G [nbase][order][order] (workspace) = circ(last row of Y) + diag(Si), Si
+ * [nbase][order]; G = U^T U blocked, then each of the nsample rows of Y is replaced by the solution of G x = y.  A non-positive
+ * pivot sets status to DMM_DELAY_NOT_POSDEF and nothing further is computed for that baseline.
+ *
+ * dmm_delay_store: spectrum [nbase][nsample][ndelay] complex128 = numpy.fft.fftshift of the rows of Y (zero imaginary
+ * part in the real time domain), zeros where nzt is 0 or status is set; mask [nbase][nsample] bytes (or NULL): 1
+ * there. */
+enum { DMM_DELAY_F32 = 0, DMM_DELAY_F64 = 1, DMM_DELAY_C64 = 2, DMM_DELAY_C128 = 3 };
+enum { DMM_DELAY_OK = 0, DMM_DELAY_SKIPPED = 1, DMM_DELAY_NOT_POSDEF = 2, DMM_DELAY_CUT = 3 };
+typedef struct dmm_delay_view {
+  const void* ptr;
+  int dtype;
+  int64_t stride_sample, stride_freq, stride_fold[4];
+} dmm_delay_view;
+int dmm_delay_fourier(dmm_ctx* ctx, int ndelay, int nchan, int complex_td, const int32_t* chan, double* F);
+int dmm_delay_prepare(dmm_ctx* ctx, int ndelay, int nchan, int nsample, int nbase, int64_t base0, int nfold, const int64_t* fold_n,
+                      const dmm_delay_view* data, const dmm_delay_view* weight, int complex_td, int wiener, int remove_mean,
+                      double time_frac, double freq_frac, double weight_boost, const double* coef, const int32_t* chan, double* X,
+                      uint8_t* nzt, int32_t* status);
+int dmm_delay_project(dmm_ctx* ctx, int order, int nchan, int nrow, int nbase, const double* X, const double* F, double* Y,
+                      const int32_t* status);
+int dmm_delay_solve(dmm_ctx* ctx, int order, int complex_td, int nsample, int nbase, double* Y, const double* Si, double* G,
+                    int32_t* status);
+int dmm_delay_store(dmm_ctx* ctx, int ndelay, int complex_td, int nsample, int nrow, int nbase, const double* Y, const uint8_t* nzt,
+                    const int32_t* status, void* spectrum, uint8_t* mask);
+
 #ifdef __cplusplus
 }
 #endif
