@@ -32,6 +32,7 @@ DMM_DAYENU_F32, DMM_DAYENU_F64 = 0, 1
 DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
 DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
 DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
+DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
 
 
 class DmmError(RuntimeError):
@@ -134,6 +135,12 @@ _SIGS = {
     "dmm_delay_project": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_delay_solve": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_delay_store": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_mfilter_mask": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_mfilter_cov": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_mfilter_pack": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_mfilter_unpack": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_mfilter_solve": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_mfilter_eye": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

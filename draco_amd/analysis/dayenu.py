@@ -1,14 +1,24 @@
-"""DAYENU high-pass delay filter on the GPU (https://arxiv.org/abs/2004.11397).
+"""DAYENU filters on the GPU (https://arxiv.org/abs/2004.11397): the high-pass delay filter along frequency and the
+m-mode filter along right ascension.
 
-Drop-in for the frequency-axis foreground filter of ``draco/analysis/dayenu.py``:
+Drop-in for ``draco/analysis/dayenu.py``:
 
 * :func:`delay_filter`, :func:`highpass_delay_filter`   ``dayenu.py:1125-1232``
 * :class:`DayenuDelayFilter`      ``dayenu.py:20-193``   (``SiderealStream`` / ``TimeStream``)
 * :class:`DayenuDelayFilterMap`   ``dayenu.py:776-975``  (``RingMap``)
+* :class:`DayenuMFilter`          ``dayenu.py:977-1122`` (``SiderealStream``)
+* :func:`bandpass_mmode_filter`, :func:`lowpass_mmode_filter`, :func:`highpass_mmode_filter`, :func:`instantaneous_m`
+  ``dayenu.py:1235-1427``
 
-Same names, config attributes, defaults and ``setup`` / ``process`` signatures.  The arithmetic runs in
+Same names, config attributes, defaults and ``setup`` / ``process`` signatures.  The delay filter's arithmetic runs in
 ``libdraco_amd.so`` (``csrc/dayenu.hip``): a per-item mask pass, a batched float64 Cholesky inverse of the masked
 covariance, and an in-place apply on the f64 matrix cores; the datasets stay on the device.
+
+The m-mode filter (``csrc/mfilter.hip``) has one pair of matrices per frequency, of the order of the RA axis (up to
+4096), and nothing couples frequencies: it shards by frequency.  Its task never forms a filter matrix: per frequency
+and kind the masked covariance is Cholesky-factored in float64 and the real and imaginary rows of the stack entries
+are solved as right-hand sides; only the three builder functions return the matrix, from the same solve on a masked
+identity.  The eigenvalue argument below holds for it too (eigenvalues in about ``[1, 1 / (a epsilon)]``).
 
 The reference takes ``numpy.linalg.pinv`` of the masked covariance.  Its eigenvalue cut, ``1e-15 lambda_max``, keeps
 every eigenvalue of these matrices (the smallest is about 1), so the pseudo-inverse is the inverse of the unflagged
@@ -20,7 +30,7 @@ The filter needs the whole band in one process: frequency sharding does not appl
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``single_mask=False`` (a filter per time
 sample), off-centre (complex) stop bands, the ``DelayCutoff`` file of the ring-map task (HDF5), and the reference's
-``DayenuDelayFilterFixedCutoff``, hybrid-visibility variants and ``DayenuMFilter``.
+``DayenuDelayFilterFixedCutoff`` and hybrid-visibility variants.
 """
 
 from __future__ import annotations
@@ -38,6 +48,7 @@ from ..device import Context, ptr
 from .transform import _dev_dataset
 
 MAX_ORDER = 1024
+MAX_RA = 4096  # order of the m-mode filter (the RA axis)
 _GROUP = {_lib.DMM_DAYENU_F32: 32, _lib.DMM_DAYENU_F64: 16}  # adjacent items per block of the items-contiguous layout
 
 
@@ -330,4 +341,257 @@ class DayenuDelayFilterMap(_DayenuTask):
         return ringmap
 
 
-__all__ = ["DayenuDelayFilter", "DayenuDelayFilterMap", "delay_filter", "highpass_delay_filter"]
+
+def instantaneous_m(ha, lat, dec, u, v, w=0.0):
+    """The instantaneous fringe rate (``dayenu.py:1399-1427``), on the host.
+
+    ``ha``, ``lat`` and ``dec`` in radians; ``u``, ``v``, ``w`` the east-west, north-south and vertical baseline in
+    wavelengths.  Returns ``2 pi d(u . s)/d(ha)`` of the direction ``s`` at that hour angle and declination.
+    """
+    cos_dec, sin_ha = np.cos(dec), np.sin(ha)
+    rate = u * (-1 * cos_dec * np.cos(ha))
+    rate = rate + v * (np.sin(lat) * cos_dec * sin_ha)
+    rate = rate + w * (-1 * np.cos(lat) * cos_dec * sin_ha)
+    return 2.0 * np.pi * rate
+
+
+def _mmode_params(ra, kind, m_cut, m_center, epsilon):
+    """``(diag, coef, m_cut, m_center)`` of ``C = diag I + coef sinc(m_cut dra / pi) cos(m_center dra)`` for the
+    reference's three covariances (``dayenu.py:1267-1279, 1326-1332, 1381-1382``)."""
+    if kind == "highpass":
+        return (1.0, 1.0 / epsilon, float(m_cut), 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a = np.median(np.abs(np.diff(ra))) * m_cut / np.pi
+        aeps = a * epsilon
+        coef = a * (1.0 - 1.0 / aeps)
+        diag = 1.0 / aeps
+    if kind == "bandpass":
+        return (float(diag), float(2 * coef), float(m_cut), float(m_center))
+    return (float(diag), float(coef), float(m_cut), 0.0)
+
+
+def check_mmode_eigenvalue_cut(ra, params):
+    """Raise ``ValueError`` if ``numpy.linalg.pinv``'s cut, ``1e-15 lambda_max``, could reach 0.5, for ``params
+    [..., 4]`` as :func:`_mmode_params` gives them.
+
+    ``lambda_max`` is bounded by the largest absolute row sum, and that by ``|diag| + |coef| (1 + 2 sum_k min(1, 1 /
+    (m_cut k delta)))``, ``k = 1 ... nra - 1``: ``|sinc(x)| <= min(1, 1 / (pi |x|))``, ``|cos| <= 1``, and two RAs ``k``
+    places apart in sorted order are at least ``k delta`` apart, ``delta`` the smallest spacing.  O(nra) per matrix.
+    """
+    ra = np.sort(np.asarray(ra, dtype=np.float64).reshape(-1))
+    par = np.asarray(params, dtype=np.float64).reshape(-1, 4)
+    k = np.arange(1, ra.size, dtype=np.float64)
+    delta = float(np.min(np.diff(ra))) if ra.size > 1 else 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        env = np.minimum(1.0, 1.0 / (np.abs(par[:, 2, np.newaxis]) * k[np.newaxis, :] * delta))
+    bound = np.abs(par[:, 0]) + np.abs(par[:, 1]) * (1.0 + 2.0 * env.sum(axis=1))
+    worst = float(bound.max()) if np.all(np.isfinite(bound)) else np.inf
+    if not 1e-15 * worst < 0.5:
+        raise ValueError(
+            f"DAYENU m-mode filter: 1e-15 x lambda_max may reach {1e-15 * worst:.3g} (row-sum bound), so the reference's "
+            "pseudo-inverse could drop modes that the inverse formed here keeps; choose a larger epsilon"
+        )
+
+
+def _check_nra(who, nra):
+    if not 1 <= nra <= MAX_RA:
+        raise ValueError(f"{who}: {nra} right ascensions, the kernels take 1 ... {MAX_RA}")
+
+
+def _mmode_filter(who, ra, flag, par):
+    """``(pinv, index)`` of the covariance ``par`` for every unique mask of ``flag [..., nra]``."""
+    ra = np.ascontiguousarray(ra, dtype=np.float64).reshape(-1)
+    flag = np.asarray(flag)
+    nra = ra.size
+    assert flag.ndim >= 2 and flag.shape[-1] == nra
+    _check_nra(who, nra)
+    check_mmode_eigenvalue_cut(ra, par)
+    uflag, uindex = np.unique(flag.reshape(-1, nra).astype(bool), return_inverse=True, axis=0)
+    uindex = np.asarray(uindex).reshape(-1)
+    nuniq = uflag.shape[0]
+    ctx = Context.get()
+    lib = _lib.lib
+    ra_d = ctx.to_device(ra)
+    pinv = ctx.empty((nuniq, nra, nra), np.float64)
+    per = max(1, min(65535, (1 << 30) // (8 * nra * nra)))
+    for m0 in range(0, nuniq, per):
+        m1 = min(nuniq, m0 + per)
+        nmat = m1 - m0
+        G = ctx.empty((nmat, nra, nra), np.float64)
+        status = ctx.empty((nmat,), np.int32)
+        mask_d = ctx.to_device(np.ascontiguousarray(uflag[m0:m1], dtype=np.uint8))
+        par_d = ctx.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float64), (nmat, 4))))
+        out = pinv[m0:m1]
+        _lib.check(lib.dmm_mfilter_cov(ctx.handle, nra, nmat, ptr(ra_d), ptr(par_d), ptr(mask_d), ptr(G), ptr(status)))
+        _lib.check(lib.dmm_mfilter_eye(ctx.handle, nra, nmat, 0, ptr(mask_d), ptr(out), ptr(status)))
+        _lib.check(lib.dmm_mfilter_solve(ctx.handle, nra, nra, nmat, ptr(G), ptr(out), ptr(status)))
+        _lib.check(lib.dmm_mfilter_eye(ctx.handle, nra, nmat, 1, ptr(mask_d), ptr(out), ptr(status)))
+        bad = status.cpu().numpy()
+        ctx.uses(G, mask_d, par_d)
+        if bad.any():
+            raise np.linalg.LinAlgError(f"{who}: the covariance of mask {m0 + int(np.flatnonzero(bad)[0])} is not positive definite")
+    ctx.uses(ra_d)
+    index = [np.unravel_index(np.flatnonzero(uindex == uu), flag.shape[:-1]) for uu in range(nuniq)]
+    return pinv, index
+
+
+def bandpass_mmode_filter(ra, m_center, m_cut, flag, epsilon=1e-10):
+    """Construct a band-pass m-mode filter with the pass band ``[m_center - m_cut, m_center + m_cut]``
+    (``dayenu.py:1235-1293``).
+
+    ``ra [nra]`` in radians, ``flag [..., nra]`` with two or more axes.  Returns ``(pinv, index)``: ``pinv [nuniq, nra,
+    nra]`` float64 **on the device**, one filter per unique RA mask, and ``index``, the positions in the leading axes
+    of ``flag`` each applies to (``numpy.unravel_index``, as the reference).  ``nra`` outside 1 ... 4096 raises
+    ``ValueError``; a matrix that is not positive definite raises ``numpy.linalg.LinAlgError``.
+    """
+    return _mmode_filter("bandpass_mmode_filter", ra, flag, _mmode_params(np.asarray(ra, dtype=np.float64), "bandpass", m_cut, m_center, epsilon))
+
+
+def lowpass_mmode_filter(ra, m_cut, flag, epsilon=1e-10):
+    """Construct a low-pass m-mode filter with the pass band ``[-m_cut, m_cut]`` (``dayenu.py:1296-1346``); arguments
+    and result as :func:`bandpass_mmode_filter`."""
+    return _mmode_filter("lowpass_mmode_filter", ra, flag, _mmode_params(np.asarray(ra, dtype=np.float64), "lowpass", m_cut, 0.0, epsilon))
+
+
+def highpass_mmode_filter(ra, m_cut, flag, epsilon=1e-10):
+    """Construct a high-pass m-mode filter with the stop band ``[-m_cut, m_cut]`` (``dayenu.py:1349-1396``); arguments
+    and result as :func:`bandpass_mmode_filter`."""
+    return _mmode_filter("highpass_mmode_filter", ra, flag, _mmode_params(np.asarray(ra, dtype=np.float64), "highpass", m_cut, 0.0, epsilon))
+
+
+class DayenuMFilter(ContainerTask):
+    """Apply a DAYENU band-pass m-mode filter to a sidereal stream (``dayenu.py:977-1122``).
+
+    Attributes
+    ----------
+    dec : float
+        The pass band is centred on the fringe rate of a source on the meridian at this declination, in degrees.
+        Default 40.
+    epsilon : float
+        The stop-band rejection of the filter.  Default 1e-10.
+    fkeep_intra : float
+        Width of the pass band for intra-cylinder baselines as a fraction of the cylinder width.  Default 0.75.
+    fkeep_inter : float
+        The same for inter-cylinder baselines.  Default 0.75.
+    workspace_mib : int
+        Device memory the matrices and right-hand sides of one batch of frequencies may take.  Default 1024.
+
+    Works in place and returns the input container with device-resident ``vis`` and ``vis_weight``.  Per frequency one
+    RA mask serves all baselines (an RA is kept where more than 90 % of the baselines with any weight have weight);
+    the weights are multiplied by it and not propagated through the filter.  A frequency whose factorisation fails
+    keeps its data and loses its weight.  The telescope must give ``feedpositions``, ``cylinder_spacing`` and
+    ``latitude``.
+    """
+
+    _config_names = ("dec", "epsilon", "fkeep_intra", "fkeep_inter", "workspace_mib")
+    dec = 40.0
+    epsilon = 1e-10
+    fkeep_intra = 0.75
+    fkeep_inter = 0.75
+    workspace_mib = 1024
+
+    def setup(self, telescope):
+        """Set the telescope needed to obtain baselines."""
+        self.telescope = io.get_telescope(telescope)
+
+    def _get_cut(self, freq, xsep):
+        """Fringe rate on the meridian at ``dec`` of an east-west separation ``xsep`` (metres) at ``freq`` (MHz)."""
+        lmbda = scipy.constants.c / (freq * 1e6)
+        u = xsep / lmbda
+        return instantaneous_m(0.0, np.radians(self.telescope.latitude), np.radians(self.dec), u, 0.0)
+
+    def process(self, stream):
+        """Filter out m-modes from a SiderealStream, in place."""
+        stream.redistribute("freq")
+        ctx = Context.get()
+        lib = _lib.lib
+        tel = self.telescope
+        spacing = tel.cylinder_spacing
+        ra = np.ascontiguousarray(np.radians(stream.ra[:]), dtype=np.float64)
+        freq = np.asarray(stream.freq[:], dtype=np.float64)
+        prod = stream.prodstack
+        vis = _dev_dataset(stream.vis, ctx, np.complex64)
+        weight = _dev_dataset(stream.weight, ctx, np.float32)
+        nfreq, nstack, nra = (int(s) for s in vis.shape)
+        _check_nra(type(self).__name__, nra)
+        if len(prod) != nstack or freq.size != nfreq or ra.size != nra:
+            raise ValueError(f"{len(prod)} products, {freq.size} frequencies, {ra.size} RAs for a dataset of shape {(nfreq, nstack, nra)}")
+
+        # east-west separation of every stack entry in whole cylinders; the intra-cylinder ones are not fringe-stopped
+        baselines = tel.feedpositions[prod["input_a"], 0] - tel.feedpositions[prod["input_b"], 0]
+        baselines = np.round(baselines / spacing) * spacing
+        db = 0.5 * spacing
+        is_intra = np.abs(baselines) < db
+        entries = [np.flatnonzero(is_intra).astype(np.int32), np.flatnonzero(~is_intra).astype(np.int32)]
+
+        # per frequency: (diag, coef, m_cut, m_center) of the two kinds and the mixer rates of the inter entries
+        par = np.zeros((2, nfreq, 4))
+        mix = np.zeros((nfreq, len(entries[1])))
+        for ff, nu in enumerate(freq):
+            m_cut = np.abs(self._get_cut(nu, db))
+            par[0, ff] = _mmode_params(ra, "bandpass", 0.5 * self.fkeep_intra * m_cut, 0.5 * (2.0 - self.fkeep_intra) * m_cut, self.epsilon)
+            par[1, ff] = _mmode_params(ra, "lowpass", self.fkeep_inter * m_cut, 0.0, self.epsilon)
+            mix[ff] = self._get_cut(nu, baselines[entries[1]])
+        check_mmode_eigenvalue_cut(ra, par)
+
+        flag_d = ctx.empty((nfreq, nra), np.uint8)
+        state_d = ctx.empty((nfreq,), np.int32)
+        _lib.check(lib.dmm_mfilter_mask(ctx.handle, nfreq, nstack, nra, ptr(weight), ptr(flag_d), ptr(state_d)))
+        flags, state = flag_d.cpu().numpy(), state_d.cpu().numpy()
+        todo = np.flatnonzero(state == _lib.DMM_MFILTER_FILTER).astype(np.int32)
+        self.log.debug(f"{nfreq} frequencies, {todo.size} to filter, {int((state == _lib.DMM_MFILTER_UNTOUCHED).sum())} without any weight.")
+
+        ra_d = ctx.to_device(ra)
+        entries_d = [ctx.to_device(e) for e in entries]
+        per = max(1, min(65535, (int(self.workspace_mib) << 20) // (8 * nra * (nra + 2 * nstack))))
+        for b0 in range(0, todo.size, per):
+            fs = todo[b0 : b0 + per]
+            nmat = fs.size
+            fs_d = ctx.to_device(fs)
+            mask_d = ctx.to_device(np.ascontiguousarray(flags[fs]))
+            G = ctx.empty((nmat, nra, nra), np.float64)
+            work = []
+            for kind in (0, 1):
+                nent = int(entries[kind].size)
+                if nent == 0:
+                    continue
+                par_d = ctx.to_device(np.ascontiguousarray(par[kind, fs]))
+                mix_d = ctx.to_device(np.ascontiguousarray(mix[fs])) if kind == 1 else None
+                status = ctx.empty((nmat,), np.int32)
+                Y = ctx.empty((nmat, 2 * nent, nra), np.float64)
+                _lib.check(lib.dmm_mfilter_cov(ctx.handle, nra, nmat, ptr(ra_d), ptr(par_d), ptr(mask_d), ptr(G), ptr(status)))
+                _lib.check(lib.dmm_mfilter_pack(ctx.handle, nra, nstack, nmat, nent, ptr(fs_d), ptr(entries_d[kind]), ptr(mix_d), ptr(ra_d), ptr(mask_d), ptr(status), ptr(vis), ptr(Y)))
+                _lib.check(lib.dmm_mfilter_solve(ctx.handle, nra, 2 * nent, nmat, ptr(G), ptr(Y), ptr(status)))
+                work.append((kind, nent, mix_d, Y, status))
+                ctx.uses(par_d, mix_d, Y, status)
+            # a frequency is written back only if both of its matrices were factored
+            failed = np.zeros(nmat, dtype=np.int32)
+            for _, _, _, _, status in work:
+                failed |= status.cpu().numpy()
+            for i in np.flatnonzero(failed):
+                self.log.error(
+                    f"Failed to factorise the covariance while processing freq {int(fs[i])} [{freq[fs[i]]:0.3f} MHz]\n"
+                    f"Percentage unmasked right ascensions:  {100 * flags[fs[i]].mean():0.1f}"
+                )
+                weight[int(fs[i])].zero_()
+            failed_d = ctx.to_device(failed)
+            for kind, nent, mix_d, Y, _ in work:
+                _lib.check(lib.dmm_mfilter_unpack(ctx.handle, nra, nstack, nmat, nent, ptr(fs_d), ptr(entries_d[kind]), ptr(mix_d), ptr(ra_d), ptr(mask_d), ptr(failed_d), ptr(Y), ptr(vis)))
+            ctx.uses(fs_d, mask_d, G, failed_d)
+        ctx.uses(ra_d, flag_d, state_d, *entries_d)
+        stream.vis.set_device(vis)
+        stream.weight.set_device(weight)
+        return stream
+
+
+__all__ = [
+    "DayenuDelayFilter",
+    "DayenuDelayFilterMap",
+    "DayenuMFilter",
+    "bandpass_mmode_filter",
+    "delay_filter",
+    "highpass_delay_filter",
+    "highpass_mmode_filter",
+    "instantaneous_m",
+    "lowpass_mmode_filter",
+]

@@ -100,6 +100,11 @@ class TransitTelescope:
             self.uniquepairs = np.stack([np.zeros(self.npairs, int), np.arange(self.npairs)], axis=1)
             self._free = True
 
+    @property
+    def cylinder_spacing(self):
+        """East-west distance between cylinder centres in metres, under the name ``DayenuMFilter`` reads."""
+        return self.cyl_sep
+
     def unix_to_lsd(self, unix):
         """Local sidereal day (integer part: day number, fraction: sidereal angle / 360 deg) of UNIX times.
 

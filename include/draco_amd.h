@@ -564,6 +564,44 @@ int dmm_delay_solve(dmm_ctx* ctx, int order, int complex_td, int nsample, int nb
 int dmm_delay_store(dmm_ctx* ctx, int ndelay, int complex_td, int nsample, int nrow, int nbase, const double* Y, const uint8_t* nzt,
                     const int32_t* status, void* spectrum, uint8_t* mask);
 
+/* DAYENU m-mode filter along right ascension (draco/analysis/dayenu.py:977-1122, 1235-1427), csrc/mfilter.hip.  All
+ * arrays [dev]; the order nra is 1 ... 4096 in every call, matrices are batched, at most 65535 per call.
+ *
+ * dmm_mfilter_mask: weight [nfreq][nstack][nra] float32 (in place), nfreq <= 65535.  Per frequency, with gb = the stack
+ * entries that have any weight > 0: flag [nfreq][nra] bytes = (number of gb entries with weight > 0 at that RA) >
+ * 0.90 * len(gb), compared in float64; state [nfreq] int32 = DMM_MFILTER_UNTOUCHED (gb is empty: weight not written,
+ * flag 0), DMM_MFILTER_WEIGHT_ONLY (no RA is kept) or DMM_MFILTER_FILTER; unless untouched, weight *= flag.  nfreq x
+ * nstack bytes come from the context's scratch.
+ *
+ * dmm_mfilter_cov: ra [nra] float64 (radians), params [nmat][4] float64 = (diag, coef, m_cut, m_center), mask
+ * [nmat][nra] bytes (non-zero: RA kept).  G [nmat][nra][nra] float64 = diag d_ij + coef sinc(m_cut (ra_i - ra_j) / pi)
+ * cos(m_center (ra_i - ra_j)) (sinc(x) = sin(pi x) / (pi x), sinc(0) = 1) on the kept RAs, identity on the rows and
+ * columns of the others.  status [nmat] int32 is reset to 0.
+ *
+ * dmm_mfilter_pack / dmm_mfilter_unpack: vis [.][nstack][nra] complex64; matrix t belongs to frequency mat_freq[t]
+ * (int32 [nmat]) and carries the nent stack entries entry [nent] int32.  Y [nmat][2 nent][nra] float64: rows 2 e and
+ * 2 e + 1 are the real and imaginary part of vis[mat_freq[t]][entry[e]] x exp(-i mix[t][e] ra), zero where mask is 0;
+ * mix [nmat][nent] float64 or NULL (no mixer).  Unpack multiplies by the conjugate mixer, rounds once to complex64 and
+ * stores exact zeros where mask is 0.  Both leave a matrix whose status is non-zero alone.
+ *
+ * dmm_mfilter_solve: G = U^T U in place (blocked, float64 matrix cores), then each of the nrow rows of Y
+ * [nmat][nrow][nra] is replaced by the solution of G x = y; nrow may be 0.  A pivot that is not positive sets status to
+ * DMM_MFILTER_NOT_POSDEF and nothing further is computed for that matrix.
+ *
+ * dmm_mfilter_eye, on Y [nmat][nra][nra]: stage 0 writes the masked identity (the right-hand sides that give the
+ * filter matrix itself), stage 1 zeroes the rows and columns where mask is 0 (the whole matrix where status is set). */
+enum { DMM_MFILTER_UNTOUCHED = 0, DMM_MFILTER_WEIGHT_ONLY = 1, DMM_MFILTER_FILTER = 2 };
+enum { DMM_MFILTER_OK = 0, DMM_MFILTER_NOT_POSDEF = 1 };
+int dmm_mfilter_mask(dmm_ctx* ctx, int nfreq, int nstack, int nra, float* weight, uint8_t* flag, int32_t* state);
+int dmm_mfilter_cov(dmm_ctx* ctx, int nra, int nmat, const double* ra, const double* params, const uint8_t* mask, double* G,
+                    int32_t* status);
+int dmm_mfilter_pack(dmm_ctx* ctx, int nra, int nstack, int nmat, int nent, const int32_t* mat_freq, const int32_t* entry,
+                     const double* mix, const double* ra, const uint8_t* mask, const int32_t* status, const void* vis, double* Y);
+int dmm_mfilter_unpack(dmm_ctx* ctx, int nra, int nstack, int nmat, int nent, const int32_t* mat_freq, const int32_t* entry,
+                       const double* mix, const double* ra, const uint8_t* mask, const int32_t* status, const double* Y, void* vis);
+int dmm_mfilter_solve(dmm_ctx* ctx, int nra, int nrow, int nmat, double* G, double* Y, int32_t* status);
+int dmm_mfilter_eye(dmm_ctx* ctx, int nra, int nmat, int stage, const uint8_t* mask, double* Y, const int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
