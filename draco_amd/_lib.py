@@ -33,6 +33,7 @@ DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
 DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
 DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
 DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
+DMM_MFILTER_OK, DMM_MFILTER_NOT_POSDEF = 0, 1
 
 
 class DmmError(RuntimeError):
