@@ -34,6 +34,7 @@ DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
 DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
 DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
 DMM_MFILTER_OK, DMM_MFILTER_NOT_POSDEF = 0, 1
+DMM_DPSS_OK, DMM_DPSS_SKIPPED, DMM_DPSS_NOT_POSDEF = 0, 1, 2
 
 
 class DmmError(RuntimeError):
@@ -142,6 +143,15 @@ _SIGS = {
     "dmm_mfilter_unpack": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmm_mfilter_solve": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "dmm_mfilter_eye": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_dpss_pack": (_i, [_vp, _i, _i, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_dpss_gram": (_i, [_vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp]),
+    "dmm_dpss_project": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_dpss_solve": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "dmm_dpss_variance": (_i, [_vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp, _vp]),
+    "dmm_dpss_synth": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_dpss_gapflag": (_i, [_vp, _i, _i, _vp, _d, _vp]),
+    "dmm_dpss_pchip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_dpss_store": (_i, [_vp, _i, _i, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -105,6 +105,12 @@ class TransitTelescope:
         """East-west distance between cylinder centres in metres, under the name ``DayenuMFilter`` reads."""
         return self.cyl_sep
 
+    @property
+    def freq_start(self):
+        """The highest frequency of the band in MHz, under the name ``DPSSFilterMMode`` reads (driftscan's band runs
+        from ``freq_start`` down to ``freq_end``)."""
+        return float(self.frequencies.max())
+
     def unix_to_lsd(self, unix):
         """Local sidereal day (integer part: day number, fraction: sidereal angle / 360 deg) of UNIX times.
 

@@ -602,6 +602,46 @@ int dmm_mfilter_unpack(dmm_ctx* ctx, int nra, int nstack, int nmat, int nent, co
 int dmm_mfilter_solve(dmm_ctx* ctx, int nra, int nrow, int nmat, double* G, double* Y, int32_t* status);
 int dmm_mfilter_eye(dmm_ctx* ctx, int nra, int nmat, int stage, const uint8_t* mask, double* Y, const int32_t* status);
 
+/* DPSS gap inpainting (draco/util/dpss.py:121-443, draco/analysis/interpolate.py), csrc/dpss.hip.  A batch is nb <=
+ * 65535 columns of n = 1 ... 4096 samples that share one real basis A [n][k] float64 row-major, k = 1 ... n (At [k][n]
+ * is its transpose).  All arrays [dev] except `layout`; everything between pack and store is float64 in packed rows:
+ * X [nb][2][n] (real row, imaginary row), Ni [nb][n], W [nb][n] bytes, xhat [nb][2], B [nb][2][k], C [nb][k][k] (only
+ * the upper triangle is written and read), Z [nb][n][k], var / wout [nb][n], F [nb][2][n], status [nb] int32.
+ *
+ * layout [4] int64 (host) = (ninner, stride_outer, stride_inner, stride_samp), in elements of vis (complex64) and of
+ * weight (float32) alike: column c starts at (c / ninner) stride_outer + (c % ninner) stride_inner and its samples are
+ * stride_samp apart; cols [nb] int64 names the column of every slot.  With stride_samp = 1 the lanes of a wave run along
+ * the samples, otherwise along adjacent slots (which should then be adjacent columns).
+ *
+ * dmm_dpss_pack: X, Ni = the column's values, W = wext (bytes in the weights' layout) or weight > 0 where wext is NULL,
+ * xhat = sum(W x) / sum(W) (0 where no W), status = DMM_DPSS_SKIPPED where every weight is zero, else DMM_DPSS_OK.
+ * dmm_dpss_gram: C = A^T diag(Ni) A + eps I (f64 MFMA).  dmm_dpss_project: B = A^T (Ni o (x - xhat)), the mean
+ * removed on load.  dmm_dpss_solve: C = U^T U in place, then B <- C^-1 B; a pivot that is not positive sets status to
+ * DMM_DPSS_NOT_POSDEF; slots whose status is set are left alone (B of a skipped slot is already zero).
+ * dmm_dpss_variance (after solve): Z <- C^-1 a_i for the rows a_i of A, var_i = a_i . z_i - eps |z_i|^2, the diagonal
+ * of F N F^H with F = A C^-1 A^T Ni (dpss.py:236-246).  dmm_dpss_synth: F = A B.
+ * dmm_dpss_gapflag: keep [nb][n] bytes = flag_above_cutoff(valid, fc) of dpss.py:307-356 along n (nb unbounded).
+ * dmm_dpss_pchip: wout = inz(var + max(p, 0)), p SciPy's PchipInterpolator of inz(Ni) through the samples where W is
+ * set, evaluated (and extrapolated) at every sample index; no p with fewer than two such samples; var counts as zero
+ * in a skipped slot; wout = 0 in a slot that is not positive definite (nb unbounded).
+ * dmm_dpss_store: vis = F + xhat, weight = wout, rounded once to complex64 / float32; with inpaint != 0 the samples
+ * where W is set get X and Ni back; weight = 0 where keep (may be NULL) is 0; a slot that is not positive definite
+ * gets X back and weight 0.  vis / weight may be the arrays pack read or others of the same layout. */
+enum { DMM_DPSS_OK = 0, DMM_DPSS_SKIPPED = 1, DMM_DPSS_NOT_POSDEF = 2 };
+int dmm_dpss_pack(dmm_ctx* ctx, int n, int nb, const int64_t* layout, const int64_t* cols, const void* vis, const float* weight,
+                  const uint8_t* wext, double* X, double* Ni, uint8_t* W, double* xhat, int32_t* status);
+int dmm_dpss_gram(dmm_ctx* ctx, int n, int k, int nb, const double* A, const double* Ni, double eps, double* C, const int32_t* status);
+int dmm_dpss_project(dmm_ctx* ctx, int n, int k, int nb, const double* A, const double* X, const double* Ni, const double* xhat, double* B);
+int dmm_dpss_solve(dmm_ctx* ctx, int k, int nb, double* C, double* B, int32_t* status);
+int dmm_dpss_variance(dmm_ctx* ctx, int n, int k, int nb, const double* A, const double* C, double eps, double* Z, double* var,
+                      const int32_t* status);
+int dmm_dpss_synth(dmm_ctx* ctx, int n, int k, int nb, const double* At, const double* B, double* F);
+int dmm_dpss_gapflag(dmm_ctx* ctx, int n, int nb, const uint8_t* valid, double fc, uint8_t* keep);
+int dmm_dpss_pchip(dmm_ctx* ctx, int n, int nb, const double* Ni, const uint8_t* W, const double* var, const int32_t* status, double* wout);
+int dmm_dpss_store(dmm_ctx* ctx, int n, int nb, const int64_t* layout, const int64_t* cols, const double* F, const double* xhat,
+                   const double* X, const double* Ni, const uint8_t* W, const double* wout, const uint8_t* keep, const int32_t* status,
+                   int inpaint, void* vis, float* weight);
+
 #ifdef __cplusplus
 }
 #endif
