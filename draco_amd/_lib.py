@@ -35,6 +35,8 @@ DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 
 DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
 DMM_MFILTER_OK, DMM_MFILTER_NOT_POSDEF = 0, 1
 DMM_DPSS_OK, DMM_DPSS_SKIPPED, DMM_DPSS_NOT_POSDEF = 0, 1, 2
+DMM_SRCBEAM_INVERSE_VARIANCE, DMM_SRCBEAM_NATURAL, DMM_SRCBEAM_UNIFORM = 0, 1, 2
+DMM_SRCBEAM_W_F32, DMM_SRCBEAM_W_F64 = 0, 1
 
 
 class DmmError(RuntimeError):
@@ -152,6 +154,9 @@ _SIGS = {
     "dmm_dpss_gapflag": (_i, [_vp, _i, _i, _vp, _d, _vp]),
     "dmm_dpss_pchip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_dpss_store": (_i, [_vp, _i, _i, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "dmm_srcbeam_prepare": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_srcbeam_form": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "dmm_srcbeam_collapse": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -662,6 +662,148 @@ class DelayTransform(DelayContainer):
         return self.datasets["weight"]
 
 
+_POSITION_DTYPE = np.dtype([("ra", np.float64), ("dec", np.float64)])
+_REDSHIFT_DTYPE = np.dtype([("z", np.float64), ("z_error", np.float64)])
+
+
+class SourceCatalog(ContainerBase):
+    """A catalogue of sources: the table ``position [object_id]`` with columns ``ra``, ``dec`` in degrees
+    (``containers.py:2745-2758``)."""
+
+    _axes = ("object_id",)
+    _dataset_spec = {"position": {"axes": ["object_id"], "dtype": _POSITION_DTYPE}}
+
+    @property
+    def position(self):
+        return self.datasets["position"]
+
+
+class SpectroscopicCatalog(SourceCatalog):
+    """A catalogue with the table ``redshift [object_id]``, columns ``z``, ``z_error``, beside ``position``
+    (``containers.py:2761-2769``)."""
+
+    _dataset_spec = {
+        "position": {"axes": ["object_id"], "dtype": _POSITION_DTYPE},
+        "redshift": {"axes": ["object_id"], "dtype": _REDSHIFT_DTYPE},
+    }
+
+    @property
+    def redshift(self):
+        return self.datasets["redshift"]
+
+
+class FormedBeam(ContainerBase, _FreqMixin):
+    """Formed beams: ``beam`` and ``weight [object_id, pol, freq]`` float64, ``position [object_id]`` and the optional
+    ``redshift [object_id]`` (``containers.py:2772-2840``)."""
+
+    _axes = ("object_id", "pol", "freq")
+    _dataset_spec = {
+        "beam": {"axes": ["object_id", "pol", "freq"], "dtype": np.float64},
+        "weight": {"axes": ["object_id", "pol", "freq"], "dtype": np.float64},
+        "position": {"axes": ["object_id"], "dtype": _POSITION_DTYPE},
+    }
+    _optional_spec = {"redshift": {"axes": ["object_id"], "dtype": _REDSHIFT_DTYPE}}
+
+    def __init__(self, **kwargs):
+        self._dataset_spec = dict(type(self)._dataset_spec)
+        super().__init__(**kwargs)
+
+    def add_dataset(self, name, allocate=True):
+        self._dataset_spec[name] = self._optional_spec[name]
+        if allocate:
+            self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=self._optional_spec[name]["dtype"]), attrs={"axis": self._optional_spec[name]["axes"]})
+
+    @property
+    def beam(self):
+        return self.datasets["beam"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+    @property
+    def position(self):
+        return self.datasets["position"]
+
+    @property
+    def redshift(self):
+        if "redshift" in self.datasets:
+            return self.datasets["redshift"]
+        raise KeyError("Dataset 'redshift' not initialised.")
+
+    @property
+    def frequency(self):
+        return self.index_map["freq"]
+
+    @property
+    def id(self):
+        return self.index_map["object_id"]
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+
+class FormedBeamHA(FormedBeam):
+    """Formed beams that keep the hour-angle axis: ``beam`` and ``weight [object_id, pol, freq, ha]`` float64 and
+    ``object_ha [object_id, ha]``, which ``.ha`` returns (``containers.py:2843-2883``)."""
+
+    _axes = ("object_id", "pol", "freq", "ha")
+    _dataset_spec = {
+        "beam": {"axes": ["object_id", "pol", "freq", "ha"], "dtype": np.float64},
+        "weight": {"axes": ["object_id", "pol", "freq", "ha"], "dtype": np.float64},
+        "position": {"axes": ["object_id"], "dtype": _POSITION_DTYPE},
+        "object_ha": {"axes": ["object_id", "ha"], "dtype": np.float64},
+    }
+
+    @property
+    def ha(self):
+        return self.datasets["object_ha"]
+
+
+class GridBeam(ContainerBase, _FreqMixin):
+    """A beam on a rectangular grid: ``beam [freq, pol, input, theta, phi]`` complex64, ``weight`` float32 of the same
+    shape, ``attrs["coords"]`` (``containers.py:883-954``; ``quality`` and ``gain`` are not carried)."""
+
+    _axes = ("freq", "pol", "input", "theta", "phi")
+    _dataset_spec = {
+        "beam": {"axes": ["freq", "pol", "input", "theta", "phi"], "dtype": np.complex64},
+        "weight": {"axes": ["freq", "pol", "input", "theta", "phi"], "dtype": np.float32},
+    }
+
+    def __init__(self, coords="celestial", **kwargs):
+        super().__init__(**kwargs)
+        self.attrs["coords"] = coords
+
+    @property
+    def beam(self):
+        return self.datasets["beam"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+    @property
+    def coords(self):
+        return self.attrs["coords"]
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+    @property
+    def input(self):
+        return self.index_map["input"]
+
+    @property
+    def theta(self):
+        return self.index_map["theta"]
+
+    @property
+    def phi(self):
+        return self.index_map["phi"]
+
+
 def _all_containers():
     found, todo = [], [ContainerBase]
     while todo:

@@ -74,3 +74,77 @@ def window_generalised(x, window="nuttall"):
         w = np.polynomial.chebyshev.chebval(np.cos(2.0 * np.pi * x), _WINDOW_COEFFS[window])
     inside = (x >= 0) & (x <= 1)
     return np.where(inside, w, 0.0)
+
+
+def _fields(table, count):
+    """The first ``count`` columns of a structured or two-dimensional table, as integer arrays."""
+    table = np.asarray(table)
+    if table.dtype.names:
+        return [table[name].astype(np.int64) for name in table.dtype.names[:count]]
+    return [table[..., c].astype(np.int64) for c in range(count)]
+
+
+def calculate_redundancy(input_flags, prod_map, stack_index, nstack):
+    """How many products with two good inputs went into every stack entry at every time: float32 ``[nstack, ntime]``
+    (``tools.calculate_redundancy`` of the reference, computed here on the host in one scatter-add).
+
+    ``input_flags [ninput, ntime]`` is non-zero where an input is good; flags that are zero everywhere count as all
+    good.  ``prod_map [nprod]`` holds the input pairs and ``stack_index [nprod]`` the stack entry of every product; a
+    product whose entry lies outside ``0 ... nstack - 1`` was not stacked.  A product index outside the inputs raises
+    ``RuntimeError``, tables of different lengths ``ValueError``."""
+    good = np.asarray(input_flags, dtype=np.float32)
+    if not good.any():
+        good = np.ones_like(good)
+    first, second = _fields(prod_map, 2)
+    entry = np.asarray(stack_index).astype(np.int64)
+    if entry.shape[0] != first.shape[0]:
+        raise ValueError(f"Number of prod_map rows ({first.shape[0]}) must match stack_index length ({entry.shape[0]}).")
+    if first.size and (min(first.min(), second.min()) < 0 or max(first.max(), second.max()) >= good.shape[0]):
+        raise RuntimeError("Input index in prod_map out of bounds.")
+    stacked = np.flatnonzero((entry >= 0) & (entry < nstack))
+    count = np.zeros((int(nstack), good.shape[1]), dtype=np.float32)
+    # (np.add.at takes repeated entries one after the other, in product order)
+    np.add.at(count, entry[stacked], good[first[stacked]] * good[second[stacked]])
+    return count
+
+
+def _stack_feeds(index_map):
+    """The two inputs (as the telescope numbers them) of the representative product of every stack entry."""
+    inputs = np.asarray(index_map["input"][:])
+    if inputs.dtype.names and "chan_id" in inputs.dtype.names:
+        inputs = inputs["chan_id"]
+    (rep,) = _fields(index_map["stack"][:], 1)
+    first, second = _fields(index_map["prod"][:], 2)
+    return inputs[first[rep]].astype(np.int64), inputs[second[rep]].astype(np.int64)
+
+
+def polarization_map(index_map, telescope, exclude_autos=True):
+    """For every entry of ``index_map['stack']`` its place in ``['XX', 'XY', 'YX', 'YY']``, or -1 (``tools.
+    polarization_map`` of the reference, vectorised over the stack axis).
+
+    The two letters come from ``telescope.beamclass`` of the representative product's inputs (0: X, 1: Y, anything
+    else: -1) and swap where ``telescope.feedconj`` marks the pair as conjugated.  Auto-correlations give -1 unless
+    ``exclude_autos`` is off.  A telescope whose ``stack_type`` is set and is not ``"redundant"`` raises
+    ``RuntimeError``."""
+    kind = getattr(telescope, "stack_type", None)
+    if kind is not None and kind != "redundant":
+        raise RuntimeError(f"Telescope stack type needs to be 'redundant'. Is {kind}")
+    a, b = _stack_feeds(index_map)
+    beamclass = np.asarray(telescope.beamclass)
+    ca, cb = beamclass[a], beamclass[b]
+    swap = np.asarray(telescope.feedconj[a, b], dtype=bool)
+    lead, trail = np.where(swap, cb, ca), np.where(swap, ca, cb)
+    polmap = (2 * lead + trail).astype(int)  # XX, XY, YX, YY in this order
+    polmap[~(np.isin(ca, (0, 1)) & np.isin(cb, (0, 1)))] = -1
+    if exclude_autos:
+        polmap[a == b] = -1
+    return polmap
+
+
+def baseline_vector(index_map, telescope):
+    """Baseline in metres of every entry of ``index_map['stack']``, shape ``(2, nstack)`` float64 (``tools.
+    baseline_vector`` of the reference, vectorised): the telescope's unique baseline of the representative product,
+    ``telescope.baselines[telescope.feedmap[a, b]]``, which already carries the conjugation."""
+    a, b = _stack_feeds(index_map)
+    unique = np.asarray(telescope.feedmap[a, b], dtype=np.int64)
+    return np.ascontiguousarray(np.asarray(telescope.baselines, dtype=np.float64)[unique].T)

@@ -642,6 +642,40 @@ int dmm_dpss_store(dmm_ctx* ctx, int n, int nb, const int64_t* layout, const int
                    const double* X, const double* Ni, const uint8_t* W, const double* wout, const uint8_t* keep, const int32_t* status,
                    int inpaint, void* vis, float* weight);
 
+/* Source beamforming (draco/analysis/beamform.py:139-385, draco/util/_fast_tools.pyx:211-290), csrc/srcbeam.hip.  All
+ * arrays [dev].  A dataset is vis [nfreq][nstack][nra] complex64 and weight of the same shape float32; one processed
+ * polarisation is the nsel stacks sel [nsel] int32 of it.
+ *
+ * dmm_srcbeam_prepare: visT [nfreq][nra][nsel] complex64 = the polarisation's visibilities with the stacks contiguous,
+ * ws (same shape, float32) = the weight of the sum: the visibility weight (DMM_SRCBEAM_INVERSE_VARIANCE),
+ * (weight > 0) redundancy [nstack][nra] (DMM_SRCBEAM_NATURAL) or (weight > 0)(redundancy > 0) (DMM_SRCBEAM_UNIFORM);
+ * SW [nfreq][nra] = sum_k ws, SW2 = sum_k ws^2 inz(weight), float64.  redundancy may be NULL for inverse variance;
+ * sel, visT and ws may be NULL when nsel = 0 (a polarisation without stacks: SW = SW2 = 0).
+ *
+ * dmm_srcbeam_form: for a chunk of nsrc sources with windows of nha slots,
+ *   F [nsrc][nfreq][nha] = sum_k ws[f][ra][k] Re(visT[f][ra][k] exp(2 pi i (u[f][k] ut[s][j] + v[f][k] vt[s][j])))
+ * float64, u / v [nfreq][nsel] the baselines in wavelengths, ut = cos(dec) sin(ha), vt = -(cos(lat) sin(dec) -
+ * sin(lat) cos(dec) cos(ha)) [nsrc][nha].  ws is float32 (DMM_SRCBEAM_W_F32) or float64 (DMM_SRCBEAM_W_F64).  Which
+ * slots exist and which sample each reads is the inverted window list: pair_id [npair] int32 = s nha + j sorted by the
+ * sample they read, pair_start [nra + 1] int32 the first pair of every sample.  fmask [nsrc][nfreq] bytes (may be NULL):
+ * frequencies a source does not process stay zero, as do slots no pair names.  nha <= nra.
+ *
+ * dmm_srcbeam_collapse: F and pb [npol][nsrc][nfreq][nha] (pb NULL: ones), SW / SW2 [npol][nfreq][nra], ra_index
+ * [nsrc][nha] int32 the sample of every slot (outside 0 ... nra - 1: no such slot), rows [nsrc] int64 the output row of
+ * every source (< nobj).  With collapse_ha: beam [nobj][npo][nfreq] = sum_j F pb inz(sum_j SW pb^2), weight = 2 (sum_j SW
+ * pb^2)^2 inz(sum_j SW2 pb^2), or 2 sum_j SW pb^2 with inverse_variance; without: beam [nobj][npo][nfreq][nha] = F inz(SW),
+ * weight = 2 SW^2 inz(SW2) or 2 SW, zero where there is no slot.  Weight is zero where fmask is.  With stokes_i npo = 1
+ * and beam = sum_p beam_p weight_p inz(sum_p weight_p), weight = sum_p weight_p; otherwise npo = npol. */
+enum { DMM_SRCBEAM_INVERSE_VARIANCE = 0, DMM_SRCBEAM_NATURAL = 1, DMM_SRCBEAM_UNIFORM = 2 };
+enum { DMM_SRCBEAM_W_F32 = 0, DMM_SRCBEAM_W_F64 = 1 };
+int dmm_srcbeam_prepare(dmm_ctx* ctx, int nfreq, int nstack, int nra, int nsel, const int32_t* sel, int mode, const void* vis, const float* weight,
+                        const float* redundancy, void* visT, float* ws, double* SW, double* SW2);
+int dmm_srcbeam_form(dmm_ctx* ctx, int nfreq, int nra, int nsel, int wtype, const void* visT, const void* ws, const double* u, const double* v, int nsrc, int nha,
+                     const double* ut, const double* vt, const uint8_t* fmask, int64_t npair, const int32_t* pair_start, const int32_t* pair_id, double* F);
+int dmm_srcbeam_collapse(dmm_ctx* ctx, int nfreq, int nra, int npol, int nsrc, int nha, int collapse_ha, int inverse_variance, int stokes_i, const double* F,
+                         const double* pb, const double* SW, const double* SW2, const int32_t* ra_index, const uint8_t* fmask, const int64_t* rows, int64_t nobj,
+                         double* beam, double* weight);
+
 #ifdef __cplusplus
 }
 #endif
