@@ -12,6 +12,8 @@
 //               of the panel in registers, the rows above arrive through LDS; a non-positive pivot sets status[mat];
 //   k_dy_inv    V = U^-1 by back substitution, one lane per column;
 //   k_dy_prod   NF = (V V^T) o (flag x flag) on v_mfma_f64_16x16x4_f64, 64 x 64 tiles (zero where status is set).
+// The factorisation of a diagonal block, the forward substitution of a panel column and the tile product are the
+// inline pieces of chol_blocked.h, the same code the blocked solver of chol_blocked.hip runs.
 // Apply (the hot path), k_dy_apply: a block stages a stripe of columns of its item(s), every frequency, in LDS (so the
 // product can be written back in place), then walks the rows of NF: the A operand streams from global memory one
 // K-chunk ahead, the B operand comes from the stripe, f64 MFMA accumulates, the store rounds once to the container's
@@ -20,16 +22,13 @@
 // item) and items contiguous (ring map: map [.., freq, ra, el], a stripe = 16 adjacent el of one RA sample, whole lines;
 // the columns of a stripe may belong to different matrices: one MFMA pass per distinct matrix with the other columns
 // zeroed).
-#include "dmm_internal.h"
+#include "chol_blocked.h"
 
 #include <algorithm>
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 constexpr int kDyMaxOrder = 1024;
-constexpr int kNB = 32;  // panel height of the Cholesky factorisation
 
 __device__ __forceinline__ double dy_sinc(double x) { return x == 0.0 ? 1.0 : sinpi(x) / (M_PI * x); }
 
@@ -50,29 +49,29 @@ __global__ void k_dy_cov(int n, int nband, const double* __restrict__ freq, cons
 
 // blockDim.x = n rounded up to 64: thread i owns column i.
 __global__ __launch_bounds__(1024) void k_dy_chol(int n, double* __restrict__ Aall, int32_t* __restrict__ status) {
-  __shared__ double sU[kNB][kNB];
-  __shared__ double sD[kNB][kNB + 1];
+  __shared__ double sU[kDB][kDB];
+  __shared__ double sD[kDB][kDB + 1];
   double* A = Aall + (size_t)blockIdx.x * n * n;
   const int i = threadIdx.x;
-  for (int J0 = 0; J0 < n; J0 += kNB) {
-    const int nb = min(kNB, n - J0);
+  for (int J0 = 0; J0 < n; J0 += kDB) {
+    const int nb = min(kDB, n - J0);
     const bool active = i >= J0 && i < n;
-    double acc[kNB];
+    double acc[kDB];
 #pragma unroll
-    for (int c = 0; c < kNB; ++c) acc[c] = (active && c < nb) ? A[(size_t)(J0 + c) * n + i] : 0.0;
+    for (int c = 0; c < kDB; ++c) acc[c] = (active && c < nb) ? A[(size_t)(J0 + c) * n + i] : 0.0;
     // ---- acc[c] = A[J0 + c][i] - sum_{k < J0} U[k][J0 + c] U[k][i]
-    for (int k0 = 0; k0 < J0; k0 += kNB) {
+    for (int k0 = 0; k0 < J0; k0 += kDB) {
       __syncthreads();
-      for (int e = threadIdx.x; e < kNB * kNB; e += blockDim.x) {
-        const int kk = e / kNB, c = e % kNB;
+      for (int e = threadIdx.x; e < kDB * kDB; e += blockDim.x) {
+        const int kk = e / kDB, c = e % kDB;
         sU[kk][c] = c < nb ? A[(size_t)(k0 + kk) * n + J0 + c] : 0.0;
       }
       __syncthreads();
       if (active) {
-        for (int kk = 0; kk < kNB; ++kk) {
+        for (int kk = 0; kk < kDB; ++kk) {
           const double a = A[(size_t)(k0 + kk) * n + i];
 #pragma unroll
-          for (int c = 0; c < kNB; ++c) acc[c] = fma(-a, sU[kk][c], acc[c]);
+          for (int c = 0; c < kDB; ++c) acc[c] = fma(-a, sU[kk][c], acc[c]);
         }
       }
     }
@@ -80,41 +79,19 @@ __global__ __launch_bounds__(1024) void k_dy_chol(int n, double* __restrict__ Aa
     __syncthreads();
     if (active && i < J0 + nb) {
 #pragma unroll
-      for (int c = 0; c < kNB; ++c) sD[c][i - J0] = acc[c];
+      for (int c = 0; c < kDB; ++c) sD[c][i - J0] = acc[c];
     }
     __syncthreads();
-    for (int c = 0; c < nb; ++c) {
-      const double d = sD[c][c];
-      if (!(d > 0.0)) {  // (the same value in every thread: the whole block leaves)
-        if (threadIdx.x == 0) status[blockIdx.x] = 1;
-        return;
-      }
-      const double r = sqrt(d);
-      __syncthreads();
-      if (i == c) sD[c][c] = r;
-      if (i > c && i < nb) sD[c][i] = sD[c][i] / r;
-      __syncthreads();
-      for (int e = threadIdx.x; e < nb * nb; e += blockDim.x) {
-        const int rr = e / nb, cc = e % nb;
-        if (rr > c && cc >= rr) sD[rr][cc] = fma(-sD[c][rr], sD[c][cc], sD[rr][cc]);
-      }
-      __syncthreads();
+    if (dl_potrf_lds(sD, nb, blockDim.x)) {  // (the whole block leaves)
+      if (threadIdx.x == 0) status[blockIdx.x] = 1;
+      return;
     }
     // ---- the panel's rows: Ud^T x = acc, column by column
     if (active) {
       if (i < J0 + nb) {
         for (int c = 0; c <= i - J0; ++c) A[(size_t)(J0 + c) * n + i] = sD[c][i - J0];
       } else {
-#pragma unroll
-        for (int c = 0; c < kNB; ++c) {
-          if (c < nb) {
-            double s = acc[c];
-#pragma unroll
-            for (int q = 0; q < c; ++q) s = fma(-sD[q][c], acc[q], s);
-            acc[c] = s / sD[c][c];
-            A[(size_t)(J0 + c) * n + i] = acc[c];
-          }
-        }
+        dl_fwd_col(sD, nb, acc, [&](int c, double x) { A[(size_t)(J0 + c) * n + i] = x; });
       }
     }
     __syncthreads();
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(64) void k_dy_inv(int n, const double* __restrict__
 
 // NF(I, J) = sum_{k >= max(i, j)} V[i][k] V[j][k], masked: one 64 x 64 tile per block, 4 waves of 2 x 2 MFMA tiles.
 __global__ __launch_bounds__(256) void k_dy_prod(int n, const double* __restrict__ Vall, const uint8_t* __restrict__ mask, const int32_t* __restrict__ status, double* __restrict__ NFall) {
-  constexpr int KC = 16, LP = KC + 1;
+  constexpr int KC = kTileK, LP = kTileLP;
   __shared__ double xs[64 * LP];
   __shared__ double ys[64 * LP];
   const int mat = blockIdx.y;
@@ -153,8 +130,6 @@ __global__ __launch_bounds__(256) void k_dy_prod(int n, const double* __restrict
   double* NF = NFall + (size_t)mat * n * n;
   const uint8_t* mk = mask + (size_t)mat * n;
   const bool ok = status[mat] == 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4;
   const v4d vz = (v4d){0.0, 0.0, 0.0, 0.0};
   v4d acc[2][2] = {{vz, vz}, {vz, vz}};
   const int r = threadIdx.x >> 2, c0 = (threadIdx.x & 3) * 4;
@@ -168,30 +143,13 @@ __global__ __launch_bounds__(256) void k_dy_prod(int n, const double* __restrict
         ys[r * LP + c0 + c] = (rj < n && k < n && k >= rj) ? V[(size_t)rj * n + k] : 0.0;
       }
       __syncthreads();
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        double a[2], b[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          a[t] = xs[(32 * wr + 16 * t + lr) * LP + kk + lk];
-          b[t] = ys[(32 * wc + 16 * t + lr) * LP + kk + lk];
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-          for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], acc[ti][tj], 0, 0, 0);
-      }
+      dl_tile_mma(xs, ys, acc);
     }
   }
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int row = I0 + 32 * wr + 16 * ti + lk + 4 * reg, col = J0 + 32 * wc + 16 * tj + lr;
-        if (row < n && col < n) NF[(size_t)row * n + col] = (ok && mk[row] && mk[col]) ? acc[ti][tj][reg] : 0.0;
-      }
+  dl_tile_each(acc, [&](int tr, int tc, double v) {
+    const int row = I0 + tr, col = J0 + tc;
+    if (row < n && col < n) NF[(size_t)row * n + col] = (ok && mk[row] && mk[col]) ? v : 0.0;
+  });
 }
 
 struct DySide {

@@ -22,7 +22,8 @@
 //   k_dl_trsm     the 32 x 32 diagonal step of Z U = Y and X U^T = Z, one right-hand side per thread (the sample rows);
 //   k_dl_store    spectrum[b, s, :] = fftshift(x) as complex128, zeros outside the retained samples, the mask bytes.
 // Every kernel after k_dl_prep leaves a baseline alone once its status word is set.  k_dl_gemm, k_dl_potrf, k_dl_panel,
-// k_dl_trsm and their host loops live in chol_blocked.h, which mfilter.hip shares.
+// k_dl_trsm and their host loops (dl_gemm, dl_factor, dl_solve_rows) are compiled once, in chol_blocked.hip, and
+// reached through chol_blocked.h; mfilter.hip and dpss.hip call the same copy.
 #include "chol_blocked.h"
 
 namespace {

@@ -17,10 +17,12 @@
 //   k_dp_pack     stream -> X [nb][2][n] (real and imaginary rows, unchanged values), Ni, W, xhat, status (skipped);
 //                 lanes run along the axis that is contiguous in the stream (columns or samples);
 //   k_dp_gram     C = A^T diag(Ni) A + Si I on v_mfma_f64_16x16x4_f64, 64 x 64 upper tiles, four columns per block: a
-//                 16-sample slice of A is staged in LDS once and scaled by each column's Ni on the way to the registers;
+//                 16-sample slice of A is staged in LDS once and scaled by each column's Ni on the way to the registers
+//                 (the tile product and its epilogue map are dl_tile_mma / dl_tile_each of chol_blocked.h);
 //   k_dp_apply    out[j] = sum_s M[s][j] v[s] for eight vectors (four columns, real and imaginary) per block: the
 //                 projection (M = A, v = Ni o (x - xhat) formed on load) and the synthesis A b (M = A^T);
-//   chol_blocked.h   C = U^T U, the solve of the two rows of xp, and the solve of the n rows of A for the variance;
+//   chol_blocked.hip   C = U^T U, the solve of the two rows of xp, and the solve of the n rows of A for the variance
+//                 (dl_factor and dl_solve_rows: the one compiled copy that delay.hip and mfilter.hip call too);
 //   k_dp_var      var_i = a_i . y_i - Si |y_i|^2, one wave per row;
 //   k_dp_gap      the gap-width pass of flag_above_cutoff (dpss.py:307-356), one wave per column;
 //   k_dp_pchip    SciPy's PchipInterpolator of inz(Ni) through the valid samples, evaluated at every sample, one wave
@@ -110,15 +112,13 @@ __global__ __launch_bounds__(512) void k_dp_pack(DpPack a) {
 // C[b] = A^T diag(Ni[b]) A + eps I, upper 64 x 64 tiles; kDpGramCols columns per block share the staged slice of A.
 __global__ __launch_bounds__(256) void k_dp_gram(int n, int k, int nb, const double* __restrict__ A, const double* __restrict__ Ni, double eps, double* __restrict__ C,
                                                  const int32_t* __restrict__ status) {
-  constexpr int KC = 16, LP = KC + 1;
+  constexpr int KC = kTileK, LP = kTileLP;
   __shared__ double as[64 * LP];
   __shared__ double bs[64 * LP];
   __shared__ double ns[kDpGramCols][KC];
   const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
   if (m0 > n0) return;
   const int64_t b0 = (int64_t)blockIdx.z * kDpGramCols;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4;
   const v4d vz = (v4d){0.0, 0.0, 0.0, 0.0};
   v4d acc[kDpGramCols][2][2];
 #pragma unroll
@@ -138,39 +138,16 @@ __global__ __launch_bounds__(256) void k_dp_gram(int n, int k, int nb, const dou
       ns[c][kk] = (b0 + c < nb && s0 + kk < n) ? Ni[(size_t)(b0 + c) * n + s0 + kk] : 0.0;
     }
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        a[t] = as[(32 * wr + 16 * t + lr) * LP + kk + lk];
-        b[t] = bs[(32 * wc + 16 * t + lr) * LP + kk + lk];
-      }
-#pragma unroll
-      for (int c = 0; c < kDpGramCols; ++c) {
-        const double w = ns[c][kk + lk];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-          const double aw = a[ti] * w;
-#pragma unroll
-          for (int tj = 0; tj < 2; ++tj) acc[c][ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, b[tj], acc[c][ti][tj], 0, 0, 0);
-        }
-      }
-    }
+    dl_tile_mma<kDpGramCols>(as, bs, acc, [&](int c, double a, int kk) { return a * ns[c][kk]; });
   }
 #pragma unroll
   for (int c = 0; c < kDpGramCols; ++c) {
     if (b0 + c >= nb || status[b0 + c]) continue;
     double* Cb = C + (size_t)(b0 + c) * k * k;
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int row = m0 + 32 * wr + 16 * ti + lk + 4 * reg, col = n0 + 32 * wc + 16 * tj + lr;
-          if (row < k && col < k) Cb[(size_t)row * k + col] = acc[c][ti][tj][reg] + (row == col ? eps : 0.0);
-        }
+    dl_tile_each(acc[c], [&](int r, int cc, double v) {
+      const int row = m0 + r, col = n0 + cc;
+      if (row < k && col < k) Cb[(size_t)row * k + col] = v + (row == col ? eps : 0.0);
+    });
   }
 }
 

@@ -16,13 +16,16 @@
 //                 exp(-i m ra), zero at masked RAs; k_mf_unpack undoes the mixer, rounds to complex64, exact zeros at
 //                 masked RAs.  RA is the contiguous axis on both sides: a wave moves 512 contiguous bytes of vis and
 //                 two runs of 512 bytes of Y;
-//   chol_blocked.h   G = U^T U and the two triangular solves on the rows of Y (shared with delay.hip);
+//   chol_blocked.hip   G = U^T U and the two triangular solves on the rows of Y (dl_factor and dl_solve_rows of
+//                 chol_blocked.h: the one compiled copy that delay.hip and dpss.hip call too);
 //   k_mf_eye      the masked identity as right-hand sides, and the (mask x mask) zeroing of the solution.
 // A non-positive pivot sets the matrix's status word; every later kernel leaves that matrix alone.
 //
 // Index ranges at n = 4096: i * n + j < 2^24 inside a matrix; every offset that carries a batch, frequency or entry
 // index is formed in size_t; grid dimensions are checked against 65535 (y, z) and 2^31 - 1 (x) on the host.
 #include "chol_blocked.h"
+
+#include <algorithm>
 
 namespace {
 

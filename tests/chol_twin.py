@@ -1,4 +1,4 @@
-"""Long-double truth for the blocked Cholesky solver of ``csrc/chol_blocked.h`` (``dl_factor`` + ``dl_solve_rows``,
+"""Long-double truth for the blocked Cholesky solver of ``csrc/chol_blocked.hip`` (``dl_factor`` + ``dl_solve_rows``,
 reached through ``dmm_mfilter_solve``), and the inputs and measures its tests share.  NumPy only.
 
 * ``chol_upper_ld``   unblocked ``G = U^T U`` in long double, reading the upper triangle only;

@@ -1,4 +1,4 @@
-"""The blocked float64 Cholesky solver of ``csrc/chol_blocked.h`` (``dl_factor``, ``dl_solve_rows``), addressed directly
+"""The blocked float64 Cholesky solver of ``csrc/chol_blocked.hip`` (``dl_factor``, ``dl_solve_rows``), addressed directly
 through ``dmm_mfilter_solve``, against the long-double truth of ``tests/chol_twin.py``; and ``k_mf_cov`` and the three
 filter builders at the orders the task-level tests leave out.
 

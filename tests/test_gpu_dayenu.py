@@ -137,6 +137,39 @@ def test_functions(gold, name):
     assert np.array_equal(low, g[f"fn_{name}/low"])
 
 
+def test_build_block_edges():
+    """`dmm_dayenu_build` at the orders around the 32-row panels of `k_dy_chol` (a last panel of 1, 2, 31, 32 and 33
+    rows, behind zero to four full ones), one matrix per order, against the long-double Cholesky inverse.  Required:
+    `e_gpu <= max(2 e_ref, n cond(C) 2**-52)`, `e_ref` the same measure of `numpy.linalg.pinv` of the float64
+    covariance; the floor is the conditioning bound, for the two tiny orders where `pinv` is nearly exact.
+
+    Measured (MI355X), `e_gpu` / `e_ref`: order 1 4.8e-17 / 4.8e-17, 2 3.1e-15 / 2.0e-15 (floor 2.2e-14), 31 2.2e-4 / 6.3e-4,
+    32 2.5e-4 / 7.1e-4, 33 2.5e-4 / 1.5e-3, 63 5.9e-4 / 9.1e-4, 64 6.0e-4 / 2.4e-3, 65 6.1e-4 / 1.3e-3, 97 7.5e-4 / 1.9e-3,
+    129 1.2e-3 / 1.7e-3: below `2 e_ref` at every order from 31 up, without the floor."""
+    from draco_amd.analysis.dayenu import build_filters
+    from draco_amd.device import Context
+
+    ctx = Context.get()
+    tw, eps = 0.2, 1e-12
+    for n in (1, 2, 31, 32, 33, 63, 64, 65, 97, 129):
+        freq = np.linspace(400.0, 800.0, 1024)[:n].copy()
+        flag = np.ones(n, dtype=bool)
+        if n > 3:
+            flag[[j for j in (0, 5, 32, n - 1) if j < n]] = False
+        nf, status = build_filters(ctx, ctx.to_device(freq), np.array([[[tw, eps]]]), flag[np.newaxis, :])
+        x = nf.cpu().numpy()[0]
+        truth = twin.filter_truth(freq, flag, tw, eps)
+        ref = twin.delay_filter_f64(freq, flag[:, np.newaxis], tw, eps)[0][0]
+        sel = np.flatnonzero(flag)
+        cond = float(np.linalg.cond(twin.covariance(freq, tw, eps)[np.ix_(sel, sel)]))
+        e_gpu, e_ref = twin.rel_err(x, truth), twin.rel_err(ref, truth)
+        print(f"dayenu build n {n}: e_gpu {e_gpu:.3e} e_ref {e_ref:.3e} floor {n * cond * 2.0**-52:.3e}")
+        assert not status.any(), (n, status)
+        assert np.isfinite(x).all(), n
+        assert not x[~flag, :].any() and not x[:, ~flag].any(), n
+        assert e_gpu <= max(2 * e_ref, n * cond * 2.0**-52), (n, e_gpu, e_ref)
+
+
 def test_failure_path(gold, caplog):
     """An indefinite covariance (negative epsilon): no exception, every weight zero, data untouched, nothing NaN."""
     task, vis, weight = _run_stream(gold, "C", epsilon=-1e-12)
