@@ -352,7 +352,9 @@ int dmm_allgather_map(dmm_ctx* ctx, void* comm, const double* shard /*[dev]*/, i
  *   float64 arithmetic (the reference's `precision = 64`), float32 stores like the reference's containers.
  * dmm_beamform_ew: BeamformEW.process (:455-495): pol_rotation [dev] complex128 [npol_out, npol_in], weight_ew [dev] double
  *   [nx] (normalised; single_beam: the central beam only); map [dev] double [nbeam, npol_out, nfreq, nra, nel],
- *   weight [npol_out, nfreq, nra, nel], rms [npol_out, nfreq, nra]; dirty beam in (float, real) / out (like map) or both NULL. */
+ *   weight [npol_out, nfreq, nra, nel], rms [npol_out, nfreq, nra]; dirty beam in (float, real) / out (like map) or both NULL.
+ *   Limits: nx <= 8 and npol_in <= 4 (DMM_E_ARG beyond).  A row of pol_rotation may have at most two non-zero entries: the
+ *   kernel keeps the first two it finds and silently drops the rest (BeamformEW._get_pol never makes more). */
 int dmm_calc_redundancy(dmm_ctx* ctx, const float* input_flags, int ninput, int nra, const int32_t* prod_a, const int32_t* prod_b,
                         const int32_t* stack_index, int64_t nprod, int nstack, int all_good, float* redundancy);
 int dmm_vis_grid(dmm_ctx* ctx, const void* vis, const float* weight, const float* redundancy, int nfreq, int nstack, int nra, int npol,
