@@ -28,6 +28,7 @@ DMM_B_FULL, DMM_B_PACKED = 0, 1
 DMM_E_ARG, DMM_E_UNSUPPORTED, DMM_E_NOMEM, DMM_E_STATE, DMM_E_COMM = -1, -2, -3, -4, -5
 DMM_MAX_NRA = 8192
 DMM_STACK_UNIFORM, DMM_STACK_INVERSE_VARIANCE = 0, 1
+DMM_REBIN_UNIFORM, DMM_REBIN_INVERSE_VARIANCE = 0, 1
 DMM_DAYENU_F32, DMM_DAYENU_F64 = 0, 1
 DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
 DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
@@ -131,7 +132,10 @@ _SIGS = {
     "dmm_regrid_band_wiener": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmm_sidereal_stack_add": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
     "dmm_sidereal_stack_finish": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i64]),
-    "dmm_dayenu_build": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_rebin": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_rebin_gradient": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i]),
+    "dmm_regrid_interp": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_dayenu_build": (_i,[_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_dayenu_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
     "dmm_dayenu_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, C.POINTER(dmm_dayenu_side), C.POINTER(dmm_dayenu_side)]),
     "dmm_delay_fourier": (_i, [_vp, _i, _i, _i, _vp, _vp]),

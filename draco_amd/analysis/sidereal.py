@@ -5,6 +5,11 @@ Drop-in for the two tasks of ``draco/analysis/sidereal.py`` that stand between t
 * :class:`SiderealRegridder`  ``sidereal.py:160-278``
 * :class:`SiderealStacker`    ``sidereal.py:834-1080``
 
+and the second family of ways onto the RA grid (``csrc/rebin.hip``):
+
+* :class:`SiderealRegridderNearest`, :class:`SiderealRegridderLinear`, :class:`SiderealRegridderCubic`  ``sidereal.py:349-547``
+* :class:`SiderealRebinner`, :class:`RebinGradientCorrection`  ``sidereal.py:550-831``
+
 Same class names, config attributes, ``setup`` / ``process`` / ``process_finish`` signatures and exceptions.  The
 arithmetic runs in ``libdraco_amd.so`` (``csrc/regrid.hip``); outputs and the stacker's running state stay on the
 device, so ``SiderealRegridder -> SiderealStacker -> MModeTransform -> DirtyMapMaker`` never crosses PCIe.
@@ -96,6 +101,221 @@ class SiderealRegridder(LanczosRegridder):
         omega, mask = self._get_fringe_rate(freq, prod)
         dphi = self._dphi(np.asarray(lsd, dtype=np.float64))
         return mask[np.newaxis, :, np.newaxis] * np.exp(-1.0j * omega[:, :, np.newaxis] * dphi[np.newaxis, np.newaxis, :])
+
+
+def _inz(x):
+    """``invert_no_zero``: 1 / x, 0 where x is 0."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x == 0, 0.0, 1.0 / np.where(x == 0, 1.0, x))
+
+
+def _search_nearest(x, xeval):
+    """Index into the sorted ``x`` of the point nearest each ``xeval``; of two equally near, the later one
+    (``sidereal.py:349-359``)."""
+    nxt = np.searchsorted(x, xeval, side="left")
+    prev = np.maximum(0, nxt - 1)
+    nxt = np.minimum(x.size - 1, nxt)
+    return np.where(np.abs(xeval - x[prev]) < np.abs(xeval - x[nxt]), prev, nxt)
+
+
+class _DirectRegridder(SiderealRegridder):
+    """Interpolators that read a few input samples per grid point: the host finds the taps, their coefficients and the
+    grid points to flag, in float64 with the reference's expressions; ``dmm_regrid_interp`` gathers."""
+
+    def _taps(self, lsd, grid):
+        """``(tap [ntap, samples] int, coeff [ntap, samples] float64, bad [samples] bool)``."""
+        raise NotImplementedError
+
+    def _regrid(self, vis, weight, lsd, mix=None):
+        from ..util import regrid
+
+        ctx = Context.get()
+        vis_d = _dev_dataset(vis, ctx, np.complex64)
+        w_d = _dev_dataset(weight, ctx, np.float32)
+        lsd = np.asarray(lsd, dtype=np.float64)
+        # a regular grid
+        interp_grid = np.arange(0, self.samples, dtype=np.float64) / self.samples
+        interp_grid = interp_grid * (self.end - self.start) + self.start
+        tap, coeff, bad = self._taps(lsd, interp_grid)
+        lead, nt = tuple(vis_d.shape[:-1]), int(vis_d.shape[-1])
+        sts, ni = regrid.regrid_interp(ctx, vis_d.reshape(-1, nt), w_d.reshape(-1, nt), tap.astype(np.int32), coeff, bad.astype(np.uint8), mix)
+        return interp_grid, sts.reshape(*lead, self.samples), ni.reshape(*lead, self.samples)
+
+
+class SiderealRegridderNearest(_DirectRegridder):
+    """Regrid onto the sidereal day using nearest neighbour interpolation (``sidereal.py:362-383``)."""
+
+    def _taps(self, lsd, grid):
+        index = _search_nearest(lsd, grid)
+        # flagged if the nearest sample is more than one sample spacing away: incomplete sidereal coverage
+        delta = np.median(np.abs(np.diff(lsd)))
+        bad = np.abs(lsd[index] - grid) > delta
+        return index[np.newaxis, :], np.ones((1, grid.size)), bad
+
+
+class SiderealRegridderLinear(_DirectRegridder):
+    """Regrid onto the sidereal day using linear interpolation (``sidereal.py:386-461``)."""
+
+    def _taps(self, lsd, grid):
+        ind2 = np.searchsorted(lsd, grid, side="left")
+        ind1 = ind2 - 1
+        # outside the range the data cover: extrapolated from the two end samples, and flagged
+        below = ind1 == -1
+        above = ind2 == lsd.size
+        ind1 = np.where(below, 0, np.where(above, lsd.size - 2, ind1))
+        ind2 = np.where(below, 1, np.where(above, lsd.size - 1, ind2))
+        delta = np.median(np.abs(np.diff(lsd)))
+        distant = (np.abs(lsd[ind1] - grid) > delta) | (np.abs(lsd[ind2] - grid) > delta)
+        dx1 = grid - lsd[ind1]
+        dx2 = lsd[ind2] - grid
+        norm = _inz(dx1 + dx2)
+        return np.stack([ind1, ind2]), np.stack([dx2 * norm, dx1 * norm]), below | above | distant
+
+
+class SiderealRegridderCubic(_DirectRegridder):
+    """Regrid onto the sidereal day using cubic Hermite spline interpolation (``sidereal.py:464-547``)."""
+
+    def _taps(self, lsd, grid):
+        index = np.searchsorted(lsd, grid, side="left")
+        index = np.stack([index + i for i in range(-2, 2)])  # the four samples around each grid point
+        below = np.any(index < 0, axis=0)
+        above = np.any(index >= lsd.size, axis=0)
+        index = np.clip(index, 0, lsd.size - 1)
+        delta = np.median(np.abs(np.diff(lsd)))
+        distant = np.any(np.abs(grid - lsd[index]) > (2.0 * delta), axis=0)
+        u = (grid - lsd[index[1]]) * _inz(lsd[index[2]] - lsd[index[1]])
+        coeff = np.zeros((4, u.size), dtype=np.float64)
+        coeff[0] = u * ((2 - u) * u - 1)
+        coeff[1] = u**2 * (3 * u - 5) + 2
+        coeff[2] = u * ((4 - 3 * u) * u + 1)
+        coeff[3] = u**2 * (u - 1)
+        coeff *= 0.5
+        return index, coeff, below | above | distant
+
+
+class SiderealRebinner(SiderealRegridder):
+    """Regrid a sidereal day of data by binning (``sidereal.py:550-731``): every time sample gives each RA bin the
+    fraction of its width that overlaps the bin.
+
+    The output carries ``nsample`` and ``effective_ra``, the weighted centre of the samples of each bin, which
+    :class:`RebinGradientCorrection` removes afterwards.  One pass of ``dmm_rebin`` over the input; all four output
+    datasets stay on the device.  Input datasets beyond ``vis`` / ``vis_weight`` are refused, and the time stamps must
+    not decrease (``NotImplementedError``).
+
+    ``weight``: ``"uniform"`` or ``"inverse_variance"``.
+    """
+
+    _config_names = ("weight",)
+    weight = "inverse_variance"
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.weight not in ("uniform", "inverse_variance"):
+            raise ValueError(f"weight must be 'uniform' or 'inverse_variance', not {self.weight!r}")
+
+    def process(self, data):
+        import inspect
+
+        from ..util import regrid
+
+        self.log.info(f"Rebinning LSD {data.attrs['lsd']:.0f} with {self.weight} weighting.")
+        container_map = {
+            containers.TimeStream: containers.SiderealStream,
+            containers.SiderealStream: containers.SiderealStream,
+            containers.HybridVisStream: containers.HybridVisStream,
+        }
+        OutputContainer = None
+        for cls in inspect.getmro(data.__class__):  # subclasses of the mapped containers count
+            OutputContainer = container_map.get(cls)
+            if OutputContainer is not None:
+                break
+        if OutputContainer is None:
+            raise TypeError(f"No valid container mapping.\nGot {data.__class__}.\nMappings exist for {list(container_map.keys())}.")
+        extra = [name for name in data.datasets if name not in ("vis", "vis_weight")]
+        if extra:
+            raise NotImplementedError(f"SiderealRebinner rebins vis and vis_weight only; the input also holds {extra}.")
+        data.redistribute("freq")
+
+        self.start = data.attrs["lsd"]
+        self.end = self.start + 1
+        if "ra" in data.index_map:
+            timestamp_lsd = self.start + data.ra / 360.0
+        else:
+            timestamp_lsd = self.observer.unix_to_lsd(data.time)
+        timestamp_lsd = np.asarray(timestamp_lsd, dtype=np.float64)
+
+        sdata = OutputContainer(ra=self.samples, axes_from=data, attrs_from=data, allocate=False)
+        sdata.add_dataset("effective_ra", allocate=False)
+        sdata.add_dataset("nsample", allocate=False)
+        sdata.redistribute("freq")
+
+        # the median width of a time sample, the regular grid of RA bins, the rebinning matrix
+        width_t = np.median(np.abs(np.diff(timestamp_lsd)))
+        target_lsd = np.linspace(self.start, self.end, self.samples, endpoint=False)
+        ctx = Context.get()
+        plan = regrid.RebinPlan(ctx, timestamp_lsd, target_lsd, width_t, self.start, sdata.index_map["ra"])
+        vis_d = _dev_dataset(data.vis, ctx, np.complex64)
+        w_d = _dev_dataset(data.weight, ctx, np.float32)
+        nt = int(vis_d.shape[-1])
+        mode = _lib.DMM_REBIN_UNIFORM if self.weight == "uniform" else _lib.DMM_REBIN_INVERSE_VARIANCE
+        hybrid = OutputContainer is containers.HybridVisStream
+        ssv, ssw, ssn, sera = regrid.rebin(ctx, plan, vis_d.reshape(-1, nt), w_d.reshape(-1, nt), mode, nsample_f32=hybrid)
+        ctx.uses(plan.row_ptr_d, plan.sample_index_d, plan.value_d, plan.tile_span_d, plan.lsd_d, plan.ra_d)
+        sdata.attach("vis", ssv.reshape(*vis_d.shape[:-1], self.samples))
+        sdata.attach("vis_weight", ssw.reshape(*w_d.shape[:-1], self.samples))
+        sdata.attach("nsample", ssn.reshape(*w_d.shape[:-1], self.samples))
+        sdata.attach("effective_ra", sera.reshape(*w_d.shape[:-1], self.samples))
+        return sdata
+
+
+class RebinGradientCorrection(ContainerTask):
+    """Apply a linear gradient correction to shift RA samples to bin centres (``sidereal.py:734-831``).
+
+    ``setup`` takes the stream the local gradient is formed from -- it needs full sidereal coverage, and may be the
+    rebinned stream itself; ``process`` corrects a stream in place on the device (``dmm_rebin_gradient``) and drops its
+    ``effective_ra``.  A stream without ``effective_ra`` passes through untouched.
+    """
+
+    def setup(self, sstream_ref):
+        self.sstream_ref = sstream_ref
+
+    def process(self, sstream):
+        from ..util import regrid
+
+        self.sstream_ref.redistribute("freq")
+        sstream.redistribute("freq")
+        try:
+            era = sstream.effective_ra
+        except KeyError:
+            self.log.info(f"Dataset of type ({type(sstream)}) does not have an effective ra dataset. No correction will be applied.")
+            return sstream
+        if len(sstream.vis.shape) != 3:
+            raise NotImplementedError(f"RebinGradientCorrection corrects [freq, stack, ra] streams; vis has shape {sstream.vis.shape}.")
+        ctx = Context.get()
+        ref_era_d = ref_ra_d = None
+        try:  # the reference's own effective RA if it has one (it may be the stream itself), else its regular RA axis
+            ref_era_d = _dev_dataset(self.sstream_ref.effective_ra, ctx, np.float32)
+        except KeyError:
+            ref_ra_d = ctx.to_device(self.sstream_ref.ra, np.float64)
+        nra = int(sstream.vis.shape[-1])
+        vis_d = _dev_dataset(sstream.vis, ctx, np.complex64)
+        w_d = _dev_dataset(sstream.weight, ctx, np.float32)
+        era_d = _dev_dataset(era, ctx, np.float32)
+        ra_d = ctx.to_device(sstream.ra, np.float64)
+        ref_vis_d = _dev_dataset(self.sstream_ref.vis, ctx, np.complex64)
+        ref_w_d = _dev_dataset(self.sstream_ref.weight, ctx, np.float32)
+        if tuple(ref_vis_d.shape) != tuple(vis_d.shape):
+            raise ValueError(f"reference stream of shape {tuple(ref_vis_d.shape)} does not match the stream's {tuple(vis_d.shape)}")
+        regrid.rebin_gradient(
+            ctx, vis_d.reshape(-1, nra), w_d.reshape(-1, nra), era_d.reshape(-1, nra), ra_d, ref_vis_d.reshape(-1, nra), ref_w_d.reshape(-1, nra),
+            None if ref_era_d is None else ref_era_d.reshape(-1, nra), ref_ra_d
+        )
+        ctx.uses(ra_d, ref_ra_d)
+        sstream.vis.set_device(vis_d)  # corrected in place: the device copy is the valid one
+        sstream.weight.set_device(w_d)
+        # the effective ra dataset is not needed anymore
+        del sstream["effective_ra"]
+        return sstream
 
 
 def _ensure_list(x):

@@ -278,6 +278,15 @@ class ContainerBase:
     def __contains__(self, name):
         return name in self.datasets
 
+    def __delitem__(self, name):
+        """Drop dataset ``name`` (``del container["effective_ra"]``)."""
+        del self.datasets[name]
+
+    def _optional(self, name):
+        if name in self.datasets:
+            return self.datasets[name]
+        raise KeyError(f"Dataset '{name}' not initialised.")
+
 
 class _FreqMixin:
     @property
@@ -308,7 +317,13 @@ class SiderealStream(ContainerBase, _FreqMixin, _VisMixin):
         # what SiderealStacker adds to its stack (containers.py:536-552): days per sample, variance over days (rr, ri, ii)
         "sample_variance": {"axes": ["component", "freq", "stack", "ra"], "dtype": np.float32},
         "nsample": {"axes": ["freq", "stack", "ra"], "dtype": np.uint16},
+        # what SiderealRebinner adds (containers.py:517-523): the weighted centre of the samples of every bin, degrees
+        "effective_ra": {"axes": ["freq", "stack", "ra"], "dtype": np.float32},
     }
+
+    @property
+    def effective_ra(self):
+        return self._optional("effective_ra")
 
     def add_dataset(self, name, allocate=True):
         self._dataset_spec = dict(self._dataset_spec)
@@ -325,7 +340,7 @@ class SiderealStream(ContainerBase, _FreqMixin, _VisMixin):
 
     @property
     def nsample(self):
-        return self.datasets["nsample"]
+        return self._optional("nsample")
 
     @property
     def sample_variance(self):
@@ -431,7 +446,24 @@ class HybridVisStream(ContainerBase, _FreqMixin, _VisMixin):
         "vis_weight": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
     }
 
-    _optional_spec = {"dirty_beam": {"axes": ["pol", "freq", "ew", "el", "ra"], "dtype": np.float32}}  # containers.py:1409-1417
+    _optional_spec = {
+        "dirty_beam": {"axes": ["pol", "freq", "ew", "el", "ra"], "dtype": np.float32},  # containers.py:1409-1417
+        # what SiderealRebinner adds (containers.py:1439-1458)
+        "effective_ra": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
+        "nsample": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
+    }
+
+    @property
+    def ra(self):
+        return self.index_map["ra"]
+
+    @property
+    def effective_ra(self):
+        return self._optional("effective_ra")
+
+    @property
+    def nsample(self):
+        return self._optional("nsample")
 
     def __init__(self, ra=None, **kwargs):
         if isinstance(ra, (int, np.integer)):

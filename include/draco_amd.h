@@ -481,6 +481,48 @@ int dmm_sidereal_stack_add(dmm_ctx* ctx, int mode, int with_variance, const void
 int dmm_sidereal_stack_finish(dmm_ctx* ctx, int mode, int with_variance, float* stack_weight, const uint16_t* stack_nsample,
                               const float* sum_coeff_sq, float* sample_variance, int64_t n);
 
+/* Sidereal rebinning, its gradient correction and the direct interpolators, csrc/rebin.hip (draco/analysis/sidereal.py:
+ * 550-731 SiderealRebinner, :734-831 RebinGradientCorrection, :349-547 SiderealRegridderNearest / Linear / Cubic).
+ * Float64 arithmetic from the float32 / complex64 inputs, every output rounded once; no atomics: two runs agree bit
+ * for bit.
+ *
+ * dmm_rebin: one pass over vis [nrow, nt] complex64 and weight [nrow / fold, nt] float32 (row k reads weight row
+ * k / fold: fold = 1 for a stream, the length of the `el` axis for a HybridVisStream).  The rebinning matrix
+ * R [nra, nt] (regrid.py:161-211) comes in CSR form by output bin: row_ptr [nra + 1], sample_index [nnz] ascending
+ * within a bin, value [nnz] float64; tile_span [ceil(nra / 64), 2] holds, per tile of 64 bins, the first and one past
+ * the last sample its bins read (0, 0 for a tile without samples).  lsd [nt] float64 are the samples' sidereal days,
+ * ra [nra] float64 the bin centres in degrees, start the day's LSD.  Per row and bin g, with (w, v) = (weight, weight)
+ * for DMM_REBIN_INVERSE_VARIANCE and (weight > 0, float32(invert_no_zero(weight))) for DMM_REBIN_UNIFORM, summed in
+ * ascending sample order:
+ *   norm = inz(sum R w),  out_vis = norm sum R w vis,  out_nsample = sum R (weight > 0),
+ *   out_weight = inz(norm^2 sum R^2 v),  out_effective_ra = 360 (norm sum R w lsd - start), ra[g] where out_weight = 0
+ * out_vis [nrow, nra] complex64; out_weight, out_effective_ra [nrow / fold, nra] float32; out_nsample [nrow / fold,
+ * nra] uint16 (truncated toward zero) or, with nsample_f32, float32.  All arrays [dev]; vis and weight 16-byte aligned
+ * (DMM_E_ARG otherwise).  Limits: nra <= 64 * 65535 (DMM_E_UNSUPPORTED beyond); a bin may hold any number of samples.
+ *
+ * dmm_rebin_gradient, in place on vis / weight [nrow, nra]: per row that has a non-zero weight, the gradient of the
+ * reference row ref_vis (flagged where ref_weight = 0) over its positions -- ref_effective_ra [nrow, nra] float32 or
+ * ref_ra [nra] float64, exactly one of the two non-NULL -- wrapped with period 360 (regrid.py:214-270, np.gradient's
+ * second-order formula for uneven spacing); a gradient that touches a flagged sample, an interval of zero length or is
+ * not finite is flagged and zero.  Then vis -= gradient (weight > 0) (effective_ra - ra), weight *= !flagged.  The
+ * reference arrays may be the arrays being corrected.  All [dev].  nra <= DMM_MAX_NRA (DMM_E_UNSUPPORTED beyond).
+ *
+ * dmm_regrid_interp: out_vis[k, o] = sum_t coeff[t, o] vis[k, tap[t, o]] for ntap = 1 (nearest), 2 (linear) or 4
+ * (cubic) taps; tap [ntap, nout] int32, coeff [ntap, nout] float64, bad [nout] uint8 as the host evaluates them
+ * (sidereal.py:365-547).  ntap = 1 copies the weight; otherwise out_weight = inz(sum coeff^2 float32(inz(weight)))
+ * where every tap has weight > 0, else 0.  out_weight = 0 where bad.  Mixing arrays as for dmm_regrid_band_wiener,
+ * dphi_out [nout].  vis, weight [nrow, nt]; out_vis, out_weight [nrow, nout]; all [dev]. */
+enum { DMM_REBIN_UNIFORM = 0, DMM_REBIN_INVERSE_VARIANCE = 1 };
+int dmm_rebin(dmm_ctx* ctx, int mode, int nsample_f32, const void* vis, const float* weight, int64_t nrow, int fold, int nt, int nra,
+              const int32_t* row_ptr, const int32_t* sample_index, const double* value, int nnz, const int32_t* tile_span,
+              const double* lsd, double start, const double* ra, void* out_vis, float* out_weight, void* out_nsample,
+              float* out_effective_ra);
+int dmm_rebin_gradient(dmm_ctx* ctx, void* vis, float* weight, const float* effective_ra, const double* ra, const void* ref_vis,
+                       const float* ref_weight, const float* ref_effective_ra, const double* ref_ra, int64_t nrow, int nra);
+int dmm_regrid_interp(dmm_ctx* ctx, int ntap, const void* vis, const float* weight, int64_t nrow, int nt, int nout,
+                      const int32_t* tap, const double* coeff, const uint8_t* bad, const double* omega, const float* feed_mask,
+                      const double* dphi_in, const double* dphi_out, void* out_vis, float* out_weight);
+
 /* DAYENU delay filter (draco/analysis/dayenu.py:20-193, 776-975, 1125-1232), csrc/dayenu.hip.
  *
  * dmm_dayenu_build: nmat filters of order nfreq (1 ... 1024) at once.  freq [nfreq] float64 (MHz), bands

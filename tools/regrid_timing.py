@@ -6,6 +6,9 @@ the spread over windows, GB/s on the algorithmic bytes (input 12 B per sample + 
 read day + state, write state) and the fraction of the 8 TB/s peak.  One JSON line per case.
 
     python tools/regrid_timing.py [--rows 97024] [--nt 1536 2048 4096 8640] [--workspace-mib 0]
+
+`--method rebin | nearest | linear | cubic` times the rebinner or one of the direct interpolators on the same data
+instead (default `band_wiener`: the above).
 """
 import argparse
 import json
@@ -31,6 +34,47 @@ def windows(ctx, fn, nwin, reps):
     return out
 
 
+def other_method(args):
+    """`--method rebin | nearest | linear | cubic`: the same rows, time stamps, flags and windows through `dmm_rebin`
+    (inverse-variance weights; bytes: 12 B per sample in, 18 B per bin out -- vis, weight, nsample, effective_ra) or
+    `dmm_regrid_interp` (12 B per sample in, 12 B per grid point out; the tap tables are uploaded once, outside the windows)."""
+    import torch
+
+    from draco_amd import _lib
+    from draco_amd.analysis import sidereal
+    from draco_amd.device import Context, ptr
+    from draco_amd.util import regrid
+
+    ctx = Context.get()
+    rng = np.random.default_rng(1)
+    gen = torch.Generator(device=ctx.device).manual_seed(1)
+    for nt in args.nt:
+        t = np.sort(np.linspace(-0.005, 1.005, nt) + rng.uniform(-0.4, 0.4, nt) * 1.01 / nt)
+        t = t[((t < 0.31) | (t > 0.33)) & ((t < 0.70) | (t > 0.705))]
+        n = len(t)
+        vis = torch.view_as_complex(torch.randn((args.rows, n, 2), dtype=torch.float32, device=ctx.device, generator=gen))
+        w = torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
+        w *= torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) > 0.2
+        if args.method == "rebin":
+            target = np.linspace(0.0, 1.0, args.samples, endpoint=False)
+            plan = regrid.RebinPlan(ctx, t, target, np.median(np.abs(np.diff(t))), 0.0, target * 360.0)
+            fn = lambda: regrid.rebin(ctx, plan, vis, w, _lib.DMM_REBIN_INVERSE_VARIANCE)  # noqa: E731
+            nbytes = args.rows * (12 * n + 18 * args.samples)
+        else:
+            task = {"nearest": sidereal.SiderealRegridderNearest, "linear": sidereal.SiderealRegridderLinear, "cubic": sidereal.SiderealRegridderCubic}[args.method](samples=args.samples)
+            tap, coeff, bad = task._taps(t, np.arange(args.samples, dtype=np.float64) / args.samples)
+            tap_d, coeff_d, bad_d = ctx.to_device(tap, np.int32), ctx.to_device(coeff, np.float64), ctx.to_device(bad, np.uint8)
+            ov, ow = ctx.empty((args.rows, args.samples), np.complex64), ctx.empty((args.rows, args.samples), np.float32)
+            fn = lambda: _lib.check(_lib.lib.dmm_regrid_interp(ctx.handle, len(tap), ptr(vis), ptr(w), args.rows, n, args.samples, ptr(tap_d), ptr(coeff_d), ptr(bad_d), None, None, None, None, ptr(ov), ptr(ow)))  # noqa: E731
+            nbytes = args.rows * 12 * (n + args.samples)
+        ms = windows(ctx, fn, args.windows, args.reps)
+        med = float(np.median(ms))
+        print(json.dumps({"case": args.method, "rows": args.rows, "nt": n, "samples": args.samples, "ms": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                          "GBps": round(nbytes / med / 1e6, 1), "frac_peak": round(nbytes / med * 1e3 / PEAK, 4), "hbm_floor_ms": round(nbytes / PEAK * 1e3, 3)}), flush=True)
+        ctx.sync()
+        del vis, w
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=256 * 379)
@@ -39,7 +83,10 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--workspace-mib", type=int, default=0)
+    ap.add_argument("--method", choices=["band_wiener", "rebin", "nearest", "linear", "cubic"], default="band_wiener")
     args = ap.parse_args()
+    if args.method != "band_wiener":
+        return other_method(args)
 
     import torch
 

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """End-to-end example: sky -> SimulateSidereal -> (noise) -> MModeTransform -> {Dirty, Wiener, ML}MapMaker.
 
-    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise] [--regrid]
+    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise] [--regrid | --rebin]
 
 --regrid: the simulated day is first sampled onto irregular time stamps (jitter, a gap, flagged samples) as a TimeStream
 and brought back to the RA grid by SiderealRegridder before the m-mode transform.
+--rebin: the same TimeStream goes through SiderealRebinner and RebinGradientCorrection instead.
 
 Mirrors the reference's tutorial pipeline (doc/pipeline_params.yaml:1-35) with this repo's
 task classes.  Prints per-task wall time (device synchronised) and a few sanity numbers.
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--makers", nargs="*", default=["dirty", "wiener"])
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--regrid", action="store_true", help="go through an irregular TimeStream and SiderealRegridder")
+    ap.add_argument("--rebin", action="store_true", help="go through an irregular TimeStream, SiderealRebinner and RebinGradientCorrection")
     ap.add_argument("--nfreq", type=int, default=0, help="override the number of frequencies")
     ap.add_argument("--pool-gb", type=float, default=0.0, help="B pool budget in GB (default: 0.6 of the free HBM)")
     args = ap.parse_args()
@@ -87,8 +89,8 @@ def main():
         gn = GaussianNoise(seed=1, ndays=733.0, recv_temp=50.0)
         gn.setup(tel)
         ss = timed("GaussianNoise_host", lambda: gn.process(ss))
-    if args.regrid:
-        from draco_amd.analysis.sidereal import SiderealRegridder
+    if args.regrid or args.rebin:
+        from draco_amd.analysis.sidereal import RebinGradientCorrection, SiderealRebinner, SiderealRegridder
         from draco_amd.util import regrid
 
         nra, lsd, a = ss.vis.shape[-1], 100, 5
@@ -107,10 +109,19 @@ def main():
         tw[..., :: 7] = 0.0
         ts.attach("vis_weight", tw)
         ts.attrs["lsd"] = lsd
-        rg = SiderealRegridder(samples=nra, kernel_width=a)
-        rg.setup(tel)
-        timed("SiderealRegridder_first_call", lambda: rg.process(ts))
-        sr = timed("SiderealRegridder", lambda: rg.process(ts))
+        if args.rebin:
+            rb = SiderealRebinner(samples=nra)
+            rb.setup(tel)
+            timed("SiderealRebinner_first_call", lambda: rb.process(ts))
+            sr = timed("SiderealRebinner", lambda: rb.process(ts))
+            gc = RebinGradientCorrection()
+            gc.setup(sr)  # the day has full coverage: it is its own reference
+            sr = timed("RebinGradientCorrection", lambda: gc.process(sr))
+        else:
+            rg = SiderealRegridder(samples=nra, kernel_width=a)
+            rg.setup(tel)
+            timed("SiderealRegridder_first_call", lambda: rg.process(ts))
+            sr = timed("SiderealRegridder", lambda: rg.process(ts))
         ss = sr
     tr = MModeTransform()
     tr.setup(bt)
