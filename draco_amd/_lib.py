@@ -38,6 +38,8 @@ DMM_MFILTER_OK, DMM_MFILTER_NOT_POSDEF = 0, 1
 DMM_DPSS_OK, DMM_DPSS_SKIPPED, DMM_DPSS_NOT_POSDEF = 0, 1, 2
 DMM_SRCBEAM_INVERSE_VARIANCE, DMM_SRCBEAM_NATURAL, DMM_SRCBEAM_UNIFORM = 0, 1, 2
 DMM_SRCBEAM_W_F32, DMM_SRCBEAM_W_F64 = 0, 1
+DMM_GP_GAUSSIAN, DMM_GP_RATIONAL, DMM_GP_MATERN15, DMM_GP_MATERN25 = 0, 1, 2, 3
+DMM_GP_OK, DMM_GP_NOT_POSDEF = 0, 1
 
 
 class DmmError(RuntimeError):
@@ -161,6 +163,11 @@ _SIGS = {
     "dmm_srcbeam_prepare": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmm_srcbeam_form": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "dmm_srcbeam_collapse": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dmm_gp_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_gp_fill": (_i, [_vp, _i, _vp, _vp, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmm_gp_project": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp, _vp]),
+    "dmm_gp_compact": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmm_gp_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i] + [_vp] * 15),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

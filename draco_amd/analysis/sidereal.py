@@ -4,6 +4,7 @@ Drop-in for the two tasks of ``draco/analysis/sidereal.py`` that stand between t
 
 * :class:`SiderealRegridder`  ``sidereal.py:160-278``
 * :class:`SiderealStacker`    ``sidereal.py:834-1080``
+* :class:`SiderealRegridderGP`  ``sidereal.py:281-346`` (``csrc/gp.hip``)
 
 and the second family of ways onto the RA grid (``csrc/rebin.hip``):
 
@@ -61,7 +62,7 @@ class SiderealRegridder(LanczosRegridder):
         if self.down_mix:
             self.log.info("Downmixing before regridding.")
             ctx = Context.get()
-            out_grid = self.start + np.arange(self.samples, dtype=np.float64) / self.samples * (self.end - self.start)
+            out_grid = self._mix_up_grid()
             omega, mask = self._get_fringe_rate(data.freq, data.prodstack)
             mix = (
                 ctx.to_device(omega.reshape(-1), np.float64),
@@ -79,6 +80,10 @@ class SiderealRegridder(LanczosRegridder):
         sdata.attrs["lsd"] = self.start
         sdata.attrs["tag"] = f"lsd_{self.start:.0f}"
         return sdata
+
+    def _mix_up_grid(self):
+        """The output samples' LSDs as the mix-up sees them."""
+        return self.start + np.arange(self.samples, dtype=np.float64) / self.samples * (self.end - self.start)
 
     @staticmethod
     def _dphi(lsd):
@@ -101,6 +106,47 @@ class SiderealRegridder(LanczosRegridder):
         omega, mask = self._get_fringe_rate(freq, prod)
         dphi = self._dphi(np.asarray(lsd, dtype=np.float64))
         return mask[np.newaxis, :, np.newaxis] * np.exp(-1.0j * omega[:, :, np.newaxis] * dphi[np.newaxis, np.newaxis, :])
+
+
+class SiderealRegridderGP(SiderealRegridder):
+    r"""Regrid onto the sidereal day using Gaussian Process Regression (``sidereal.py:281-346``).
+
+    A Matern-5/2 kernel of ``kernel_width`` grid cells with ``epsilon`` on the diagonal; per frequency the kernel matrix
+    of the unflagged samples is truncated to a band, factored, and the projection applied to every stack
+    (:mod:`draco_amd.util.gaussian_process`, ``csrc/gp.hip``).  Frequencies with the same flags share a factorisation.
+    Raises ``scipy.linalg.LinAlgError`` if a truncated matrix is not positive definite.
+
+    ``mask_cutoff``: distance (in input samples) from the `n`\th nearest unflagged input sample within which an output
+    sample is kept.  ``mask_cutoff_partition``: that `n`, counted from zero.
+    """
+
+    _config_names = ("mask_cutoff", "mask_cutoff_partition")
+    mask_cutoff = 1.7
+    mask_cutoff_partition = 1
+
+    def _mix_up_grid(self):
+        # the grid this regridder returns carries no LSD offset, and the mix-up is formed from that grid
+        return np.arange(self.samples, dtype=np.float64) / self.samples
+
+    def _regrid(self, vis, weight, times, mix=None, timings=None):
+        from ..util import gaussian_process
+
+        ctx = Context.get()
+        vis_d = _dev_dataset(vis, ctx, np.complex64)
+        w_d = _dev_dataset(weight, ctx, np.float32)
+        if len(vis_d.shape) != 3:
+            raise NotImplementedError(f"SiderealRegridderGP regrids [freq, stack, time] streams; vis has shape {tuple(vis_d.shape)}.")
+        # a regular grid, padded at either end to suppress interpolation issues
+        pad = 5 * self.kernel_width
+        grid = np.arange(-pad, self.samples + pad, dtype=np.float64) / self.samples
+        # the kernels are normalised to a day that starts at zero
+        times = np.asarray(times, dtype=np.float64) - self.start
+        kernel_spec = {"name": "matern", "width": self.kernel_width, "alpha": 1.0, "nu": 2.5, "epsilon": self.epsilon}
+        vout, wout = gaussian_process.resample_device(
+            ctx, vis_d, w_d, times, grid, cutoff_dist=self.mask_cutoff, cutoff_partition=self.mask_cutoff_partition, kernel_spec=kernel_spec, pad=pad, samples=self.samples, mix=mix,
+            timings=timings
+        )
+        return grid[pad:-pad].copy(), vout, wout
 
 
 def _inz(x):

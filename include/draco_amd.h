@@ -720,6 +720,43 @@ int dmm_srcbeam_collapse(dmm_ctx* ctx, int nfreq, int nra, int npol, int nsrc, i
                          const double* pb, const double* SW, const double* SW2, const int32_t* ra_index, const uint8_t* fmask, const int64_t* rows, int64_t nobj,
                          double* beam, double* weight);
 
+/* Gaussian-process regridding (draco/util/gaussian_process.py:71-226, draco/analysis/sidereal.py:281-346), csrc/gp.hip.
+ * A group is one distinct (input mask, kept output rows) pair; frequencies that share it share its projection.  Sizes
+ * of group g: dims[g] = (n, M, nk, 0) int32 [host], n compressed input samples, M band rows (1 ... n, decided by the
+ * caller), nk kept output rows; dims_dev [ngroup][4] int32 [dev] receives a copy.  ngroup <= 65535.  Arrays [dev]:
+ *   pos [ngroup][nmax] f64 compressed sample positions, xout [ngroup][nkpad] f64 kept output positions,
+ *   Kb [ngroup][nmax][Mmax] f64, Kb[i][d] = K[i][i - d] (the lower band; whatever lies beyond it is dropped),
+ *   Y [ngroup][nmax][nkpad] f64, Y[j][b] = Kstar[b][j]; nkpad a multiple of 64,
+ *   status [ngroup], start / end [ngroup][nkpad] int32, Ac [ngroup][width][nkpad] f64.
+ * dmm_gp_masks: mask_pos / mask_nonzero [nfreq][nt] bytes = any over the stacks of weight > 0 / != 0; rowflag
+ * [nfreq nstack] bytes = any over time of weight > 0.  weight [nfreq][nstack][nt].
+ * dmm_gp_fill: Kb and Y from the positions: the product of nspec <= 4 kernels, types [nspec] and params [nspec][3] =
+ * (width, alpha, a or 0) [host], of |xa / width - xb / width| with NumPy's expressions; epsilon is added to the diagonal.
+ * dmm_gp_project: K = L L^T in place on the band, Y <- K^-1 Y (f64 MFMA), then start / end of every column b < nk of Y:
+ * the first and one past the last j with |Y[j][b]| > tol, (0, 0) if none.  A pivot that is not positive sets status to
+ * DMM_GP_NOT_POSDEF and nothing further is computed for that group (its start = end = 0).  Kb and Y may come from
+ * dmm_gp_fill or from the caller.
+ * dmm_gp_compact: Ac[w][b] = Y[start_b + w][b] for start_b + w < end_b, else 0; width >= every end - start.
+ * dmm_gp_apply: per frequency f of group freq_group[f] (-1: left alone), stack s with rowflag set and kept row b whose
+ * out_index[b] - pad lies in [0, samples): out_vis = sum_j A[b][j] x[j] over [start_b, end_b) in float64 (real and
+ * imaginary part apart, rounded to complex64), out_weight = inz(float32(sum_j A[b][j]^2 float32(inz(w[j])))) in float32,
+ * both zero where that is negative; x[j] = vis[f][s][sample_index[j]].  Mixing arrays as for dmm_regrid_band_wiener
+ * (omega, feed_mask [nfreq nstack], dphi_in [nt], dphi_out [samples]).  Entries it does not write are left alone (the
+ * caller zeroes the outputs).  vis, weight [nfreq][nstack][nt]; out_vis, out_weight [nfreq][nstack][samples]. */
+enum { DMM_GP_GAUSSIAN = 0, DMM_GP_RATIONAL = 1, DMM_GP_MATERN15 = 2, DMM_GP_MATERN25 = 3 };
+enum { DMM_GP_OK = 0, DMM_GP_NOT_POSDEF = 1 };
+int dmm_gp_masks(dmm_ctx* ctx, const float* weight, int nfreq, int nstack, int nt, uint8_t* mask_pos, uint8_t* mask_nonzero, uint8_t* rowflag);
+int dmm_gp_fill(dmm_ctx* ctx, int nspec, const int32_t* types, const double* params, double epsilon, int ngroup, const int32_t* dims, int32_t* dims_dev, int nmax,
+                int Mmax, int nkpad, const double* pos, const double* xout, double* Kb, double* Y);
+int dmm_gp_project(dmm_ctx* ctx, int ngroup, const int32_t* dims, int32_t* dims_dev, int nmax, int Mmax, int nkpad, double* Kb, double* Y, double tol, int32_t* status,
+                   int32_t* start, int32_t* end);
+int dmm_gp_compact(dmm_ctx* ctx, int ngroup, const int32_t* dims, int32_t* dims_dev, int nmax, int nkpad, int width, const double* Y, const int32_t* start,
+                   const int32_t* end, double* Ac);
+int dmm_gp_apply(dmm_ctx* ctx, int nfreq, int nstack, int nt, int samples, int pad, int ngroup, const int32_t* dims, int32_t* dims_dev, int nmax, int nkpad, int width,
+                 const int32_t* freq_group, const int32_t* sample_index, const int32_t* out_index, const int32_t* start, const int32_t* end, const double* Ac,
+                 const uint8_t* rowflag, const void* vis, const float* weight, const double* omega, const float* feed_mask, const double* dphi_in,
+                 const double* dphi_out, void* out_vis, float* out_weight);
+
 #ifdef __cplusplus
 }
 #endif

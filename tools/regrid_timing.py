@@ -9,11 +9,17 @@ read day + state, write state) and the fraction of the 8 TB/s peak.  One JSON li
 
 `--method rebin | nearest | linear | cubic` times the rebinner or one of the direct interpolators on the same data
 instead (default `band_wiener`: the above).
+
+`--method gp` times the Gaussian-process regridder (`dmm_gp_fill` / `dmm_gp_project` + `dmm_gp_compact` / `dmm_gp_apply`)
+on `--freqs` frequencies x rows / freqs stacks, once for every entry of `--gp-masks` (the number of distinct flag
+patterns among the frequencies: 1 = every frequency shares one factorisation), split into the three stages with the
+float64 FLOP rate of each against the counts of DESIGN.md section 7h, and the band-Wiener regridder on the same data.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -75,6 +81,69 @@ def other_method(args):
         del vis, w
 
 
+def gp_method(args):
+    """`--method gp`: see the module docstring.  FLOP counts per distinct mask of order n, band M, nk kept rows: fill 24
+    per evaluated entry (n M + n nk entries), projection n M^2 + 4 n M nk, apply 6 per (stack, kept row, sample of its
+    span) and frequency."""
+    import torch
+
+    from draco_amd.device import Context
+    from draco_amd.util import gaussian_process as gp
+    from draco_amd.util import regrid
+
+    ctx = Context.get()
+    rng = np.random.default_rng(1)
+    gen = torch.Generator(device=ctx.device).manual_seed(1)
+    kw, pad = 5, 25
+    grid = np.arange(-pad, args.samples + pad, dtype=np.float64) / args.samples
+    spec = {"name": "matern", "width": kw, "alpha": 1.0, "nu": 2.5, "epsilon": 1e-3}
+    nfreq = args.freqs
+    nstack = args.rows // nfreq
+    for nt in args.nt:
+        t = np.sort(np.linspace(-0.005, 1.005, nt) + rng.uniform(-0.4, 0.4, nt) * 1.01 / nt)
+        t = t[((t < 0.31) | (t > 0.33)) & ((t < 0.70) | (t > 0.705))]
+        n = len(t)
+        vis = torch.view_as_complex(torch.randn((nfreq, nstack, n, 2), dtype=torch.float32, device=ctx.device, generator=gen))
+        w0 = torch.rand((nfreq, nstack, n), dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
+        w0 *= torch.rand((nfreq, nstack, n), dtype=torch.float32, device=ctx.device, generator=gen) > 0.2
+        gp.resample_device(ctx, vis[:1, :64].contiguous(), w0[:1, :64].contiguous(), t, grid, 1.7, 1, spec, pad=pad, samples=args.samples)  # warm-up: loads the code
+        ctx.sync()
+        for nmask in args.gp_masks:
+            w = w0.clone()
+            for f in range(nfreq):  # frequency f carries flag pattern f % nmask: five samples flagged in every stack
+                k = f % nmask
+                if k:
+                    w[f, :, 100 + 7 * k : 105 + 7 * k] = 0
+            runs = []
+            for _ in range(args.windows):
+                tm, info = {}, {}
+                ctx.sync()
+                t0 = time.perf_counter()
+                gp.resample_device(ctx, vis, w, t, grid, 1.7, 1, spec, pad=pad, samples=args.samples, timings=tm, info=info)
+                ctx.sync()
+                tm["wall_ms"] = (time.perf_counter() - t0) * 1e3
+                runs.append(tm)
+            med = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+            ng = info["ngroup"]
+            fl_fill = 24.0 * sum(a * (m + k) for a, m, k in zip(info["n"], info["M"], info["nk"]))
+            fl_proj = float(sum(a * m * m + 4.0 * a * m * k for a, m, k in zip(info["n"], info["M"], info["nk"])))
+            fl_apply = 6.0 * nstack * sum(info["span_sum"][g] * info["nfreq_of"][g] for g in range(ng))
+            print(json.dumps({"case": "gp", "rows": nfreq * nstack, "nfreq": nfreq, "nstack": nstack, "nt": n, "samples": args.samples, "masks": ng, "M": max(info["M"]), "order": max(info["n"]),
+                              "kept_rows": max(info["nk"]), "max_span": max(info["span"]), "windows": args.windows,
+                              "fill_ms": round(med["fill_ms"], 3), "project_ms": round(med["project_ms"], 3), "apply_ms": round(med["apply_ms"], 3), "wall_ms": round(med["wall_ms"], 1),
+                              "fill_gflop": round(fl_fill / 1e9, 2), "project_gflop": round(fl_proj / 1e9, 2), "apply_gflop": round(fl_apply / 1e9, 2),
+                              "fill_gflops": round(fl_fill / med["fill_ms"] / 1e6, 1), "project_gflops": round(fl_proj / med["project_ms"] / 1e6, 1),
+                              "apply_gflops": round(fl_apply / med["apply_ms"] / 1e6, 1)}), flush=True)
+            del w
+        plan = regrid.RegridPlan(ctx, grid, t, kw)
+        v2, w2 = vis.reshape(-1, n), w0.reshape(-1, n)
+        ms = windows(ctx, lambda: regrid.band_wiener(ctx, plan, v2, w2, 1e-3, pad, args.samples), args.windows, 1)
+        print(json.dumps({"case": "regrid", "rows": nfreq * nstack, "nt": n, "samples": args.samples, "ms": round(float(np.median(ms)), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3)}), flush=True)
+        ctx.sync()
+        plan.close()
+        del vis, w0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=256 * 379)
@@ -83,8 +152,12 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--workspace-mib", type=int, default=0)
-    ap.add_argument("--method", choices=["band_wiener", "rebin", "nearest", "linear", "cubic"], default="band_wiener")
+    ap.add_argument("--method", choices=["band_wiener", "rebin", "nearest", "linear", "cubic", "gp"], default="band_wiener")
+    ap.add_argument("--freqs", type=int, default=256, help="gp: frequencies the rows are split into")
+    ap.add_argument("--gp-masks", type=int, nargs="+", default=[1, 256], help="gp: numbers of distinct flag patterns to time")
     args = ap.parse_args()
+    if args.method == "gp":
+        return gp_method(args)
     if args.method != "band_wiener":
         return other_method(args)
 

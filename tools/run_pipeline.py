@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """End-to-end example: sky -> SimulateSidereal -> (noise) -> MModeTransform -> {Dirty, Wiener, ML}MapMaker.
 
-    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise] [--regrid | --rebin]
+    python tools/run_pipeline.py [--config 1] [--makers dirty wiener ml] [--noise] [--regrid | --rebin | --regrid-gp]
 
 --regrid: the simulated day is first sampled onto irregular time stamps (jitter, a gap, flagged samples) as a TimeStream
 and brought back to the RA grid by SiderealRegridder before the m-mode transform.
@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--regrid", action="store_true", help="go through an irregular TimeStream and SiderealRegridder")
     ap.add_argument("--rebin", action="store_true", help="go through an irregular TimeStream, SiderealRebinner and RebinGradientCorrection")
+    ap.add_argument("--regrid-gp", action="store_true", help="go through an irregular TimeStream and SiderealRegridderGP (kernel width 5 from 512 RA samples up, else 2: "
+                    "the band-truncated kernel matrix of a short day is not positive definite at width 5)")
     ap.add_argument("--nfreq", type=int, default=0, help="override the number of frequencies")
     ap.add_argument("--pool-gb", type=float, default=0.0, help="B pool budget in GB (default: 0.6 of the free HBM)")
     args = ap.parse_args()
@@ -89,8 +91,8 @@ def main():
         gn = GaussianNoise(seed=1, ndays=733.0, recv_temp=50.0)
         gn.setup(tel)
         ss = timed("GaussianNoise_host", lambda: gn.process(ss))
-    if args.regrid or args.rebin:
-        from draco_amd.analysis.sidereal import RebinGradientCorrection, SiderealRebinner, SiderealRegridder
+    if args.regrid or args.rebin or args.regrid_gp:
+        from draco_amd.analysis.sidereal import RebinGradientCorrection, SiderealRebinner, SiderealRegridder, SiderealRegridderGP
         from draco_amd.util import regrid
 
         nra, lsd, a = ss.vis.shape[-1], 100, 5
@@ -117,6 +119,11 @@ def main():
             gc = RebinGradientCorrection()
             gc.setup(sr)  # the day has full coverage: it is its own reference
             sr = timed("RebinGradientCorrection", lambda: gc.process(sr))
+        elif args.regrid_gp:
+            rg = SiderealRegridderGP(samples=nra, kernel_width=a if nra >= 512 else 2)
+            rg.setup(tel)
+            timed("SiderealRegridderGP_first_call", lambda: rg.process(ts))
+            sr = timed("SiderealRegridderGP", lambda: rg.process(ts))
         else:
             rg = SiderealRegridder(samples=nra, kernel_width=a)
             rg.setup(tel)
