@@ -40,6 +40,8 @@ DMM_SRCBEAM_INVERSE_VARIANCE, DMM_SRCBEAM_NATURAL, DMM_SRCBEAM_UNIFORM = 0, 1, 2
 DMM_SRCBEAM_W_F32, DMM_SRCBEAM_W_F64 = 0, 1
 DMM_GP_GAUSSIAN, DMM_GP_RATIONAL, DMM_GP_MATERN15, DMM_GP_MATERN25 = 0, 1, 2, 3
 DMM_GP_OK, DMM_GP_NOT_POSDEF = 0, 1
+DMM_RFI_MAX_WINDOW, DMM_RFI_MAX_STRIP, DMM_RFI_MAX_ROW, DMM_RFI_MAX_ST_WINDOW = 255, 8192, 16384, 4096
+DMM_RFI_OR, DMM_RFI_SELECT = 0, 1
 
 
 class DmmError(RuntimeError):
@@ -168,6 +170,17 @@ _SIGS = {
     "dmm_gp_project": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp, _vp]),
     "dmm_gp_compact": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_gp_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i] + [_vp] * 15),
+    "dmm_rfi_medfilt": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dmm_rfi_quantile": (_i, [_vp, _vp, _vp, _i64, _i, _d, _vp, _vp]),
+    "dmm_rfi_sumthreshold": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
+    "dmm_rfi_sir": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp]),
+    "dmm_rfi_absdev": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dmm_rfi_nsigma": (_i, [_vp, _vp, _vp, _d, _d, _d, _i, _i64, _vp, _vp, _vp]),
+    "dmm_rfi_tv_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _d, _vp, _vp]),
+    "dmm_rfi_mask_op": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "dmm_rfi_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "dmm_rfi_radiometer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "dmm_rfi_apply_mask": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -836,6 +836,99 @@ class GridBeam(ContainerBase, _FreqMixin):
         return self.index_map["phi"]
 
 
+class _TimeAxisMixin:
+    def __init__(self, time=None, **kwargs):
+        if time is not None and not isinstance(time, (int, np.integer)):
+            time = np.asarray(time, dtype=np.float64)
+        super().__init__(time=time, **kwargs)
+
+    @property
+    def time(self):
+        return self.index_map["time"]
+
+
+class _RaAxisMixin:
+    def __init__(self, ra=None, **kwargs):
+        if isinstance(ra, (int, np.integer)):
+            ra = np.linspace(0.0, 360.0, int(ra), endpoint=False)
+        super().__init__(ra=ra, **kwargs)
+
+    @property
+    def ra(self):
+        return self.index_map["ra"]
+
+
+class _MaskMixin:
+    @property
+    def mask(self):
+        return self.datasets["mask"]
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+
+class SystemSensitivity(_TimeAxisMixin, ContainerBase, _FreqMixin):
+    """The total system sensitivity: ``measured``, ``radiometer`` and ``weight [freq, pol, time]`` float32 and
+    ``frac_lost [freq, time]`` float32 (``containers.py:596-658``)."""
+
+    _axes = ("freq", "pol", "time")
+    _dataset_spec = {
+        "measured": {"axes": ["freq", "pol", "time"], "dtype": np.float32},
+        "radiometer": {"axes": ["freq", "pol", "time"], "dtype": np.float32},
+        "weight": {"axes": ["freq", "pol", "time"], "dtype": np.float32},
+        "frac_lost": {"axes": ["freq", "time"], "dtype": np.float32},
+    }
+
+    @property
+    def measured(self):
+        return self.datasets["measured"]
+
+    @property
+    def radiometer(self):
+        return self.datasets["radiometer"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+    @property
+    def frac_lost(self):
+        return self.datasets["frac_lost"]
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+
+class RFIMask(_TimeAxisMixin, ContainerBase, _FreqMixin, _MaskMixin):
+    """An RFI mask for a timestream: ``mask [freq, time]`` bool, True for contaminated samples (``containers.py:661-681``)."""
+
+    _axes = ("freq", "time")
+    _dataset_spec = {"mask": {"axes": ["freq", "time"], "dtype": np.bool_}}
+
+
+class RFIMaskByPol(RFIMask):
+    """A polarisation-dependent RFI mask: ``mask [pol, freq, time]`` bool (``containers.py:684-706``)."""
+
+    _axes = ("pol", "freq", "time")
+    _dataset_spec = {"mask": {"axes": ["pol", "freq", "time"], "dtype": np.bool_}}
+
+
+class SiderealRFIMask(_RaAxisMixin, ContainerBase, _FreqMixin, _MaskMixin):
+    """An RFI mask for a sidereal stream: ``mask [freq, ra]`` bool (``containers.py:709-729``)."""
+
+    _axes = ("freq", "ra")
+    _dataset_spec = {"mask": {"axes": ["freq", "ra"], "dtype": np.bool_}}
+
+
+class SiderealRFIMaskByPol(SiderealRFIMask):
+    """A polarisation-dependent RFI mask as a function of RA: ``mask [pol, freq, ra]`` bool (``containers.py:732-754``)."""
+
+    _axes = ("pol", "freq", "ra")
+    _dataset_spec = {"mask": {"axes": ["pol", "freq", "ra"], "dtype": np.bool_}}
+
+
 def _all_containers():
     found, todo = [], [ContainerBase]
     while todo:

@@ -757,6 +757,58 @@ int dmm_gp_apply(dmm_ctx* ctx, int nfreq, int nstack, int nt, int samples, int p
                  const uint8_t* rowflag, const void* vis, const float* weight, const double* omega, const float* feed_mask, const double* dphi_in,
                  const double* dphi_out, void* out_vis, float* out_weight);
 
+/* RFI flagging (draco/util/filters.py:99-130, draco/util/rfi.py:8-257, draco/analysis/flagging.py:1808-2377 and
+ * :3231-3381), csrc/rfi.hip.  Planes are [nf][nt] row-major [dev]: float64 data, flags and masks one byte per sample
+ * (non-zero = flagged).  Nothing here uses a floating-point atomic; every result is independent of the launch shape.
+ * dmm_rfi_medfilt: masked moving median of nplane planes.  The window of (size_f, size_t) samples is centred on the
+ * sample and clipped at the plane's edge; the result is 0.5 (v[(n-1)/2] + v[n/2]) of the n unflagged samples v of the
+ * window in ascending order, NaN for n = 0.  Supported: both sizes odd, each <= DMM_RFI_MAX_WINDOW, their product <=
+ * DMM_RFI_MAX_STRIP (one block's strip of sorted columns lives in LDS); anything else is DMM_E_ARG.  Signed zeros are
+ * equal numbers: which of them comes out is not promised.  An unflagged NaN sorts above +inf.
+ * dmm_rfi_quantile: per row of y [nrow][n] the "split" quantile of the n' unflagged samples: t = q n', 0.5 (v[lo] +
+ * v[hi]) with lo = ceil(t) - 1, hi = floor(t) clamped to 0 ... n' - 1, NaN for n' = 0; count [nrow] int32 (may be NULL)
+ * receives n'.  n <= DMM_RFI_MAX_ROW.
+ * dmm_rfi_sumthreshold: flag <- flag | !finite(data), then nstep steps, step s with window[s] samples along axis[s]
+ * (0: frequency, 1: time) against threshold[s] [all three host arrays]: sums of data (0 where flagged) and of the
+ * count (!flag, times variance if given) over samples j - m + 1 ... j (below 0: sample 0), the count sum square-rooted
+ * with correct_for_missing; |sum| (sum with only_positive) > count threshold flags j - m + 1 ... j.  A step completes
+ * before the next reads the flags.  hit [nf][nt] bytes is scratch.  window[s] <= DMM_RFI_MAX_ST_WINDOW.
+ * dmm_rfi_sir: out = flag | SIR(flag) along the axis (accumulate: out |= that): per line the strictly sequential
+ * float64 running sum S of flag + (eta - 1), flagged where max(S after the sample) >= min(S before it) with the
+ * reference's ranges.  work: 2 nf nt float64.  out may not be flag.
+ * dmm_rfi_absdev: dy = y - med (dy may be NULL), ady = |dy|, or the modulus when the imaginary parts are given.
+ * dmm_rfi_nsigma: s = scale mad, ratio = ady (1 / s) with 1 / 0 = 0 (divide: ratio = ady / s), a NaN ratio replaced by
+ * nan_fill unless that is NaN itself, variance = s s and mask = ratio > nsigma (either may be NULL).
+ * dmm_rfi_tv_flag: frac = float32(count / N) of x > chan_thr[c] over the N rows chan_rows[chan_ptr[c] ... chan_ptr[c+1])
+ * of the channel c = row_chan[row] the row keeps (1 where row_chan < 0), mask = frac > float32(f).  frac may be NULL.
+ * dmm_rfi_mask_op: out = a | b (DMM_RFI_OR), c ? a : b (DMM_RFI_SELECT); out may be an input.
+ * dmm_rfi_rows: y[f][t] -= row_sub[f], flag[f][t] |= row_flag[f] (either pair may be NULL).
+ * dmm_rfi_radiometer: measured, radiometer, weight [nf][npol][nt] float32 -> y [npol][nf][nt] = float64(measured
+ * float32(1 / radiometer)) with 1 / 0 = 0, flag = weight == 0.
+ * dmm_rfi_apply_mask: weight [dims...][nt] float32 *= !mask for the nsel samples data_index [dev] of the last axis,
+ * each reading sample mask_index [dev] of the mask's nmask; the mask element of leading coordinates (i0, ...) lies at
+ * sum_d i_d mask_stride[d] + sample mask_stride_t (a stride of 0 broadcasts).  dims, mask_stride [ndim <= 4, host]. */
+#define DMM_RFI_MAX_WINDOW 255
+#define DMM_RFI_MAX_STRIP 8192
+#define DMM_RFI_MAX_ROW 16384
+#define DMM_RFI_MAX_ST_WINDOW 4096
+enum { DMM_RFI_OR = 0, DMM_RFI_SELECT = 1 };
+int dmm_rfi_medfilt(dmm_ctx* ctx, const double* x, const uint8_t* flag, int nplane, int nf, int nt, int size_f, int size_t_, double* out);
+int dmm_rfi_quantile(dmm_ctx* ctx, const double* y, const uint8_t* flag, int64_t nrow, int n, double q, double* out, int32_t* count);
+int dmm_rfi_sumthreshold(dmm_ctx* ctx, const double* data, const double* variance, uint8_t* flag, uint8_t* hit, int nf, int nt, int nstep, const int32_t* window,
+                         const int32_t* axis, const double* threshold, int correct_for_missing, int only_positive);
+int dmm_rfi_sir(dmm_ctx* ctx, const uint8_t* flag, int nf, int nt, int axis, double eta, int accumulate, double* work, uint8_t* out);
+int dmm_rfi_absdev(dmm_ctx* ctx, const double* y, const double* med, const double* y_imag, const double* med_imag, int64_t n, double* dy, double* ady);
+int dmm_rfi_nsigma(dmm_ctx* ctx, const double* ady, const double* mad, double scale, double nsigma, double nan_fill, int divide, int64_t n, double* ratio,
+                   double* variance, uint8_t* mask);
+int dmm_rfi_tv_flag(dmm_ctx* ctx, const double* x, int nf, int nt, const int32_t* row_chan, int nchan, const int32_t* chan_ptr, const int32_t* chan_rows, int nrows,
+                    const double* chan_thr, double f, float* frac, uint8_t* mask);
+int dmm_rfi_mask_op(dmm_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, const uint8_t* c, int64_t n, uint8_t* out);
+int dmm_rfi_rows(dmm_ctx* ctx, double* y, uint8_t* flag, const double* row_sub, const uint8_t* row_flag, int nf, int nt);
+int dmm_rfi_radiometer(dmm_ctx* ctx, const float* measured, const float* radiometer, const float* weight, int nf, int npol, int nt, double* y, uint8_t* flag);
+int dmm_rfi_apply_mask(dmm_ctx* ctx, float* weight, int ndim, const int64_t* dims, int nt, const uint8_t* mask, const int64_t* mask_stride, int64_t mask_stride_t,
+                       int nmask, int nsel, const int32_t* data_index, const int32_t* mask_index);
+
 #ifdef __cplusplus
 }
 #endif

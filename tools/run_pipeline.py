@@ -6,6 +6,7 @@
 --regrid: the simulated day is first sampled onto irregular time stamps (jitter, a gap, flagged samples) as a TimeStream
 and brought back to the RA grid by SiderealRegridder before the m-mode transform.
 --rebin: the same TimeStream goes through SiderealRebinner and RebinGradientCorrection instead.
+--rfi (with one of the three): bursts are injected into the TimeStream and RFIMask -> ApplyTimeFreqMask run ahead of the regridder.
 
 Mirrors the reference's tutorial pipeline (doc/pipeline_params.yaml:1-35) with this repo's
 task classes.  Prints per-task wall time (device synchronised) and a few sanity numbers.
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--rebin", action="store_true", help="go through an irregular TimeStream, SiderealRebinner and RebinGradientCorrection")
     ap.add_argument("--regrid-gp", action="store_true", help="go through an irregular TimeStream and SiderealRegridderGP (kernel width 5 from 512 RA samples up, else 2: "
                     "the band-truncated kernel matrix of a short day is not positive definite at width 5)")
+    ap.add_argument("--rfi", action="store_true", help="with --regrid / --rebin / --regrid-gp: inject bursts into the TimeStream, then RFIMask and ApplyTimeFreqMask ahead of the regridder")
     ap.add_argument("--nfreq", type=int, default=0, help="override the number of frequencies")
     ap.add_argument("--pool-gb", type=float, default=0.0, help="B pool budget in GB (default: 0.6 of the free HBM)")
     args = ap.parse_args()
@@ -111,6 +113,17 @@ def main():
         tw[..., :: 7] = 0.0
         ts.attach("vis_weight", tw)
         ts.attrs["lsd"] = lsd
+        if args.rfi:  # bursts on a few time samples of every product, found on one stack entry and masked in all
+            from draco_amd.analysis.flagging import ApplyTimeFreqMask, RFIMask
+
+            tv = ts.vis.device(ctx)
+            bursts = rng.choice(len(lsds), size=max(2, len(lsds) // 100), replace=False)
+            tv[..., torch.from_numpy(bursts).to(ctx.device)] += 50.0 * tv.abs().mean()
+            rfimask = timed("RFIMask", lambda: RFIMask(stack_ind=0).process(ts))
+            ts = timed("ApplyTimeFreqMask", lambda: ApplyTimeFreqMask().process(ts, rfimask))
+            found = rfimask.mask[:][:, bursts].mean()
+            report["rfi_masked_fraction"] = float(rfimask.mask[:].mean())
+            report["rfi_bursts_found"] = float(found)
         if args.rebin:
             rb = SiderealRebinner(samples=nra)
             rb.setup(tel)
