@@ -42,6 +42,7 @@ DMM_GP_GAUSSIAN, DMM_GP_RATIONAL, DMM_GP_MATERN15, DMM_GP_MATERN25 = 0, 1, 2, 3
 DMM_GP_OK, DMM_GP_NOT_POSDEF = 0, 1
 DMM_RFI_MAX_WINDOW, DMM_RFI_MAX_STRIP, DMM_RFI_MAX_ROW, DMM_RFI_MAX_ST_WINDOW = 255, 8192, 16384, 4096
 DMM_RFI_OR, DMM_RFI_SELECT = 0, 1
+DMM_SENS_MAX_GROUP = 64
 
 
 class DmmError(RuntimeError):
@@ -181,6 +182,9 @@ _SIGS = {
     "dmm_rfi_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
     "dmm_rfi_radiometer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "dmm_rfi_apply_mask": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "dmm_sens_measured": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_sens_radiometer": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    "dmm_sens_negative_autos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -1,0 +1,1 @@
+from .sensitivity import ComputeSystemSensitivity  # noqa: F401

@@ -7,8 +7,8 @@ in-place semantics (the input container is returned with its weights zeroed).  I
 (``test/pipe_config.yaml:100-131``); the map-makers treat zero weights as "row absent".
 
 The RFI part (``flagging.py:1808-2377`` and ``:3231-3381``): ``RFISensitivityMask``, ``RFIMask`` and
-``ApplyTimeFreqMask`` (alias ``ApplyRFIMask``) with the functions ``mad``, ``tv_channels_flag``, ``sigma_to_p``,
-``p_to_sigma`` and ``inverse_binom_cdf_prob``.  The planes stay on the device across the iterations of a mask task:
+``ApplyTimeFreqMask`` (alias ``ApplyRFIMask``), ``NegativeAutosMask`` (``:666-699``), with the functions ``mad``,
+``tv_channels_flag``, ``sigma_to_p``, ``p_to_sigma`` and ``inverse_binom_cdf_prob``.  The planes stay on the device across the iterations of a mask task:
 medians, SumThreshold, SIR and the elementwise stages are the kernels of ``csrc/rfi.hip``; only scalars (the TV
 thresholds, from SciPy) and the frequency-length arrays of the static channel mask are formed on the host.  The
 convention is ``True`` for contaminated samples.
@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import copy as _copy
 import ctypes as C
+import logging
 
 import numpy as np
 import torch
@@ -486,6 +487,33 @@ class RFIMask(ContainerTask):
         out = kind(axes_from=sstream, attrs_from=sstream)
         out.mask[:] = mask
         self.log.info("Flagging %0.2f%% of data due to RFI." % (100.0 * mask.mean()))
+        return out
+
+
+class NegativeAutosMask(ContainerTask):
+    """Flag a (frequency, time) sample if any autocorrelation is negative there (drop-in for ``flagging.py:666-699``).
+
+    The autocorrelations are the stack entries whose ``prodstack`` pair is one input twice; their rows are read on the
+    device (``dmm_sens_negative_autos``, the row list ``ComputeSystemSensitivity``'s radiometer kernel takes) and the
+    mask of the ``RFIMask`` that comes back is written there.
+    """
+
+    def process(self, data):
+        data.redistribute("freq")
+        ps = _prodstack(data)
+        ctx = Context.get()
+        vis = _dev_dataset(data.vis, ctx, np.complex64)
+        nfreq, nstack, ntime = (int(s) for s in vis.shape)
+        if ps is None or len(ps) != nstack:
+            raise ValueError("NegativeAutosMask needs the prod/stack index maps to find the auto-correlations")
+        rows = np.ascontiguousarray(np.flatnonzero(ps["input_a"] == ps["input_b"]), dtype=np.int32)
+        mask = torch.empty((nfreq, ntime), dtype=torch.uint8, device=ctx.device)
+        table = torch.empty((len(rows) + 1,), dtype=torch.int32, device=ctx.device)
+        _lib.check(_lib.lib.dmm_sens_negative_autos(ctx.handle, ptr(vis), nfreq, nstack, ntime, len(rows), C.c_void_p(rows.ctypes.data), ptr(table), ptr(mask)))
+        if self.log.isEnabledFor(logging.DEBUG):
+            self.log.debug(f"{100.0 * float(mask.float().mean()):.2f}% of data flagged due to negative autos.")
+        out = containers.RFIMask(axes_from=data, attrs_from=data, allocate=False)
+        out.attach("mask", mask.view(torch.bool))
         return out
 
 

@@ -268,15 +268,7 @@ def _cmap(i, j, n):
     return (n * (n + 1) // 2) - ((n - i) * (n - i + 1) // 2) + (j - i)
 
 
-def _find_inputs(input_index, inputs, require_match=False):
-    """``tools.find_inputs`` (``util/tools.py:130-169``): match on ``correlator_input`` or ``chan_id``."""
-    names = input_index.dtype.names or ()
-    field = "correlator_input" if "correlator_input" in names else ("chan_id" if "chan_id" in names else None)
-    if field is None:
-        raise ValueError("`input_index` must have either a `chan_id` or `correlator_input` field.")
-    if field not in (inputs.dtype.names or ()):
-        raise ValueError(f"`inputs` array does not have a `{field!s}` field.")
-    return tools.find_keys(input_index[field], inputs[field], require_match=require_match)
+_find_inputs = tools.find_inputs  # the name this module has always used for it
 
 
 class TelescopeStreamMixIn:
@@ -298,33 +290,7 @@ class TelescopeStreamMixIn:
         self.bt_rev["conjugate"] = np.where(fm, np.asarray(tel.feedconj)[triu], 0)
 
 
-def _redefine_stack_index_map(tel, tel_index, prod, stack, reverse_stack):
-    """Give every stack entry a representative product the telescope can use (``util/tools.py:359-414``).
-
-    A product is *usable* when both of its inputs exist in the telescope (``tel_index[i]`` is not None) and the pair
-    is not masked there.  Entries whose current representative is usable keep it; the others take the first usable
-    member of their stack (lowest product index) together with that member's conjugation flag.  Returns the new map
-    and, per entry, whether a usable representative exists at all.
-    """
-    present = np.array([t is not None for t in tel_index], dtype=bool)
-    slot = np.array([t if t is not None else 0 for t in tel_index], dtype=np.int64)
-    pa, pb = np.asarray(prod["input_a"], dtype=np.int64), np.asarray(prod["input_b"], dtype=np.int64)
-    usable = present[pa] & present[pb] & np.asarray(tel.feedmask)[slot[pa], slot[pb]]  # per product of the file
-
-    nstack = stack.size
-    member_of = np.asarray(reverse_stack["stack"], dtype=np.int64)
-    cand = np.flatnonzero(usable & (member_of >= 0) & (member_of < nstack))
-    first = np.full(nstack, len(pa), dtype=np.int64)
-    np.minimum.at(first, member_of[cand], cand)  # lowest usable member of every stack
-
-    current = np.asarray(stack["prod"], dtype=np.int64)
-    keep = usable[current]
-    found = keep | (first < len(pa))
-    swap = ~keep & found
-    out = stack.copy()
-    out["prod"][swap] = first[swap]
-    out["conjugate"][swap] = reverse_stack["conjugate"][first[swap]]
-    return out, found
+_redefine_stack_index_map = tools.redefine_stack_from_index
 
 
 class CollateProducts(TelescopeStreamMixIn, ContainerTask):

@@ -72,6 +72,7 @@ class Dataset:
                 torch.int32: np.int32,
                 torch.uint8: np.uint8,
                 torch.uint16: np.uint16,
+                torch.bool: np.bool_,
             }[self._dev_t.dtype]
         )
 
@@ -378,14 +379,34 @@ class SiderealStream(ContainerBase, _FreqMixin, _VisMixin):
         return t
 
 
+class _DatasetGroup:
+    """The datasets ``<group>/<name>`` of a container under their short names: ``data["flags"]["frac_lost"]``."""
+
+    def __init__(self, cont, group):
+        self._cont, self._prefix = cont, group + "/"
+
+    def __getitem__(self, name):
+        return self._cont.datasets[self._prefix + name]
+
+    def __contains__(self, name):
+        return self._prefix + name in self._cont.datasets
+
+
 class TimeStream(ContainerBase, _FreqMixin, _VisMixin):
     """Time-ordered visibilities: ``vis [freq, stack, time]`` complex64 + ``vis_weight`` float32, ``time`` the samples'
-    UNIX time stamps (``containers.py:1195-1242``; gain and input_flags datasets are not carried)."""
+    UNIX time stamps (``containers.py:821-880``).  Optional, through :meth:`add_dataset`: ``input_flags [input, time]``
+    float32, ``gain [freq, input, time]`` complex64, and ``flags/frac_lost [freq, time]`` float32, the fraction of
+    correlator packets lost, which is read as ``data["flags"]["frac_lost"]``."""
 
     _axes = ("freq", "stack", "time", "prod", "input")
     _dataset_spec = {
         "vis": {"axes": ["freq", "stack", "time"], "dtype": np.complex64},
         "vis_weight": {"axes": ["freq", "stack", "time"], "dtype": np.float32},
+    }
+    _optional_spec = {
+        "input_flags": {"axes": ["input", "time"], "dtype": np.float32},  # containers.py:854-859
+        "gain": {"axes": ["freq", "input", "time"], "dtype": np.complex64},  # containers.py:860-868
+        "flags/frac_lost": {"axes": ["freq", "time"], "dtype": np.float32},
     }
 
     def __init__(self, time=None, stack=None, prod=None, input=None, reverse_map_stack=None, **kwargs):
@@ -397,9 +418,34 @@ class TimeStream(ContainerBase, _FreqMixin, _VisMixin):
         if reverse_map_stack is not None:
             self.reverse_map["stack"] = reverse_map_stack
 
+    def add_dataset(self, name, allocate=True):
+        self._dataset_spec = dict(self._dataset_spec)
+        self._dataset_spec[name] = spec = self._optional_spec[name]
+        if allocate:
+            self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=spec["dtype"]), attrs={"axis": spec["axes"]})
+
+    def _groups(self):
+        return {k.split("/")[0] for k in self.datasets if "/" in k}
+
+    def __getitem__(self, name):
+        if name not in self.datasets and name in self._groups():
+            return _DatasetGroup(self, name)
+        return self.datasets[name]
+
+    def __contains__(self, name):
+        return name in self.datasets or name in self._groups()
+
     @property
     def time(self):
         return self.index_map["time"]
+
+    @property
+    def input_flags(self):
+        return self._optional("input_flags")
+
+    @property
+    def gain(self):
+        return self._optional("gain")
 
     prodstack = SiderealStream.prodstack
 

@@ -106,6 +106,12 @@ class TransitTelescope:
         return self.cyl_sep
 
     @property
+    def cylinder_width(self):
+        """East-west width of a cylinder in metres, under the name ``ComputeSystemSensitivity`` reads: the cylinders
+        of the regular grid touch, so it equals their spacing."""
+        return self.cyl_sep
+
+    @property
     def freq_start(self):
         """The highest frequency of the band in MHz, under the name ``DPSSFilterMMode`` reads (driftscan's band runs
         from ``freq_start`` down to ``freq_end``)."""

@@ -42,6 +42,65 @@ def find_keys(key_list, keys, require_match=False):
     return found
 
 
+def find_inputs(input_index, inputs, require_match=False):
+    """Position of every entry of ``inputs`` inside ``input_index`` (``tools.py:130-170``): :func:`find_keys` on the
+    ``correlator_input`` field, or on ``chan_id`` where ``input_index`` has no ``correlator_input``.  An index without
+    either field, or ``inputs`` without the chosen one, raises ``ValueError``."""
+    names = input_index.dtype.names or ()
+    field = "correlator_input" if "correlator_input" in names else ("chan_id" if "chan_id" in names else None)
+    if field is None:
+        raise ValueError("`input_index` must have either a `chan_id` or `correlator_input` field.")
+    if field not in (inputs.dtype.names or ()):
+        raise ValueError(f"`inputs` array does not have a `{field!s}` field.")
+    return find_keys(input_index[field], inputs[field], require_match=require_match)
+
+
+def redefine_stack_index_map(telescope, inputs, prod, stack, reverse_stack):
+    """Give every stack entry a representative product between unmasked inputs (``tools.py:359-414``).
+
+    A product is *usable* when both of its inputs exist in the telescope and ``telescope.feedmask`` has the pair.
+    Entries whose representative is usable keep it (one vectorised test over the stack axis); only the products of the
+    others are searched, and each of those entries takes the first usable product that was stacked into it, in product
+    order, with that product's conjugation flag from ``reverse_stack``.  Returns ``(stack_new, stack_flag)``: the new map and, per entry, whether a usable representative
+    exists at all (an entry without one keeps its old representative)."""
+    return redefine_stack_from_index(telescope, find_inputs(telescope.input_index, inputs, require_match=False), prod, stack, reverse_stack)
+
+
+def redefine_stack_from_index(telescope, tel_index, prod, stack, reverse_stack):
+    """:func:`redefine_stack_index_map` for a caller that already holds ``tel_index``, the telescope's number of every
+    input of the data (``None``: not in the telescope)."""
+    present = np.array([t is not None for t in tel_index], dtype=bool)
+    slot = np.array([t if t is not None else 0 for t in tel_index], dtype=np.int64)
+    pa, pb = _fields(prod, 2)
+    usable = present[pa] & present[pb] & np.asarray(telescope.feedmask)[slot[pa], slot[pb]]  # per product of the data
+    nstack = stack.size
+    member_of = np.asarray(reverse_stack["stack"]).astype(np.int64)
+    keep = usable[np.asarray(stack["prod"]).astype(np.int64)]
+    # only the entries that need another representative are searched: the lowest usable product stacked into each
+    stacked = (member_of >= 0) & (member_of < nstack)
+    cand = np.flatnonzero(usable & stacked & ~keep[np.where(stacked, member_of, 0)])
+    first = np.full(nstack, len(pa), dtype=np.int64)
+    np.minimum.at(first, member_of[cand], cand)
+    swap = first < len(pa)
+    out = stack.copy()
+    out["prod"][swap] = first[swap]
+    out["conjugate"][swap] = reverse_stack["conjugate"][first[swap]]
+    return out, keep | swap
+
+
+def unique_columns(flags):
+    """The distinct columns of a Boolean ``[n, m]`` array: ``(columns [n, k] bool, inverse [m])`` with ``columns[:,
+    inverse]`` the input.  The rows are packed to bits first, so that ``np.unique`` sorts ``ceil(n / 8)`` bytes per
+    column as one key instead of ``n`` values; the order of the distinct columns is that of the packed keys."""
+    flags = np.ascontiguousarray(np.asarray(flags, dtype=bool))
+    packed = np.ascontiguousarray(np.packbits(flags, axis=0).T)  # [m, nbyte]
+    if packed.shape[1] == 0:
+        return flags[:, :1] if flags.shape[1] else flags, np.zeros(flags.shape[1], dtype=np.int64)
+    keys = packed.view(np.dtype((np.void, packed.shape[1]))).ravel()
+    _, first, inverse = np.unique(keys, return_index=True, return_inverse=True)
+    return flags[:, first], np.asarray(inverse).reshape(-1).astype(np.int64)
+
+
 _WINDOW_COEFFS = {
     "uniform": (1.0, 0.0, 0.0, 0.0),
     "hann": (0.5, -0.5, 0.0, 0.0),

@@ -809,6 +809,36 @@ int dmm_rfi_radiometer(dmm_ctx* ctx, const float* measured, const float* radiome
 int dmm_rfi_apply_mask(dmm_ctx* ctx, float* weight, int ndim, const int64_t* dims, int nt, const uint8_t* mask, const int64_t* mask_stride, int64_t mask_stride_t,
                        int nmask, int nsel, const int32_t* data_index, const int32_t* mask_index);
 
+/* System sensitivity of a time stream (draco/analysis/sensitivity.py:11-261) and the mask of negative autocorrelations
+ * (draco/analysis/flagging.py:666-699), csrc/sensitivity.hip.  vis complex64 and weight float32 are [nf][nstack][nt]
+ * [dev] and are read once; sums run in float64 in a fixed order (no atomics: two runs give the same bits) and are
+ * rounded to float32 at the store.  inv0(x) = 1 / x, 0 for x = 0.
+ * Index tables are [host] pointers, checked before anything is launched (a row index outside the stack axis, a column
+ * index outside cnt, a *_ptr table that does not start at 0 or decreases: DMM_E_ARG); the library copies them to
+ * `tables` [dev], int32 scratch of the caller's with room for every table of the call, in the order of the argument
+ * list.  Everything else is [dev].
+ * cnt [nstack][ncol] float32: the redundancy of every stack entry under every distinct column of input flags; col
+ * [niff][nt] [host]: the column of the sample (f % niff, t), niff = 1 or nf.
+ * dmm_sens_measured: the rows of polarisation p are rows[pol_ptr[p] ... pol_ptr[p+1]) [host], each a pair (stack entry
+ * s, factor k = 1 for an autocorrelation, else 2).  With c = cnt[s][col], w = weight[f][s][t]: V = sum c c k [w > 0] / w,
+ * C = sum c k [w > 0]; measured [nf][npol][nt] = sqrt(2 V inv0(C C)), out_weight = C.  tables: niff nt + npol + 1 +
+ * 2 pol_ptr[npol] words.  A polarisation without rows gives zeros.
+ * dmm_sens_radiometer: the autocorrelation rows of group g (one polarisation of the inputs at one east-west position)
+ * are auto_rows[grp_ptr[g] ... grp_ptr[g+1]) [host], ngroup <= DMM_SENS_MAX_GROUP; the ordered group pairs (g, h) of
+ * polarisation p are pairs[pair_ptr[p] ... pair_ptr[p+1]) [host].  With n = c [w > 0], a = Re vis: S_g = sum n a, N_g =
+ * sum n, R = sum S_g S_h, K = sum N_g N_h, nint = dnu_tint (1 - frac_lost[f][t]) (frac_lost [nf][nt] float32 or NULL
+ * for 0): radiometer [nf][npol][nt] = sqrt(2 R inv0(nint K K)), NaN for R < 0 or a NaN dnu_tint; frac_out [nf][nt] receives frac_lost.
+ * tables: niff nt + ngroup + 1 + grp_ptr[ngroup] + npol + 1 + 2 pair_ptr[npol] words.
+ * dmm_sens_negative_autos: mask [nf][nt] bytes = 1 where Re vis[f][s][t] < 0 for any s of auto_rows [nauto] [host];
+ * tables: nauto words. */
+#define DMM_SENS_MAX_GROUP 64
+int dmm_sens_measured(dmm_ctx* ctx, const float* weight, int nf, int nstack, int nt, const float* cnt, int ncol, int niff, const int32_t* col, int npol,
+                      const int32_t* pol_ptr, const int32_t* rows, int32_t* tables, float* measured, float* out_weight);
+int dmm_sens_radiometer(dmm_ctx* ctx, const void* vis, const float* weight, int nf, int nstack, int nt, const float* cnt, int ncol, int niff, const int32_t* col,
+                        int ngroup, const int32_t* grp_ptr, const int32_t* auto_rows, int npol, const int32_t* pair_ptr, const int32_t* pairs, const float* frac_lost,
+                        double dnu_tint, int32_t* tables, float* radiometer, float* frac_out);
+int dmm_sens_negative_autos(dmm_ctx* ctx, const void* vis, int nf, int nstack, int nt, int nauto, const int32_t* auto_rows, int32_t* tables, uint8_t* mask);
+
 #ifdef __cplusplus
 }
 #endif
