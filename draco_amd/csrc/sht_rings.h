@@ -42,6 +42,11 @@ __device__ __forceinline__ int class_ring(const RingClass& rc, const ShtGeom& g,
 
 // direct evaluation, block = (ring of the class, f): map(j) = Re sum_m fac_m b_m e^{i m phi_j}.
 // Fallback for rings whose FFT does not fit the LDS (nside > 512) and the check of the FFT path.
+// The phasor of the direct sums is rotated step by step; the rotation's rounding error grows with the number of steps
+// (over the 4092 pixels of a cap ring of nside 1024 the analysis was 17 times as far from a long-double evaluation as
+// float64 NumPy), so it restarts from sincospi of the exactly reduced angle every kDirectRun steps.  Sums of at most
+// kDirectRun terms keep the values they had.
+constexpr int kDirectRun = 64;
 template <int NPOL>
 __global__ __launch_bounds__(kThreads) void k_ring_synth(RingParams p, RingClass rc) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -70,19 +75,23 @@ __global__ __launch_bounds__(kThreads) void k_ring_synth(RingParams p, RingClass
   for (int j = threadIdx.x; j < nphi; j += kThreads) {
     double sn, cs;
     sincospi(2.0 * (double)j / (double)nphi, &sn, &cs);
-    double pr = 1.0, pi_ = 0.0;
     double acc[NPOL];
 #pragma unroll
     for (int q = 0; q < NPOL; ++q) acc[q] = 0.0;
-    for (int m = 0; m < nm; ++m) {
+    for (int m0 = 0; m0 < nm; m0 += kDirectRun) {
+      double pr, pi_;  // e^{2 pi i m0 j / nphi}, then rotated by one pixel step per m
+      sincospi(2.0 * (double)(((int64_t)m0 * j) % nphi) / (double)nphi, &pi_, &pr);
+      const int m1 = min(m0 + kDirectRun, nm);
+      for (int m = m0; m < m1; ++m) {
 #pragma unroll
-      for (int q = 0; q < NPOL; ++q) {
-        const double2 cm = c[q * nm + m];
-        acc[q] = fma(cm.x, pr, fma(-cm.y, pi_, acc[q]));
+        for (int q = 0; q < NPOL; ++q) {
+          const double2 cm = c[q * nm + m];
+          acc[q] = fma(cm.x, pr, fma(-cm.y, pi_, acc[q]));
+        }
+        const double nr = pr * cs - pi_ * sn;
+        pi_ = fma(pr, sn, pi_ * cs);
+        pr = nr;
       }
-      const double nr = pr * cs - pi_ * sn;
-      pi_ = fma(pr, sn, pi_ * cs);
-      pr = nr;
     }
 #pragma unroll
     for (int q = 0; q < NPOL; ++q) p.map[((int64_t)f * NPOL + q) * p.npix + base + j] = acc[q];
@@ -336,22 +345,27 @@ __global__ __launch_bounds__(kThreads) void k_ring_anal(RingParams p, RingClass 
   const double w = 4.0 * M_PI / (double)p.npix;
   for (int m = threadIdx.x; m < nm; m += kThreads) {
     // e^{-i m phi_j} = e^{-i m phi0} * step^j, step = e^{-2 pi i m / nphi} (m reduced mod nphi exactly)
+    const int mr = m % nphi;
     double sn, cs;
-    sincospi(-2.0 * (double)(m % nphi) / (double)nphi, &sn, &cs);
-    double pr = 1.0, pi_ = 0.0;
+    sincospi(-2.0 * (double)mr / (double)nphi, &sn, &cs);
     double are[NPOL], aim[NPOL];
 #pragma unroll
     for (int q = 0; q < NPOL; ++q) are[q] = aim[q] = 0.0;
-    for (int j = 0; j < nphi; ++j) {
+    for (int j0 = 0; j0 < nphi; j0 += kDirectRun) {
+      double pr, pi_;  // step^j0, then rotated by one step per pixel
+      sincospi(-2.0 * (double)(((int64_t)mr * j0) % nphi) / (double)nphi, &pi_, &pr);
+      const int j1 = min(j0 + kDirectRun, nphi);
+      for (int j = j0; j < j1; ++j) {
 #pragma unroll
-      for (int q = 0; q < NPOL; ++q) {
-        const double v = px[q * nphi + j];
-        are[q] = fma(v, pr, are[q]);
-        aim[q] = fma(v, pi_, aim[q]);
+        for (int q = 0; q < NPOL; ++q) {
+          const double v = px[q * nphi + j];
+          are[q] = fma(v, pr, are[q]);
+          aim[q] = fma(v, pi_, aim[q]);
+        }
+        const double nr = pr * cs - pi_ * sn;
+        pi_ = fma(pr, sn, pi_ * cs);
+        pr = nr;
       }
-      const double nr = pr * cs - pi_ * sn;
-      pi_ = fma(pr, sn, pi_ * cs);
-      pr = nr;
     }
     double s0, c0;
     sincos(-(double)m * phi0, &s0, &c0);
