@@ -43,6 +43,7 @@ DMM_GP_OK, DMM_GP_NOT_POSDEF = 0, 1
 DMM_RFI_MAX_WINDOW, DMM_RFI_MAX_STRIP, DMM_RFI_MAX_ROW, DMM_RFI_MAX_ST_WINDOW = 255, 8192, 16384, 4096
 DMM_RFI_OR, DMM_RFI_SELECT = 0, 1
 DMM_SENS_MAX_GROUP = 64
+DMM_PS_MAX_BINS = 4096
 
 
 class DmmError(RuntimeError):
@@ -185,6 +186,10 @@ _SIGS = {
     "dmm_sens_measured": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_sens_radiometer": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
     "dmm_sens_negative_autos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_uv_fft2_supported": (_i, [_i]),
+    "dmm_uv_fft2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64]),
+    "dmm_ps3d_cross": (_i, [_vp, _vp, _vp, _i, _i, _i64, _d, _vp]),
+    "dmm_ps_cyl_bin": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -839,6 +839,27 @@ int dmm_sens_radiometer(dmm_ctx* ctx, const void* vis, const float* weight, int 
                         double dnu_tint, int32_t* tables, float* radiometer, float* frac_out);
 int dmm_sens_negative_autos(dmm_ctx* ctx, const void* vis, int nf, int nstack, int nt, int nauto, const int32_t* auto_rows, int32_t* tables, uint8_t* mask);
 
+/* 3-D power spectrum of a ring-map delay cube (draco/analysis/powerspec.py:539-1017), csrc/powerspec.hip.  float64
+ * throughout, no floating-point atomics: two runs give the same bits.  Everything is [dev] unless marked [host].
+ * dmm_uv_fft2: spectrum [npol][nel][nra][ndelay] complex128 (the delay transform of a ring map, baseline = pol x el) ->
+ * vis [npol][ndelay][nra][nel] complex128 = fftshift(fft2(x * (w_ra (x) w_el))) / (nra nel) per (pol, delay) plane; w_ra
+ * [nra] and w_el [nel] float64, both NULL for no taper.  Two in-LDS row transforms (along el, then along ra in place in
+ * vis), run slab by slab of about slab_mib MiB of vis (0: 128); spectrum is not modified.  dmm_uv_fft2_supported(n):
+ * 1 if an axis of length n can be transformed (powers of two to 8192, other lengths to 4096); a longer axis is
+ * DMM_E_UNSUPPORTED, before anything is launched.
+ * dmm_ps3d_cross: out [npol1 npol2][ncell] = ps_norm vis1[p1] conj(vis2[p2]), p = p1 npol2 + p2, vis1 [npol1][ncell],
+ * vis2 [npol2][ncell] complex128 (they may be the same array: the imaginary part of an auto spectrum is exactly 0).
+ * dmm_ps_cyl_bin: per plane (pol, delay) of spec [nplane][nu nv] complex128 and per bin b of binmap [nu nv] int16
+ * [host] (-1: the cell belongs to no bin; a value >= nbins is DMM_E_ARG), with w = 1 (sigma NULL) or 1 / |sigma|^2, 0
+ * where sigma [nplane][nu nv] complex128 is 0:  out_spec [nplane][nbins] = sum w p / sum w, out_weight = sum w, out_neff
+ * = (sum w)^2 / sum w^2, summed in a fixed order; an empty bin gives NaN, 0, NaN.  Synchronises the context's stream. */
+#define DMM_PS_MAX_BINS 4096
+int dmm_uv_fft2_supported(int n);
+int dmm_uv_fft2(dmm_ctx* ctx, const void* spectrum, int npol, int nel, int nra, int ndelay, const double* w_ra, const double* w_el, void* vis, int64_t slab_mib);
+int dmm_ps3d_cross(dmm_ctx* ctx, const void* vis1, const void* vis2, int npol1, int npol2, int64_t ncell, double ps_norm, void* out);
+int dmm_ps_cyl_bin(dmm_ctx* ctx, const void* spec, const void* sigma, const int16_t* binmap, int nplane, int nu, int nv, int nbins, void* out_spec, double* out_weight,
+                   double* out_neff);
+
 #ifdef __cplusplus
 }
 #endif
