@@ -44,6 +44,8 @@ DMM_RFI_MAX_WINDOW, DMM_RFI_MAX_STRIP, DMM_RFI_MAX_ROW, DMM_RFI_MAX_ST_WINDOW = 
 DMM_RFI_OR, DMM_RFI_SELECT = 0, 1
 DMM_SENS_MAX_GROUP = 64
 DMM_PS_MAX_BINS = 4096
+DMM_STACK_SRC_CHUNK, DMM_STACK_MAX_FREQ = 256, 2048
+DMM_STACK3D_INPUT, DMM_STACK3D_DEC, DMM_STACK3D_PATCH = 0, 1, 2
 
 
 class DmmError(RuntimeError):
@@ -190,6 +192,9 @@ _SIGS = {
     "dmm_uv_fft2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64]),
     "dmm_ps3d_cross": (_i, [_vp, _vp, _vp, _i, _i, _i64, _d, _vp]),
     "dmm_ps_cyl_bin": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dmm_ringmap_extract": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_source_stack": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
+    "dmm_ringmap_stack3d": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

@@ -21,6 +21,11 @@ Two deliberate differences from the reference:
   ``NotImplementedError``.
 * A window longer than the RA axis (``2 int(ha_side) + 1 > nra``) raises ``ValueError``; the reference wraps indices once
   in each direction only and then indexes from the wrong end.
+
+The ring-map half of the reference's module is here too: :class:`RingMapBeamForm` extracts the pixel containing each
+source from a ``RingMap`` (``dmm_ringmap_extract``) and :class:`RingMapStack2D` stacks the patches around the sources into a
+``Stack3D`` (``dmm_ringmap_stack3d``, both ``csrc/sourcestack.hip``).  The CIRS rule holds for them whenever the ring map
+carries an ``lsd`` attribute; a ring map without one takes the catalogue's coordinates as they are.
 """
 
 from __future__ import annotations
@@ -30,11 +35,13 @@ import scipy.constants
 import scipy.interpolate
 import torch
 
+from .. import _lib
 from ..core import containers, io
 from ..core.task import ContainerTask
-from ..device import Context
+from ..device import Context, ptr
 from ..util import _fast_tools
 from ..util.tools import baseline_vector, calculate_redundancy, polarization_map
+from .sidereal import _search_nearest
 from .transform import _dev_dataset
 
 NU21 = 1420.40575177  # MHz
@@ -423,3 +430,201 @@ class BeamFormExternal(BeamFormExternalMixin, BeamForm):
 
 class BeamFormExternalCat(BeamFormExternalMixin, BeamFormCat):
     """:class:`BeamFormCat` with an external beam model: ``setup(beam, manager, data)``."""
+
+
+class RingMapBeamForm(ContainerTask):
+    """Beamform by extracting the pixel containing each source from a ``RingMap`` (``beamform.py:915-1094``).
+
+    Much faster than :class:`BeamForm`, at the mercy of what was done to produce the ring map.  A ring map without an
+    ``lsd`` attribute is taken to be in the epoch of the catalogue, whose coordinates are used as they are; with ``lsd``
+    the catalogue must be marked ``attrs["coordinates"] == "CIRS"`` (see the module's docstring).
+
+    The host finds the pixels in float64 exactly as the reference (``_source_ind``); ``dmm_ringmap_extract`` copies, so
+    ``beam`` and ``weight`` (device resident) are bit-equal to the reference's.
+    """
+
+    def setup(self, telescope, ringmap):
+        """``telescope``: anything ``io.get_telescope`` understands; ``ringmap``: the ``RingMap`` to extract from."""
+        self.telescope = io.get_telescope(telescope)
+        self.ringmap = ringmap
+
+    def _map_tensors(self, ctx):
+        """``(map [pol, freq, ra, el], weight source, rms?)`` on the device; the first beam of the map only."""
+        rmm = _dev_dataset(self.ringmap.map, ctx, np.float64)[0].contiguous()
+        if "weight" in self.ringmap.datasets:
+            return rmm, _dev_dataset(self.ringmap.weight, ctx, np.float64).contiguous(), False
+        return rmm, _dev_dataset(self.ringmap.rms, ctx, np.float64).contiguous(), True
+
+    def process(self, catalog):
+        """``catalog``: a ``SourceCatalog``.  Returns the ``FormedBeam`` of the sources inside the map."""
+        ringmap = self.ringmap
+        src_ra, src_dec = self._process_catalog(catalog)
+        ra_ind, el_ind, src_ind = self._source_ind(src_ra, src_dec)
+        nsrc = int(src_ind.size)
+
+        formed_beam = containers.FormedBeam(object_id=catalog.index_map["object_id"][src_ind], axes_from=ringmap, attrs_from=catalog, distributed=True, allocate=False)
+        formed_beam.datasets["position"] = containers.Dataset(host=np.array(catalog["position"][:][src_ind]), attrs={"axis": ["object_id"]})
+        if "redshift" in catalog:
+            formed_beam.add_dataset("redshift")
+            formed_beam["redshift"][:] = catalog["redshift"][:][src_ind]
+
+        npol, nfreq = len(ringmap.index_map["pol"]), len(ringmap.index_map["freq"])
+        nra, nel = len(ringmap.index_map["ra"]), len(ringmap.index_map["el"])
+        ctx = Context.get()
+        fbb, fbw = ctx.empty((nsrc, npol, nfreq), np.float64), ctx.empty((nsrc, npol, nfreq), np.float64)
+        if nsrc:
+            rmm, rmw, rms = self._map_tensors(ctx)
+            order = np.argsort(ra_ind.astype(np.int64) * nel + el_ind, kind="stable").astype(np.int32)
+            ri_d, ei_d, or_d = (ctx.to_device(np.ascontiguousarray(x, dtype=np.int32)) for x in (ra_ind, el_ind, order))
+            _lib.check(_lib.lib.dmm_ringmap_extract(ctx.handle, npol, nfreq, nra, nel, ptr(rmm), ptr(rmw), int(rms), nsrc, ptr(ri_d), ptr(ei_d), ptr(or_d), ptr(fbb), ptr(fbw)))
+        formed_beam.attach("beam", fbb)
+        formed_beam.attach("weight", fbw)
+        return formed_beam
+
+    def _process_catalog(self, catalog):
+        """The catalogue's coordinates in the epoch of the map (``beamform.py:1000-1028``)."""
+        if "position" not in catalog:
+            raise ValueError("Input is missing a position table.")
+        position = catalog["position"]
+        if "lsd" not in self.ringmap.attrs:
+            self.log.info("Input map has no epoch set, assuming that it matches the catalog.")
+        elif catalog.attrs.get("coordinates") != "CIRS":
+            lsd = self.ringmap.attrs["lsd"][0] if isinstance(self.ringmap.attrs["lsd"], np.ndarray) else self.ringmap.attrs["lsd"]
+            icrs_to_cirs(position["ra"], position["dec"], self.telescope.lsd_to_unix(lsd))  # (raises: see the module's docstring)
+        return np.array(position["ra"], dtype=np.float64), np.array(position["dec"], dtype=np.float64)
+
+    def _source_ind(self, src_ra, src_dec):
+        """Indices ``(ra_ind, el_ind, src_ind)`` of the pixels nearest to the sources that fall inside the map
+        (``beamform.py:1030-1094``), in float64 NumPy."""
+        src_el = np.sin(np.radians(src_dec - self.telescope.latitude))
+        ra = np.asarray(self.ringmap.index_map["ra"], dtype=np.float64)
+        el = np.asarray(self.ringmap.index_map["el"], dtype=np.float64)
+        delta_ra = np.median(np.abs(np.diff(ra)))
+        delta_el = np.median(np.abs(np.diff(el)))
+        # (sources just below 360 deg may be closest to the first sample)
+        ra_ind = _search_nearest(np.append(ra, 360.0 + ra[0]), src_ra) % ra.size
+        ra_sep = src_ra - ra[ra_ind]
+        ra_sep = (ra_sep + 180.0) % 360.0 - 180.0
+        el_ind = _search_nearest(el, src_el)
+        el_sep = src_el - el[el_ind]
+        src_flag = (np.abs(ra_sep) > (0.5 * delta_ra)) | (np.abs(el_sep) > (0.5 * delta_el))
+        if np.any(src_flag):
+            self.log.info(f"There are {np.sum(src_flag)} (of {src_flag.size}) sources outside of the RA and Declination range covered by the map.")
+        src_ind = np.flatnonzero(~src_flag)
+        return ra_ind[src_ind], el_ind[src_ind], src_ind
+
+
+class RingMapStack2D(RingMapBeamForm):
+    """Stack ring maps on sources directly (``beamform.py:1097-1302``): the patch of ``(2 num_ra + 1) x (2 num_dec + 1)``
+    pixels around every source, binned in frequency offset from the source's line, into a ``Stack3D``.
+
+    Attributes
+    ----------
+    num_ra, num_dec : int
+        The number of RA and DEC pixels to stack either side of the source.  Default 10.
+    num_freq : int
+        Number of final frequency channels either side of the source redshift to stack.  Default 256.
+    freq_width : float
+        Length of the frequency interval either side of the source in MHz; zero: the ring map's own resolution.
+    weight : {"patch", "dec", "input"}
+        ``"input"``: pixel by pixel as the map's weights (default); ``"patch"``: the inverse variance of the extracted
+        patch; ``"dec"``: the inverse variance over RA of each declination strip.
+    workspace_mib : int
+        Device memory the partial sums of a pass may take.  The result does not depend on it.  Default 1024.
+
+    The frequency axis of the map must be strictly monotonic.  A patch longer than the RA axis, or ``2 num_dec + 1 >
+    nel``, raises ``ValueError`` (the reference indexes from the wrong end there).
+    """
+
+    _config_names = ("num_ra", "num_dec", "num_freq", "freq_width", "weight", "workspace_mib")
+    num_ra = 10
+    num_dec = 10
+    num_freq = 256
+    freq_width = 0.0
+    weight = "input"
+    workspace_mib = 1024
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.weight not in ("patch", "dec", "input"):
+            raise ValueError(f"Invalid weight parameter: {self.weight}")
+
+    def process(self, catalog):
+        """``catalog``: a ``SpectroscopicCatalog``.  Returns the ``Stack3D``."""
+        from .sourcestack import _monotonic, stack_partials
+
+        ringmap = self.ringmap
+        src_ra, src_dec = self._process_catalog(catalog)
+        if "redshift" not in catalog:
+            raise ValueError("Input is missing a required redshift table.")
+        src_z = np.asarray(catalog["redshift"]["z"], dtype=np.float64)
+        ra_ind, el_ind, src_ind = self._source_ind(src_ra, src_dec)
+        src_z = src_z[src_ind]
+
+        freq = np.asarray(ringmap.freq, dtype=np.float64)
+        ra = np.asarray(ringmap.index_map["ra"], dtype=np.float64)
+        el = np.asarray(ringmap.index_map["el"], dtype=np.float64)
+        dra = np.median(np.abs(np.diff(ra)))
+        dell = np.median(np.abs(np.diff(el)))
+        nra, nel, nfreq, npol = ra.size, el.size, freq.size, len(ringmap.index_map["pol"])
+        if 2 * self.num_ra + 1 > nra or self.num_ra < 0:
+            raise ValueError(f"a patch of {2 * self.num_ra + 1} pixels is longer than the RA axis ({nra})")
+        if 2 * self.num_dec + 1 > nel or self.num_dec < 0:
+            raise ValueError(f"a patch of {2 * self.num_dec + 1} pixels is longer than the el axis ({nel})")
+        fdir = _monotonic(freq)
+        if fdir == 0:
+            raise ValueError("the frequency axis is not strictly monotonic")
+        if nfreq > _lib.DMM_STACK_MAX_FREQ:
+            raise ValueError(f"{nfreq} channels: at most {_lib.DMM_STACK_MAX_FREQ}")
+
+        # does the RA axis wrap around from 360 to 0 deg?
+        tol = dra / 100.0
+        ra_wraps = bool(np.isclose(ra[-1] + dra, 360.0, atol=tol) and np.isclose(ra[0], 0.0, atol=tol))
+
+        nbins = 2 * self.num_freq + 1
+        if self.freq_width > 0:
+            bin_edges = np.linspace(-self.freq_width, self.freq_width, nbins + 1, endpoint=True)
+        else:
+            df = np.median(np.abs(np.diff(freq)))
+            bin_edges = (np.arange(-self.num_freq, self.num_freq + 2) - 0.5) * df
+        if _monotonic(bin_edges) != 1:
+            raise ValueError("bins must be monotonically increasing")
+
+        # sources outside the band are dropped
+        source_freq = NU21 / (1 + src_z)
+        keep = ~((source_freq > freq.max()) | (source_freq < freq.min()))
+        ra_ind, el_ind, source_freq = ra_ind[keep], el_ind[keep], source_freq[keep]
+        nsrc = int(source_freq.size)
+
+        ctx = Context.get()
+        nrp, ndp = 2 * self.num_ra + 1, 2 * self.num_dec + 1
+        n = npol * nbins * nrp * ndp
+        partial, chunks, running = stack_partials(ctx, n, nsrc, self.workspace_mib)
+        out_s, out_w = ctx.empty((npol, nrp, ndp, nbins), np.float64), ctx.empty((npol, nrp, ndp, nbins), np.float64)
+        rmm = rmw = wdec = ri_d = ei_d = sf_d = None
+        rms = False
+        mode = {"input": _lib.DMM_STACK3D_INPUT, "dec": _lib.DMM_STACK3D_DEC, "patch": _lib.DMM_STACK3D_PATCH}[self.weight]
+        if nsrc or self.weight == "dec":
+            rmm, rmw, rms = self._map_tensors(ctx)
+        if self.weight == "dec":
+            rmvar = rmm.var(dim=2, unbiased=False)
+            wdec = torch.where(rmvar < 3e-7, torch.zeros_like(rmvar), rmvar)
+            wdec = torch.where(wdec == 0, torch.zeros_like(wdec), 1.0 / torch.where(wdec == 0, torch.ones_like(wdec), wdec)).contiguous()
+        if nsrc:
+            ri_d, ei_d = (ctx.to_device(np.ascontiguousarray(x, dtype=np.int32)) for x in (ra_ind, el_ind))
+            sf_d = ctx.to_device(np.ascontiguousarray(source_freq))
+        freq_d, edges_d = ctx.to_device(freq), ctx.to_device(np.ascontiguousarray(bin_edges, dtype=np.float64))
+        _lib.check(_lib.lib.dmm_ringmap_stack3d(ctx.handle, npol, nfreq, nra, nel, ptr(rmm), ptr(rmw), int(rms), int(mode), ptr(wdec), nsrc, ptr(ri_d), ptr(ei_d), ptr(sf_d),
+                                                ptr(freq_d), int(fdir < 0), nbins, ptr(edges_d), int(self.num_ra), int(self.num_dec), int(ra_wraps), ptr(partial), chunks,
+                                                ptr(running), ptr(out_s), ptr(out_w)))
+
+        delta_f = np.zeros(nbins, dtype=[("centre", float), ("width", float)])
+        delta_f["centre"] = 0.5 * (bin_edges[1:] + bin_edges[:-1])
+        delta_f["width"] = bin_edges[1:] - bin_edges[:-1]
+        delta_ra = np.arange(-self.num_ra, self.num_ra + 1) * dra
+        delta_dec = np.degrees(np.arcsin(np.arange(-self.num_dec, self.num_dec + 1) * dell))
+        stack = containers.Stack3D(freq=delta_f, delta_ra=delta_ra, delta_dec=delta_dec, axes_from=ringmap, attrs_from=ringmap, allocate=False)
+        stack.attrs["tag"] = catalog.attrs["tag"]
+        stack.attach("stack", out_s)
+        stack.attach("weight", out_w)
+        return stack

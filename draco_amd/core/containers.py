@@ -946,6 +946,70 @@ class FormedBeamHA(FormedBeam):
         return self.datasets["object_ha"]
 
 
+class FrequencyStack(ContainerBase, _FreqMixin):
+    """The stack of formed beams over the sources of a catalogue: ``stack`` and ``weight [freq]`` float64, ``freq`` the
+    offset from the sources' line frequency (``containers.py:2610-2639``)."""
+
+    _axes = ("freq",)
+    _dataset_spec = {"stack": {"axes": ["freq"], "dtype": np.float64}, "weight": {"axes": ["freq"], "dtype": np.float64}}
+
+    @property
+    def stack(self):
+        return self.datasets["stack"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+
+class FrequencyStackByPol(FrequencyStack):
+    """A frequency stack split by polarisation: ``[pol, freq]`` (``containers.py:2642-2665``)."""
+
+    _axes = ("pol", "freq")
+    _dataset_spec = {"stack": {"axes": ["pol", "freq"], "dtype": np.float64}, "weight": {"axes": ["pol", "freq"], "dtype": np.float64}}
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+
+class MockFrequencyStack(FrequencyStack):
+    """Frequency stacks of many mock catalogues: ``[mock, freq]`` (``containers.py:2668-2689``)."""
+
+    _axes = ("mock", "freq")
+    _dataset_spec = {"stack": {"axes": ["mock", "freq"], "dtype": np.float64}, "weight": {"axes": ["mock", "freq"], "dtype": np.float64}}
+
+
+class MockFrequencyStackByPol(FrequencyStackByPol):
+    """Frequency stacks by polarisation of many mock catalogues: ``[mock, pol, freq]`` (``containers.py:2692-2713``)."""
+
+    _axes = ("mock", "pol", "freq")
+    _dataset_spec = {"stack": {"axes": ["mock", "pol", "freq"], "dtype": np.float64}, "weight": {"axes": ["mock", "pol", "freq"], "dtype": np.float64}}
+
+
+class Stack3D(ContainerBase, _FreqMixin):
+    """A 3-D stack of ring-map patches: ``stack`` and ``weight [pol, delta_ra, delta_dec, freq]`` float64
+    (``containers.py:2716-2742``)."""
+
+    _axes = ("pol", "delta_ra", "delta_dec", "freq")
+    _dataset_spec = {
+        "stack": {"axes": ["pol", "delta_ra", "delta_dec", "freq"], "dtype": np.float64},
+        "weight": {"axes": ["pol", "delta_ra", "delta_dec", "freq"], "dtype": np.float64},
+    }
+
+    @property
+    def stack(self):
+        return self.datasets["stack"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+
 class GridBeam(ContainerBase, _FreqMixin):
     """A beam on a rectangular grid: ``beam [freq, pol, input, theta, phi]`` complex64, ``weight`` float32 of the same
     shape, ``attrs["coords"]`` (``containers.py:883-954``; ``quality`` and ``gain`` are not carried)."""

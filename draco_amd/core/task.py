@@ -11,6 +11,10 @@ from __future__ import annotations
 import logging
 
 
+class PipelineStopIteration(Exception):
+    """Raised by a task's ``process`` when it has nothing more to produce (caput's ``PipelineStopIteration`` [3P])."""
+
+
 class ContainerTask:
     _config_names: tuple = ()
 

@@ -860,6 +860,42 @@ int dmm_ps3d_cross(dmm_ctx* ctx, const void* vis1, const void* vis2, int npol1, 
 int dmm_ps_cyl_bin(dmm_ctx* ctx, const void* spec, const void* sigma, const int16_t* binmap, int nplane, int nu, int nv, int nbins, void* out_spec, double* out_weight,
                    double* out_neff);
 
+/* Source stacking (draco/analysis/sourcestack.py:17-211, draco/analysis/beamform.py:915-1302), csrc/sourcestack.hip.
+ * float64 throughout, no floating-point atomics: sums run over chunks of DMM_STACK_SRC_CHUNK sources in catalogue
+ * order and the chunks' partial sums are added one after the other, so two runs give the same bits whatever
+ * partial_chunks is.  Everything is [dev].  Nothing here synchronises.
+ *
+ * dmm_ringmap_extract: beam [nsrc][npol][nfreq] = map [npol][nfreq][nra][nel] at (ra_ind[s], el_ind[s]); weight
+ * likewise from wsrc [npol][nfreq][nra][nel] (rms = 0) or inz(wsrc [npol][nfreq][nra])^2 (rms = 1).  order [nsrc]
+ * (may be NULL) is the order in which sources are visited (a permutation, sorted by pixel); a source whose indices are
+ * outside the map gets zeros.  nsrc = 0 launches nothing.
+ *
+ * dmm_source_stack: beam / weight [nsrc][npol][nfreq], freq [nfreq] strictly monotonic (freq_descending says which
+ * way), sfreq [nsrc] the sources' line frequencies, smask [nsrc] bytes (NULL: every source), bins [nstack + 1] the
+ * strictly monotonic bin edges (bins_ascending).  Channel f of source s is in bin np.digitize(freq[f] - sfreq[s], bins)
+ * - 1; with w_eff = weight, or (weight > 0) when uniform, stack [npol][nstack] = S inz(W), out_weight = W, S = sum w_eff
+ * beam, W = sum w_eff over sources and the channels of a bin.  partial holds partial_chunks x 2 npol nstack doubles,
+ * running 2 npol nstack.
+ *
+ * dmm_ringmap_stack3d: around the pixel (ra_ind[s], el_ind[s]) of each source the patch of (2 num_ra + 1) x (2 num_dec
+ * + 1) pixels, clipped at both ends of el, and in ra wrapped (ra_wraps) or clipped; channel f of source s is in bin
+ * np.digitize(freq[f] - sfreq[s], edges) - 1 of edges [nbins + 1] ascending, the two overflow bins dropped.  The weight w
+ * of a pixel is the map's (mode DMM_STACK3D_INPUT; wsrc and rms as above, the rms spread over el), (w != 0) wdec [npol]
+ * [nfreq][nel] (DMM_STACK3D_DEC) or (w != 0) inz(population variance of the clipped patch) (DMM_STACK3D_PATCH).  stack
+ * [npol][2 num_ra + 1][2 num_dec + 1][nbins] = sum(map w) inz(sum w), out_weight = sum w.  partial holds partial_chunks x
+ * 2 n doubles and running 2 n, n = npol nbins (2 num_ra + 1)(2 num_dec + 1). */
+#define DMM_STACK_SRC_CHUNK 256
+#define DMM_STACK_MAX_FREQ 2048
+enum { DMM_STACK3D_INPUT = 0, DMM_STACK3D_DEC = 1, DMM_STACK3D_PATCH = 2 };
+int dmm_ringmap_extract(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, const double* map, const double* wsrc, int rms, int64_t nsrc, const int32_t* ra_ind,
+                        const int32_t* el_ind, const int32_t* order, double* beam, double* weight);
+int dmm_source_stack(dmm_ctx* ctx, int64_t nsrc, int npol, int nfreq, int nstack, const double* beam, const double* weight, const double* freq, int freq_descending,
+                     const double* sfreq, const uint8_t* smask, const double* bins, int bins_ascending, int uniform, double* partial, int64_t partial_chunks,
+                     double* running, double* stack, double* out_weight);
+int dmm_ringmap_stack3d(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, const double* map, const double* wsrc, int rms, int mode, const double* wdec, int64_t nsrc,
+                        const int32_t* ra_ind, const int32_t* el_ind, const double* sfreq, const double* freq, int freq_descending, int nbins, const double* edges,
+                        int num_ra, int num_dec, int ra_wraps, double* partial, int64_t partial_chunks, double* running, double* stack, double* out_weight);
+
 #ifdef __cplusplus
 }
 #endif
