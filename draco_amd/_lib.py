@@ -46,6 +46,7 @@ DMM_SENS_MAX_GROUP = 64
 DMM_PS_MAX_BINS = 4096
 DMM_STACK_SRC_CHUNK, DMM_STACK_MAX_FREQ = 256, 2048
 DMM_STACK3D_INPUT, DMM_STACK3D_DEC, DMM_STACK3D_PATCH = 0, 1, 2
+DMM_WD_MAX_FREQ = 1024
 
 
 class DmmError(RuntimeError):
@@ -195,6 +196,8 @@ _SIGS = {
     "dmm_ringmap_extract": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmm_source_stack": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "dmm_ringmap_stack3d": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp]),
+    "dmm_wienerdelay_build": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 9 + [_i, _i64, C.POINTER(_i64)]),
+    "dmm_wienerdelay_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

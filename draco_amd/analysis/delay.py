@@ -23,7 +23,8 @@ The transform needs the whole band in one process: frequency sharding does not a
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``use_average_weights=False`` (the reference's
 Wiener function cannot take per-sample weights either) and ``scale_freq=True``; not provided: the Gibbs, NRML and
-cross-spectrum estimators, ``DelayFilter`` / ``DelayFilterBase`` and ``DelayTransformOperator``.
+cross-spectrum estimators and ``DelayFilter`` / ``DelayFilterBase``.  (The ``DelayTransformOperator`` container and the
+Wiener delay transform of a filtered ring map that fills it are in ``draco_amd.analysis.powerspec``.)
 """
 
 from __future__ import annotations

@@ -3,6 +3,7 @@
 Drop-in for the part of ``draco/analysis/powerspec.py`` that turns the delay transform of a ring map into power spectra:
 
 * :class:`TransformJyPerBeamToKelvin`                                   ``powerspec.py:25-115``
+* :class:`ConstructWienerDelayTransform`, :class:`ApplyWienerDelayTransform`   ``powerspec.py:118-458``
 * :class:`SpatialTransformDelayMap`                                     ``powerspec.py:539-705``
 * :class:`CrossPowerSpectrum3D`, :class:`AutoPowerSpectrum3D`           ``powerspec.py:708-834``
 * :class:`CylindricalPowerSpectrum2D`                                   ``powerspec.py:837-1017``
@@ -22,12 +23,21 @@ One cosmology is used throughout -- that of :func:`get_cosmo`, or of the contain
 cosmology is :class:`draco_amd.util.cosmology.Cosmology` (cora [3P] is not available; its defaults are not checked
 against cora's), the constants below are caput's [3P] values.
 
-Not provided: ``ConstructWienerDelayTransform`` / ``ApplyWienerDelayTransform``, ``ReduceExcessScatter``,
-``ScaleDelayTransform`` and ``SphericalPowerSpectrum3Dto1D``.
+The Wiener delay transform of a filtered ring map (``csrc/wienerdelay.hip``) builds, per pixel, the operator that takes
+the map from frequency to delay given the masked channels, the foreground filter already applied and the noise
+covariance between frequencies (``dmm_wienerdelay_build``), and applies it with propagated weights
+(``dmm_wienerdelay_apply``); the operator, the spectrum and its weight stay on the device.  The ring map's ``filter``
+and ``freq_cov`` datasets are real: complex filters (off-centre stop bands) raise ``NotImplementedError`` as in
+``dayenu.py``.  The tasks that put these two datasets on a ring map (``DayenuDelayFilterHybridVis(save_filter,
+calculate_cov)``, ``RADependentWeights``) are not provided yet, nor is a host-resident operator or a distribution of
+the elevations over processes: an operator that does not fit the device is built from ``el`` slices of the map.
+
+Not provided: ``ReduceExcessScatter``, ``ScaleDelayTransform`` and ``SphericalPowerSpectrum3Dto1D``.
 """
 
 from __future__ import annotations
 
+import ctypes
 import types
 from functools import cache
 
@@ -321,6 +331,184 @@ class TransformJyPerBeamToKelvin(ContainerTask):
         return out
 
 
+_LOS_WINDOWS = ("uniform", "hann", "hanning", "hamming", "blackman", "nuttall", "blackman_nuttall", "blackman_harris", "tukey-0.5", "None")
+
+
+def _free_device_bytes(ctx):
+    """Device memory a new tensor can take: what the driver reports free and what torch's allocator holds unused."""
+    import torch
+
+    free, _ = torch.cuda.mem_get_info(ctx.device)
+    return int(free) + int(torch.cuda.memory_reserved(ctx.device)) - int(torch.cuda.memory_allocated(ctx.device))
+
+
+class ConstructWienerDelayTransform(ContainerTask):
+    """Construct the Wiener filter that takes a filtered ring map from frequency to delay (``powerspec.py:118-369``).
+
+    Per pixel, with ``K`` the foreground filter and ``C`` the noise covariance of its RA, ``w`` the weights, ``b`` the
+    root of the dirty beam power, ``F`` the Fourier matrix from delay to frequency and ``S`` the prior:
+    ``D = diag(S) F^H H^T (H (F S F^H o b b^T) H^T + C o r r^T)^-1 window``, ``H = diag(M) K``, ``M`` the channels
+    inside the window with a weight, ``r = sqrt(inv0(w diag C))`` inside the window; the inverse is that of the block
+    of the channels of ``M``.  ``tau``, ``F``, ``S``, ``F S F^H`` and the window are formed once on the host as the
+    reference forms them; everything per pixel runs on the device in float64, slab by slab, and the output's ``filter``
+    (complex64) stays there.
+
+    prior_amp : float
+        Amplitude of the signal prior in delay space.  Default 2.8e-5.
+    prior_scale : float
+        Inverse coherence scale in MHz of the exponential decay of the prior with delay; 0: constant.  Default 0.
+    window : str
+        Apodisation along frequency, a window of ``tools.window_generalised``.  Default 'uniform'.
+    window_lower_freq, window_upper_freq : float, optional
+        The band in MHz the window spans (default: that of the data); channels outside weigh zero.
+    workspace_mib : int
+        Library scratch the pixels of one slab may take.  Default 1024.  The result does not depend on it.
+
+    ``1 <= nfreq <= 1024``.  A pixel without a valid channel gets a zero operator; one whose covariance is not positive
+    definite raises ``numpy.linalg.LinAlgError``, as the reference's ``cho_factor`` does.  An operator larger than the
+    free device memory raises ``ValueError`` before anything is launched: build it from ``el`` slices of the map.
+    """
+
+    _config_names = ("prior_amp", "prior_scale", "window", "window_lower_freq", "window_upper_freq", "workspace_mib")
+    prior_amp = 2.8e-5
+    prior_scale = 0.0
+    window = "uniform"
+    window_lower_freq = None
+    window_upper_freq = None
+    workspace_mib = 1024
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.window not in _LOS_WINDOWS:
+            raise ValueError(f"window must be one of {_LOS_WINDOWS}, not {self.window!r}")
+        for k in ("window_lower_freq", "window_upper_freq"):
+            if getattr(self, k) is not None:
+                setattr(self, k, float(getattr(self, k)))
+        if self.workspace_mib < 1:
+            raise ValueError(f"workspace_mib must be at least 1, not {self.workspace_mib}")
+
+    def _get_prior(self, delay):
+        """``prior_amp exp(-2 pi prior_scale |delay|)``, delay in micro-seconds."""
+        return self.prior_amp * np.exp(-2.0 * np.pi * self.prior_scale * np.abs(delay))
+
+    def _get_window(self, freq):
+        """The window at the frequencies ``freq`` (MHz)."""
+        frng = np.percentile(freq, [0, 100])
+        if self.window_lower_freq is not None:
+            frng[0] = self.window_lower_freq
+        if self.window_upper_freq is not None:
+            frng[1] = self.window_upper_freq
+        self.log.info(f"Applying a {self.window} window spanning {frng[0]:0.2f} - {frng[1]:0.2f} MHz.")
+        x = (freq - frng[0]) / (frng[1] - frng[0])
+        return _window(x, self.window)
+
+    def _constants(self, freq):
+        """``(tau, F [freq, delay], Sdiag, F S F^H, window)`` as the reference forms them."""
+        dfreq = np.median(np.abs(np.diff(freq)))
+        window = self._get_window(freq)
+        win_mask = window > 0
+        ntau = np.sum(win_mask, dtype=int)
+        tau = np.fft.fftshift(np.fft.fftfreq(ntau, d=dfreq))
+        tau = tau[tau >= 0.0]
+        F = np.exp(2.0j * np.pi * np.outer(freq, tau)) / np.sqrt(ntau)
+        FT = F.T.conj()
+        Sdiag = self._get_prior(tau)
+        FSFT = (F * Sdiag[np.newaxis, :]) @ FT
+        return tau, F, Sdiag, FSFT, window
+
+    def _build(self, data, dtype=np.complex64):
+        """``(tau, operator)``: the device tensor ``[pol, ra, el, delay, freq]`` of ``dtype`` (complex64 or complex128:
+        one computation, cast at the store)."""
+        for name in ("complex_filter", "complex_freq_cov"):
+            if name in data.datasets:
+                raise NotImplementedError(f"{type(self).__name__}: the ring map carries {name!r}; complex filters are not supported")
+        npol, nfreq, nra, nel = (int(n) for n in data.weight.shape)
+        if not 1 <= nfreq <= _lib.DMM_WD_MAX_FREQ:
+            raise ValueError(f"{type(self).__name__}: {nfreq} frequencies; the transform takes 1 to {_lib.DMM_WD_MAX_FREQ}")
+        freq = np.asarray(data.freq, dtype=np.float64)
+        tau, F, Sdiag, FSFT, window = self._constants(freq)
+        ndelay = int(tau.size)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            raise ValueError(f"{type(self).__name__}: the operator is complex64 or complex128, not {dtype}")
+        ctx = Context.get()
+        size = npol * nra * nel * ndelay * nfreq * dtype.itemsize
+        free = _free_device_bytes(ctx)
+        if size > free:
+            raise ValueError(f"{type(self).__name__}: the operator [{npol}, {nra}, {nel}, {ndelay}, {nfreq}] takes {size / 2**30:.2f} GiB, the device has {free / 2**30:.2f} GiB free: "
+                             "pass an el slice of the ring map (nothing couples elevations)")
+        prior_d = ctx.to_device(np.ascontiguousarray(np.hstack([FSFT.real, FSFT.imag]), dtype=np.float64))
+        four_d = ctx.to_device(np.ascontiguousarray(np.stack([F.real, F.imag]), dtype=np.float64))
+        s_d = ctx.to_device(np.ascontiguousarray(Sdiag, dtype=np.float64))
+        win_d = ctx.to_device(np.ascontiguousarray(window, dtype=np.float64))
+        K = _dev_dataset(data.filter, ctx, np.float64).contiguous()
+        Cv = _dev_dataset(data.freq_cov, ctx, np.float64).contiguous()
+        w = _dev_dataset(data.weight, ctx, np.float64).contiguous()
+        beam = _dev_dataset(data.dirty_beam_power, ctx, np.float64).contiguous()[0]
+        for name, t, shape in (("filter", K, (npol, nfreq, nfreq, nra)), ("freq_cov", Cv, (npol, nfreq, nfreq, nra)), ("dirty_beam_power", beam, (npol, nfreq, nel))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{type(self).__name__}: {name} is {tuple(t.shape)}, the weights need {shape}")
+        out = ctx.empty((npol, nra, nel, ndelay, nfreq), dtype)
+        bad = ctypes.c_int64(-1)
+        _lib.check(_lib.lib.dmm_wienerdelay_build(ctx.handle, npol, nfreq, nra, nel, ndelay, ptr(K), ptr(Cv), ptr(w), ptr(beam), ptr(prior_d), ptr(four_d), ptr(s_d), ptr(win_d), ptr(out),
+                                                  _lib.DMM_C64 if dtype == np.dtype(np.complex64) else _lib.DMM_C128, int(self.workspace_mib), ctypes.byref(bad)))
+        ctx.uses(K, Cv, w, beam, prior_d, four_d, s_d, win_d)
+        if bad.value >= 0:
+            pp, rr, ee = np.unravel_index(bad.value, (npol, nra, nel))
+            raise np.linalg.LinAlgError(f"{type(self).__name__}: the covariance of pixel (pol, ra, el) = ({pp}, {rr}, {ee}) is not positive definite")
+        return tau, out
+
+    def process(self, data):
+        data.redistribute("el")
+        tau, op = self._build(data, np.complex64)
+        out = containers.DelayTransformOperator(delay=tau, axes_from=data, attrs_from=data, allocate=False)
+        out.redistribute("el")
+        for attr in ["window", "window_lower_freq", "window_upper_freq"]:
+            out.attrs[attr] = getattr(self, attr)
+        out.attach("filter", op)
+        return out
+
+
+class ApplyWienerDelayTransform(ContainerTask):
+    """Apply the operator of :class:`ConstructWienerDelayTransform` to a ring map (``powerspec.py:372-458``): per pixel
+    ``spectrum = D map`` (complex128) and ``weight = inv0(|D|^2 inv0(w))`` (float32), into a ``DelayTransform`` with
+    ``baseline = (pol, el)`` and ``sample = ra`` whose datasets stay on the device.  The operator is read once."""
+
+    def process(self, data, operator):
+        data.redistribute("ra")
+        operator.redistribute("ra")
+        npol, nfreq, nra, nel = (int(n) for n in data.weight.shape)
+        delay = operator.index_map["delay"]
+        ndelay = int(len(delay))
+        out = containers.DelayTransform(baseline=npol * nel, sample=data.index_map["ra"], delay=delay, attrs_from=data, allocate=False)
+        out.add_dataset("weight", allocate=False)
+        out.redistribute("sample")
+        bl_axes = np.array(["pol", "el"])
+        for ax in bl_axes:
+            out.create_index_map(ax, data.index_map[ax])
+        out.attrs["baseline_axes"] = bl_axes
+        out.attrs["freq"] = data.freq
+        for attr in ["window", "window_lower_freq", "window_upper_freq"]:
+            out.attrs[attr.replace("window", "window_los")] = operator.attrs[attr]
+
+        ctx = Context.get()
+        op = operator.filter.device(ctx).contiguous()
+        if tuple(op.shape) != (npol, nra, nel, ndelay, nfreq):
+            raise ValueError(f"{type(self).__name__}: the operator is {tuple(op.shape)}, the map needs {(npol, nra, nel, ndelay, nfreq)}")
+        if operator.filter.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            raise ValueError(f"{type(self).__name__}: the operator is {operator.filter.dtype}, not complex64 or complex128")
+        m = _dev_dataset(data.map, ctx, np.float64).contiguous()[0]
+        w = _dev_dataset(data.weight, ctx, np.float64).contiguous()
+        spec = ctx.empty((npol * nel, nra, ndelay), np.complex128)
+        sweight = ctx.empty((npol * nel, nra, ndelay), np.float32)
+        _lib.check(_lib.lib.dmm_wienerdelay_apply(ctx.handle, npol, nfreq, nra, nel, ndelay, ptr(op), _lib.DMM_C64 if operator.filter.dtype == np.dtype(np.complex64) else _lib.DMM_C128,
+                                                  ptr(m), ptr(w), ptr(spec), ptr(sweight)))
+        ctx.uses(op, m, w)
+        out.attach("spectrum", spec)
+        out.attach("weight", sweight)
+        return out
+
+
 class SpatialTransformDelayMap(ContainerTask):
     """Transform a delay map from (RA, Dec) to the (u, v) domain (``powerspec.py:539-705``): per (pol, delay) plane the
     2-D FFT over (RA, el) of the tapered map, shifted and normalised by the number of pixels, into a
@@ -595,7 +783,9 @@ class SphericalPowerSpectrum2Dto1D(ContainerTask):
 
 
 __all__ = [
+    "ApplyWienerDelayTransform",
     "AutoPowerSpectrum3D",
+    "ConstructWienerDelayTransform",
     "CrossPowerSpectrum3D",
     "CylindricalPowerSpectrum2D",
     "SpatialTransformDelayMap",

@@ -569,9 +569,11 @@ class HybridVisMModes(MContainer, _FreqMixin, _VisMixin):
 
 class RingMap(ContainerBase, _FreqMixin):
     """Multi-frequency ring maps: ``map [beam, pol, freq, ra, el]``, ``weight [pol, freq, ra, el]`` float64
-    (``containers.py:1577-1653``); optional ``dirty_beam``, ``dirty_beam_power`` via :meth:`add_dataset`."""
+    (``containers.py:1577-1693``); optional ``dirty_beam``, ``dirty_beam_power``, ``rms`` and, from a foreground filter
+    that kept them, ``filter`` and ``freq_cov`` ``[pol, freq, freq_sum, ra]`` float64 via :meth:`add_dataset`; the
+    ``freq_sum`` axis is a copy of ``freq``.  The complex forms of the last two are not provided."""
 
-    _axes = ("beam", "pol", "freq", "ra", "el", "ew")
+    _axes = ("beam", "pol", "freq", "freq_sum", "ra", "el", "ew")
     _dataset_spec = {
         "map": {"axes": ["beam", "pol", "freq", "ra", "el"], "dtype": np.float64},
         "weight": {"axes": ["pol", "freq", "ra", "el"], "dtype": np.float64},
@@ -580,7 +582,10 @@ class RingMap(ContainerBase, _FreqMixin):
         "dirty_beam": {"axes": ["beam", "pol", "freq", "ra", "el"], "dtype": np.float64},
         "dirty_beam_power": {"axes": ["beam", "pol", "freq", "el"], "dtype": np.float64},
         "rms": {"axes": ["pol", "freq", "ra"], "dtype": np.float64},  # containers.py:1643-1650
+        "filter": {"axes": ["pol", "freq", "freq_sum", "ra"], "dtype": np.float64},  # containers.py:1654-1693
+        "freq_cov": {"axes": ["pol", "freq", "freq_sum", "ra"], "dtype": np.float64},
     }
+    _complex_datasets = ("complex_filter", "complex_freq_cov")
 
     def __init__(self, ra=None, **kwargs):
         if isinstance(ra, (int, np.integer)):
@@ -589,7 +594,12 @@ class RingMap(ContainerBase, _FreqMixin):
         super().__init__(ra=ra, **kwargs)
 
     def add_dataset(self, name, allocate=False):
+        if name in self._complex_datasets:
+            raise NotImplementedError(f"RingMap: the dataset {name!r} is not provided (complex filters are not supported)")
         self._dataset_spec[name] = self._optional_spec[name]
+        if "freq_sum" in self._optional_spec[name]["axes"] and "freq_sum" not in self.index_map:
+            self.index_map["freq_sum"] = self.index_map["freq"]  # (a copy of the frequency axis: the second index of a matrix)
+            self.index_attrs.setdefault("freq_sum", {})
         if allocate:
             self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=np.float64))
 
@@ -612,6 +622,22 @@ class RingMap(ContainerBase, _FreqMixin):
     @property
     def rms(self):
         return self.datasets["rms"]
+
+    @property
+    def filter(self):
+        return self.datasets["filter"]
+
+    @property
+    def freq_cov(self):
+        return self.datasets["freq_cov"]
+
+    @property
+    def complex_filter(self):
+        raise NotImplementedError("RingMap: complex filters are not supported")
+
+    @property
+    def complex_freq_cov(self):
+        raise NotImplementedError("RingMap: complex noise covariances are not supported")
 
 
 class SVDSpectrum(ContainerBase):
@@ -738,6 +764,18 @@ class DelayTransform(DelayContainer):
     @property
     def weight(self):
         return self.datasets["weight"]
+
+
+class DelayTransformOperator(DelayContainer):
+    """The operator of a Wiener delay transform: ``filter [pol, ra, el, delay, freq]`` complex64, per pixel the matrix
+    that takes the filtered map from frequency to delay (``containers.py:2185-2203``)."""
+
+    _axes = ("pol", "ra", "el", "delay", "freq")
+    _dataset_spec = {"filter": {"axes": ["pol", "ra", "el", "delay", "freq"], "dtype": np.complex64}}
+
+    @property
+    def filter(self):
+        return self.datasets["filter"]
 
 
 class CosmologyContainer(ContainerBase):

@@ -896,6 +896,31 @@ int dmm_ringmap_stack3d(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, con
                         const int32_t* ra_ind, const int32_t* el_ind, const double* sfreq, const double* freq, int freq_descending, int nbins, const double* edges,
                         int num_ra, int num_dec, int ra_wraps, double* partial, int64_t partial_chunks, double* running, double* stack, double* out_weight);
 
+/* Wiener delay transform of a filtered ring map (draco/analysis/powerspec.py:118-458), csrc/wienerdelay.hip.  float64
+ * arithmetic in a fixed order, no floating-point atomics: the results are the same bits whatever workspace_mib is.
+ * Everything is [dev] unless marked [host].  1 <= nfreq <= DMM_WD_MAX_FREQ, 1 <= ndelay <= nfreq; a count of zero pixels
+ * launches nothing.
+ *
+ * dmm_wienerdelay_build: filter, freq_cov [npol][nfreq][nfreq][nra], weight [npol][nfreq][nra][nel], beam_power [npol]
+ * [nfreq][nel] (beam 0 of dirty_beam_power), prior [nfreq][2 nfreq] = [Re | Im] of F S F^H, fourier [2][nfreq][ndelay]
+ * = Re, Im of F, sdiag [ndelay] = S, window [nfreq].  Per pixel, with K, C the [freq, freq] slices at this RA, w the
+ * weights, b = sqrt(beam_power), win_mask = window > 0:  M = win_mask and (w > 0), H = diag(M) K, r = sqrt(inv0(w diag C))
+ * win_mask, A = H (F S F^H o b b^T) H^T + C o r r^T, out [npol][nra][nel][ndelay][nfreq] = diag(S) F^H H^T A^-1 window, the
+ * inverse taken on the channels of M and zero elsewhere (only the upper triangle of A is used).  out_dtype DMM_C64 or
+ * DMM_C128: one computation, cast at the store.  A pixel without a valid channel gives zeros.  The pixels are worked on
+ * in slabs of about workspace_mib MiB (0: 1024) of library scratch; after every slab the stream is synchronised and the
+ * call ends at the first slab with a pixel whose A is not positive definite: *first_bad [host] = (pol nra + ra) nel + el
+ * of the lowest such pixel of that slab (-1: none), whose part of out, and every later slab's, is not meaningful.
+ *
+ * dmm_wienerdelay_apply: op [npol][nra][nel][ndelay][nfreq] (op_dtype DMM_C64, widened on load, or DMM_C128), map and
+ * weight [npol][nfreq][nra][nel] float64: spectrum [npol nel][nra][ndelay] complex128 = sum_f op[d][f] map[f], sweight
+ * (float32, same shape) = inv0(sum_f |op[d][f]|^2 inv0(weight[f])), in a fixed order.  Does not synchronise. */
+#define DMM_WD_MAX_FREQ 1024
+int dmm_wienerdelay_build(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, int ndelay, const double* filter, const double* freq_cov, const double* weight, const double* beam_power,
+                          const double* prior, const double* fourier, const double* sdiag, const double* window, void* out, int out_dtype, int64_t workspace_mib, int64_t* first_bad);
+int dmm_wienerdelay_apply(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, int ndelay, const void* op, int op_dtype, const double* map, const double* weight, void* spectrum,
+                          float* sweight);
+
 #ifdef __cplusplus
 }
 #endif
