@@ -97,9 +97,7 @@ def _tile_sizes(provider, ms, b_layout):
 
 def _two_stage_max_order(ctx):
     """The largest matrix order the library's two-stage ML reduction takes (a property of the build)."""
-    v = C.c_int64()
-    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, b"ml_two_stage_max_order", C.byref(v)))
-    return int(v.value)
+    return ctx.counter("ml_two_stage_max_order")
 
 
 def release_pools():
@@ -485,15 +483,9 @@ class SolveEngine:
         ``dmm_dirty_run``)."""
         PA = C.c_void_p * len(alms)
         pv, pw, pa = PA(*[ptr(x) for x in mvis_l]), PA(*[ptr(x) for x in mweight_l]), PA(*[ptr(x) for x in alms])
-        nofill = self._alm_internal
-        if nofill:
-            _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, b"dirty_nofill", 1))
-        try:
-            with self._timed(slab):
-                _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, len(alms)))
-        finally:
-            if nofill:
-                _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, b"dirty_nofill", 0))
+        nofill = self.ctx.options(dirty_nofill=1) if self._alm_internal else contextlib.nullcontext()
+        with nofill, self._timed(slab):
+            _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), pv, pw, pa, len(alms)))
 
     def _run_wiener(self, slab, mvis_l, mweight_l, alms, params):
         """One slab's Wiener solves, day after day."""
@@ -550,7 +542,7 @@ class SolveEngine:
         mib = min(int(cap_mib), int(free * 0.5) >> 20)
         self._ws_offer[option] = mib
         # (0 = the library's own default: an offer that fell below 1 GiB must not leave an earlier, larger one standing)
-        _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, option, mib if mib >= 1024 else 0))
+        self.ctx.set_option(option, mib if mib >= 1024 else 0)
 
     def project(self, alm_d, freq_ind, mmax):
         """``vis [mmax+1, 2, nfreq, npairs] = B_m[f] a_m[f]`` (``stream.py:109-112``)."""

@@ -16,7 +16,6 @@ never transposed to m and back (``mapmaker.py:62-67,99``): every stage is per-fr
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import numpy as np
 import torch
@@ -48,13 +47,8 @@ def _alm2map_neighbourly(c, alm, nfreq, lmax, mmax, nside, maps):
     if pinned is not None:  # (whatever `sht_variant` the caller has pinned on the context stays as it is)
         _lib.check(lib.dmm_alm2map(c.handle, ptr(alm), nfreq, 4, lmax, mmax, nside, ptr(maps)))
         return
-    before = C.c_int64()  # the option's value as the caller left it: restored, not reset
-    _lib.check(lib.dmm_ctx_get_counter(c.handle, b"opt_sht_synth_form", C.byref(before)))
-    _lib.check(lib.dmm_ctx_set_option(c.handle, b"sht_synth_form", 1))
-    try:
+    with c.options(sht_synth_form=1):  # (the caller's own value comes back afterwards: restored, not reset)
         _lib.check(lib.dmm_alm2map(c.handle, ptr(alm), nfreq, 4, lmax, mmax, nside, ptr(maps)))
-    finally:
-        _lib.check(lib.dmm_ctx_set_option(c.handle, b"sht_synth_form", int(before.value)))
 
 
 def _bound_run_ahead(ctx, depth):

@@ -67,6 +67,23 @@ static void free_tables(std::map<int, dmm_fft_tables<T2>>& m) {
   m.clear();
 }
 
+// One row per option: its name and the field it holds, an int or a workspace size in MiB (negative: 0); each reads back as the counter "opt_<name>".
+struct dmm_option { const char* name; int dmm_ctx::*field; int64_t dmm_ctx::*mib; };
+#define OPT(f) &dmm_ctx::opt_##f
+static const dmm_option kOptions[] = {
+    {"dirty_variant", OPT(dirty_variant)}, {"grid_mult", OPT(grid_mult)}, {"dirty_static", OPT(dirty_static)}, {"dirty_nofill", OPT(dirty_nofill)},
+    {"dirty_prio", OPT(dirty_prio)}, {"project_variant", OPT(project_variant)}, {"project_grid_mult", OPT(project_grid_mult)},
+    {"sht_variant", OPT(sht_variant)}, {"sht_synth_form", OPT(sht_synth_form)}, {"ringmap_variant", OPT(ringmap_variant)}, {"gram_stage", OPT(gram_stage)},
+    {"ml_shortcut", OPT(ml_shortcut)}, {"ml_eigen", OPT(ml_eigen)}, {"ml_null", OPT(ml_null)}, {"ml_reduce", OPT(ml_reduce)}, {"ml_rank_stop", OPT(ml_rank_stop)},
+    {"ml_chase_split", OPT(ml_chase_split)}, {"ml_inner_sweeps", OPT(ml_inner_sweeps)}, {"ml_outer_sweeps", OPT(ml_outer_sweeps)}, {"wiener_overlap", OPT(wiener_overlap)},
+    {"ml_workspace_mib", nullptr, OPT(ml_ws_mib)}, {"regrid_workspace_mib", nullptr, OPT(regrid_ws_mib)}, {"wiener_workspace_mib", nullptr, OPT(wiener_ws_mib)},
+    {"profile", OPT(profile)}};  // (setting it also collects the open spans and clears the sums; stored as 0 / 1)
+static const dmm_option* find_option(const char* name) {  // (touches no context: the lookup works with any handle)
+  for (const dmm_option& o : kOptions)
+    if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+
 extern "C" {
 
 int dmm_version(void) { return DMM_VERSION; }
@@ -120,35 +137,15 @@ int dmm_ctx_set_stream(dmm_ctx* c, void* s) {
 
 int dmm_ctx_set_option(dmm_ctx* c, const char* name, int64_t value) {
   DMM_REQUIRE(c != nullptr && name != nullptr, "dmm_ctx_set_option: NULL argument");
-  if (!strcmp(name, "dirty_variant")) c->opt_dirty_variant = (int)value;
-  else if (!strcmp(name, "grid_mult")) c->opt_grid_mult = (int)value;
-  else if (!strcmp(name, "dirty_static")) c->opt_dirty_static = (int)value;
-  else if (!strcmp(name, "dirty_nofill")) c->opt_dirty_nofill = (int)value;
-  else if (!strcmp(name, "project_grid_mult")) c->opt_project_grid_mult = (int)value;
-  else if (!strcmp(name, "project_variant")) c->opt_project_variant = (int)value;
-  else if (!strcmp(name, "ml_inner_sweeps")) c->opt_ml_inner_sweeps = (int)value;
-  else if (!strcmp(name, "ml_outer_sweeps")) c->opt_ml_outer_sweeps = (int)value;
-  else if (!strcmp(name, "sht_variant")) c->opt_sht_variant = (int)value;
-  else if (!strcmp(name, "sht_synth_form")) c->opt_sht_synth_form = (int)value;
-  else if (!strcmp(name, "ml_shortcut")) c->opt_ml_shortcut = (int)value;
-  else if (!strcmp(name, "ml_null")) c->opt_ml_null = (int)value;
-  else if (!strcmp(name, "ml_rank_stop")) c->opt_ml_rank_stop = (int)value;
-  else if (!strcmp(name, "ml_chase_split")) c->opt_ml_chase_split = (int)value;
-  else if (!strcmp(name, "dirty_prio")) c->opt_dirty_prio = (int)value;
-  else if (!strcmp(name, "ml_eigen")) c->opt_ml_eigen = (int)value;
-  else if (!strcmp(name, "ringmap_variant")) c->opt_ringmap_variant = (int)value;
-  else if (!strcmp(name, "ml_reduce")) c->opt_ml_reduce = (int)value;
-  else if (!strcmp(name, "gram_stage")) c->opt_gram_stage = (int)value;
-  else if (!strcmp(name, "wiener_overlap")) c->opt_wiener_overlap = (int)value;
-  else if (!strcmp(name, "ml_workspace_mib")) c->opt_ml_ws_mib = value > 0 ? value : 0;
-  else if (!strcmp(name, "regrid_workspace_mib")) c->opt_regrid_ws_mib = value > 0 ? value : 0;
-  else if (!strcmp(name, "wiener_workspace_mib")) c->opt_wiener_ws_mib = value > 0 ? value : 0;
-  else if (!strcmp(name, "profile")) {  // (re)start the per-class kernel timing: sums cleared
+  const dmm_option* o = find_option(name);
+  if (!o) return dmm_set_error(DMM_E_ARG, "dmm_ctx_set_option: unknown option '%s'", name);
+  if (o->mib) c->*o->mib = value > 0 ? value : 0;
+  else if (o->field == &dmm_ctx::opt_profile) {  // (re)start the per-class kernel timing: sums cleared
     prof_collect(c);
     for (int k = 0; k < DMM_PROF_NSLOT; ++k) c->prof_us[k] = 0.0, c->prof_n[k] = 0;
     c->opt_profile = value != 0;
   }
-  else return dmm_set_error(DMM_E_ARG, "dmm_ctx_set_option: unknown option '%s'", name);
+  else c->*o->field = (int)value;
   return DMM_OK;
 }
 
@@ -173,8 +170,11 @@ int dmm_ctx_get_counter(dmm_ctx* c, const char* name, int64_t* value) {
     *value = 0;
 #endif
   }
-  else if (!strcmp(name, "opt_ml_eigen")) *value = c->opt_ml_eigen;  // (the option's current value: a run never changes it)
-  else if (!strcmp(name, "opt_sht_synth_form")) *value = c->opt_sht_synth_form;  // (the option's current value: callers that set it around a call restore it)
+  else if (!strncmp(name, "opt_", 4)) {  // an option's current value (no wait for profile spans)
+    const dmm_option* o = find_option(name + 4);
+    if (!o) return dmm_set_error(DMM_E_ARG, "dmm_ctx_get_counter: unknown option '%s'", name + 4);
+    *value = o->mib ? c->*o->mib : c->*o->field;
+  }
   else if (!strncmp(name, "prof_", 5)) {
     const size_t len = strlen(name);
     const bool want_n = len > 7 && !strcmp(name + len - 2, "_n");

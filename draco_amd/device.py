@@ -7,6 +7,7 @@ produces comes out of a kernel in ``libdraco_amd.so``.  Raises if there is no GP
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -24,6 +25,28 @@ _NP2TORCH = {
     np.dtype(np.uint16): torch.uint16,
     np.dtype(np.int16): torch.int16,
 }
+
+
+def _name(name) -> bytes:
+    return name if isinstance(name, bytes) else str(name).encode()
+
+
+@contextlib.contextmanager
+def scoped_options(get, set_, values):
+    """Set ``values`` (name -> value, names as str or bytes) through ``set_(name, value)`` for the length of the
+    block, then put back what ``get(name)`` returned before, last set first.  An option whose set fails is not
+    set again on the way out; the ones set before it are restored before the exception leaves."""
+    saved = []
+    try:
+        for name, value in values.items():
+            name = _name(name)
+            old = get(name)
+            set_(name, value)
+            saved.append((name, old))
+        yield
+    finally:
+        for name, old in reversed(saved):
+            set_(name, old)
 
 
 class Context:
@@ -140,6 +163,23 @@ class Context:
         ms = C.c_float()
         _lib.check(_lib.lib.dmm_timer_stop(self.handle, C.byref(ms)))
         return float(ms.value)
+
+    # ---- options and counters (names as str or bytes; an unknown name is a ValueError)
+    def set_option(self, name, value):
+        _lib.check(_lib.lib.dmm_ctx_set_option(self.handle, _name(name), int(value)))
+
+    def counter(self, name) -> int:
+        v = C.c_int64()
+        _lib.check(_lib.lib.dmm_ctx_get_counter(self.handle, _name(name), C.byref(v)))
+        return int(v.value)
+
+    def get_option(self, name) -> int:
+        return self.counter(b"opt_" + _name(name))
+
+    def options(self, **values):
+        """``with ctx.options(ml_eigen=1, profile=1): ...`` sets the options for the block and puts back the values
+        they had before it, whatever they were and however the block ends."""
+        return scoped_options(self.get_option, self.set_option, values)
 
     # ---- memory helpers
     def empty(self, shape, dtype) -> torch.Tensor:

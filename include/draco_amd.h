@@ -70,27 +70,38 @@ int dmm_ctx_destroy(dmm_ctx* ctx);
 /* run on the caller's HIP stream (hipStream_t passed as void*; NULL = default stream) */
 int dmm_ctx_set_stream(dmm_ctx* ctx, void* hip_stream);
 int dmm_ctx_sync(dmm_ctx* ctx);
-/* Options (name, integer value).  All but the first group change run time only, never results; details: INTEGRATION.md section C.
- *  accuracy-affecting: "ml_rank_stop" (0 on at 1e-13 of lambda_max [default], 1 off, v >= 11 on at 10^-v; positive
- *    semi-definite input only), "ml_inner_sweeps" / "ml_outer_sweeps" (iteration caps of the Jacobi fallback);
- *  ML path: "ml_shortcut" (0 certificate on, 2 always eigen-decompose, 3 telescope side only), "ml_eigen" (0 by batch
- *    size, 4 tridiagonal + QL, 1 blocked Jacobi, 2 full-matrix trailing updates, 3 QL made to fail: tests), "ml_null"
- *    (0 sampled null certificate, 1 off, 2 every tile), "ml_reduce" (0 two-stage with every other update deferred;
- *    3 its reading sweeps as one block per matrix; 2 none deferred; 1 one-stage), "ml_chase_split" (1: one chase launch with the full band image), "gram_stage"
- *    (1: LDS-DMA operand staging of the Gram kernel), "wiener_overlap" (0: one stream);
- *  sizes: "ml_workspace_mib" / "wiener_workspace_mib" (0 = 20 / 6 GiB), "regrid_workspace_mib" (0 = 12 GiB: a cfg-3 day in one launch), "grid_mult", "project_grid_mult";
- *  kernel forms: "dirty_variant", "dirty_static", "dirty_prio" (1: the Dirty kernel's waves raise their issue priority;
- *    it applies to dmm_dirty_run and to every group of dmm_dirty_run_multi -- the multi-day launches used to ignore it),
- *    "dirty_nofill" (1: dmm_dirty_run_multi does not write the structural zeros alm[l < m] -- they stay whatever the memory
- *    held; for an a_lm that only dmm_alm2map reads, which loads l >= m alone: same maps, half the a_lm bytes written; every
- *    other entry always writes them),
- *    "project_variant", "ringmap_variant" (1 three-kernel
- *    form, 2 eight elevations per block), "sht_variant" (bits: 2 direct ring sums, 3 vector-ALU Legendre kernels,
- *    6 first MFMA synthesis form, 7 pipelined synthesis with 4 frequencies per block), "sht_synth_form" (1: first MFMA form);
- *  "profile" (1: HIP-event timing of the dense solvers' kernel classes, sums cleared; 0 off).
- * Bits of "sht_variant" other than 2, 3, 6 and 7 selected A/B forms that are gone: setting them is accepted and ignored. */
+/* Options (name, integer value): option, default, meaning.  Every option reads back as "opt_<name>" through
+ * dmm_ctx_get_counter.  All but the accuracy-affecting ones change run time only, never results; details: INTEGRATION.md
+ * section C.
+ *   "dirty_variant"         0  kernel form of the Dirty solve
+ *   "grid_mult"             0  size: blocks per CU of the Dirty launch
+ *   "dirty_static"          0  1: static striding of the Dirty kernel's task list
+ *   "dirty_nofill"          0  1: dmm_dirty_run_multi does not write the structural zeros alm[l < m] (they stay whatever the
+ *                              memory held): for an a_lm that only dmm_alm2map reads, which loads l >= m alone; every other entry writes them
+ *   "dirty_prio"            0  1: the Dirty kernel's waves raise their issue priority (dmm_dirty_run and every group of dmm_dirty_run_multi)
+ *   "project_variant"       0  kernel form of dmm_project_run
+ *   "project_grid_mult"     0  size: blocks per CU of the projection launch
+ *   "sht_variant"           0  bits: 2 direct ring sums, 3 vector-ALU Legendre kernels, 6 first MFMA synthesis form, 7 pipelined
+ *                              synthesis with 4 frequencies per block; the other bits selected A/B forms that are gone: accepted and ignored
+ *   "sht_synth_form"        0  1: first MFMA synthesis form, whatever "sht_variant" says
+ *   "ringmap_variant"       0  1 three-kernel form, 2 eight elevations per block
+ *   "ml_shortcut"           0  0 certificate on, 2 always eigen-decompose, 3 telescope side only
+ *   "ml_eigen"              0  0 by batch size, 4 tridiagonal + QL, 1 blocked Jacobi, 2 full-matrix trailing updates, 3 QL made to fail (tests)
+ *   "ml_null"               0  0 sampled null certificate, 1 off, 2 every tile
+ *   "ml_reduce"             0  0 two-stage with every other update deferred, 3 its reading sweeps as one block per matrix, 2 none deferred, 1 one-stage
+ *   "ml_rank_stop"          0  accuracy-affecting (positive semi-definite input only): 0 on at 1e-13 of lambda_max, 1 off, v >= 11 on at 10^-v
+ *   "ml_chase_split"        0  1: one chase launch with the full band image
+ *   "ml_inner_sweeps"       0  accuracy-affecting: iteration cap of the Jacobi fallback (0: the built-in cap)
+ *   "ml_outer_sweeps"       0  accuracy-affecting: iteration cap of the Jacobi fallback (0: the built-in cap)
+ *   "gram_stage"            0  1: LDS-DMA operand staging of the Gram kernel
+ *   "wiener_overlap"        1  0: the batches of dmm_wiener_run on one stream
+ *   "ml_workspace_mib"      0  size the ML solve plans its batches for (0 = 20 GiB; negative values are stored as 0)
+ *   "regrid_workspace_mib"  0  scratch the regridder sizes its row chunks for (0 = 12 GiB: a cfg-3 day in one launch; negative: 0)
+ *   "wiener_workspace_mib"  0  size the Wiener solve plans its batches for (0 = 6 GiB; negative: 0)
+ *   "profile"               0  1: HIP-event timing of the dense solvers' kernel classes; every set collects the open spans and
+ *                              clears the sums; reads back as 0 or 1 */
 int dmm_ctx_set_option(dmm_ctx* ctx, const char* name, int64_t value);
-/* diagnostics counters, cumulative per context ("opt_sht_synth_form", "opt_ml_eigen": that option's current value): "ml_tiles_direct" (tiles whose pseudo-inverse was
+/* diagnostics counters, cumulative per context ("opt_<name>": the current value of option <name>, no wait): "ml_tiles_direct" (tiles whose pseudo-inverse was
  * certified to cut no mode and solved by Cholesky), "ml_tiles_eigen" (tiles eigen-decomposed), "ml_tiles_null" (tiles answered with zero by the null certificate: every
  * singular value at or below acond), "ml_tiles_stopped" / "ml_stop_cols" (eigen-decomposed tiles whose reduction the rank stop cut off,
  * and the sum of their effective orders), "ml_gram_flops" / "ml_band_bytes" (useful flops 4 k^2 K of the

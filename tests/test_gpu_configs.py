@@ -159,7 +159,6 @@ def test_cfg3_tile_ml_pseudo_inverse_property_and_sampled_oracle_svd():
     """BASELINE config 3 names ML at 758 x 2052.  For each sampled tile: the defining property of the pseudo-inverse
     solution with the reference's cut removing nothing (exact fit + minimum norm when nsky_m >= ntel, normal equations
     otherwise), and the oracle's SVD solve (``pinv_svd`` restated, mapmaker.py:287-300) on the same tile."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core.products import SyntheticProvider
     from draco_amd.device import Context
@@ -198,11 +197,8 @@ def test_cfg3_tile_ml_pseudo_inverse_property_and_sampled_oracle_svd():
             else:
                 assert np.abs(Bt.conj().T @ r).max() < 1e-9 * np.abs(Bt.conj().T @ dv).max(), m
         # the same tile through the eigen path (certificate off)
-        try:
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
+        with ctx.options(ml_shortcut=2):
             a_eig = ml._solve_m(m, 0, v, Ni)
-        finally:
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
         assert _rel(a_eig, a_ref) < 1e-8, (m, _rel(a_eig, a_ref))
 
 

@@ -96,7 +96,6 @@ def test_gram_operands_by_lds_dma_vs_oracle(kind, tol):
     """The A/B form of the beam Gram kernel (`gram_stage` = 1: operands DMA'd into a source-swizzled LDS image, the
     prior applied after the LDS read, the last partial chunk masked) against the oracle: ntel = 182 (three row tiles,
     padding), K = 4 (lmax + 1 - m) from 164 down to 4, so every m has a partial last chunk of a different length."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker, WienerMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import SyntheticProvider
@@ -113,13 +112,10 @@ def test_gram_operands_by_lds_dma_vs_oracle(kind, tol):
     mm.vis[:] = mv
     mm.weight[:] = mw
     ctx = Context.get()
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"gram_stage", 1))
-    try:
+    with ctx.options(gram_stage=1):
         task = (WienerMapMaker(prior_amp=2.5, prior_tilt=1.25) if kind == "wiener" else MaximumLikelihoodMapMaker())
         task.setup(bt)
         alm = task.alm_square(task.make_alm(mm))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"gram_stage", 0))
     beam = lambda m, f: osyn.beam_tile(540, m, f, tel.npairs, 4, lmax)  # noqa: E731
     kw = dict(prior_amp=2.5, prior_tilt=1.25) if kind == "wiener" else {}
     ref = omm.solve_alm(kind, beam, mv, mw, lmax, tel.mmax, list(range(nfreq)), **kw)
@@ -130,7 +126,6 @@ def test_wiener_two_batches_in_flight_is_the_same_solve(monkeypatch):
     """`dmm_wiener_run` alternates its batches between two streams, half the workspace each (`wiener_overlap`, default
     on).  A small workspace forces several batches per side; every tile's arithmetic is independent of its batch, so
     the one-stream pass must give the same bits -- and both agree with the oracle."""
-    from draco_amd import _lib
     from draco_amd.analysis._solve import SolveEngine
     from draco_amd.analysis.mapmaker import WienerMapMaker
     from draco_amd.core import containers
@@ -149,36 +144,20 @@ def test_wiener_two_batches_in_flight_is_the_same_solve(monkeypatch):
     ctx = Context.get()
     out, batches = {}, {}
     # the engine offers the solver half of the free HBM (one batch would take every tile): pin 24 MiB instead
-    monkeypatch.setattr(SolveEngine, "_offer_workspace", lambda self, option, cap_mib: _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, option, 24)))
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 1))
-        for ov in (1, 0):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"wiener_overlap", ov))
+    monkeypatch.setattr(SolveEngine, "_offer_workspace", lambda self, option, cap_mib: self.ctx.set_option(option, 24))
+    for ov in (1, 0):
+        with ctx.options(wiener_workspace_mib=24, profile=1, wiener_overlap=ov):
             task = WienerMapMaker(prior_amp=1.5, prior_tilt=0.75)
             task.setup(bt)
-            n0 = _counter(ctx, b"prof_gram_n")
+            n0 = ctx.counter(b"prof_gram_n")
             out[ov] = task.alm_square(task.make_alm(mm))
-            batches[ov] = _counter(ctx, b"prof_gram_n") - n0  # one Gram span per batch
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"wiener_overlap", 1))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"wiener_workspace_mib", 0))
+            batches[ov] = ctx.counter(b"prof_gram_n") - n0  # one Gram span per batch
     # batches alternate between the two streams: more than two per stream = a half's device lists were reused
     assert batches[1] >= 6 and batches[0] >= 3, batches
     assert np.array_equal(out[1], out[0])
     beam = lambda m, f: osyn.beam_tile(541, m, f, tel.npairs, 4, lmax)  # noqa: E731
     ref = omm.solve_alm("wiener", beam, mv, mw, lmax, tel.mmax, list(range(nfreq)), prior_amp=1.5, prior_tilt=0.75)
     assert _rel(out[1], ref) < 1e-10
-
-
-def _counter(ctx, name):
-    import ctypes as C
-
-    from draco_amd import _lib
-
-    v = C.c_int64()
-    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-    return int(v.value)
 
 
 _SHORTCUT_CASE = {}
@@ -225,7 +204,6 @@ def _shortcut_case():
 def test_ml_certified_shortcut_vs_eigen_path():
     """ML: the certified full-rank shortcut (Cholesky on the smaller Gram matrix, telescope or sky side)
     against the eigen-decomposition path on the same tiles, and both against the oracle (`_shortcut_case`)."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.device import Context
 
@@ -234,16 +212,13 @@ def test_ml_certified_shortcut_vs_eigen_path():
     nfreq, lmax, bt, mm, ref = case["nfreq"], case["lmax"], case["bt"], case["mm"], case["ref"]
     out = {}
     stats = {}
-    try:
-        for mode in (0, 2, 3):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", mode))
-            d0, e0 = _counter(ctx, b"ml_tiles_direct"), _counter(ctx, b"ml_tiles_eigen")
+    for mode in (0, 2, 3):
+        with ctx.options(ml_shortcut=mode):
+            d0, e0 = ctx.counter(b"ml_tiles_direct"), ctx.counter(b"ml_tiles_eigen")
             task = MaximumLikelihoodMapMaker()
             task.setup(bt)
             out[mode] = task.alm_square(task.make_alm(mm))
-            stats[mode] = (_counter(ctx, b"ml_tiles_direct") - d0, _counter(ctx, b"ml_tiles_eigen") - e0)
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
+            stats[mode] = (ctx.counter(b"ml_tiles_direct") - d0, ctx.counter(b"ml_tiles_eigen") - e0)
     ntile = nfreq * (lmax + 1)
     assert stats[2] == (0, ntile)
     assert stats[0][0] + stats[0][1] == ntile and stats[0][1] >= 2  # the two deficient tiles at least
@@ -260,7 +235,6 @@ def test_ml_pipelined_pass_reuses_its_slots_at_a_small_order(eigen, monkeypatch)
     range of the work array, its device lists -- is reused some twenty times.  `ml_eigen` = 3 makes QL give up on every
     other matrix of a chunk: those are collected when the chunk retires and go through the synchronous Jacobi batches
     at the end of the pass, which must leave the caller's `ml_eigen` alone."""
-    from draco_amd import _lib
     from draco_amd.analysis._solve import SolveEngine
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.device import Context
@@ -271,22 +245,16 @@ def test_ml_pipelined_pass_reuses_its_slots_at_a_small_order(eigen, monkeypatch)
     ntile = nfreq * (lmax + 1)
     mib, asked = 6, []
     workspace = SolveEngine._workspace
-    monkeypatch.setattr(SolveEngine, "_offer_workspace", lambda self, option, cap_mib: _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, option, mib)))
+    monkeypatch.setattr(SolveEngine, "_offer_workspace", lambda self, option, cap_mib: self.ctx.set_option(option, mib))
     monkeypatch.setattr(SolveEngine, "_workspace", lambda self, nbytes: (asked.append(nbytes), workspace(self, nbytes))[1])
     names = (b"ml_tiles_eigen", b"ml_tiles_direct", b"ml_tiles_ql_failed")
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", eigen))
-        c0 = [_counter(ctx, n) for n in names]
+    with ctx.options(ml_workspace_mib=mib, ml_shortcut=2, ml_eigen=eigen):
+        c0 = [ctx.counter(n) for n in names]
         task = MaximumLikelihoodMapMaker()
         task.setup(case["bt"])
         out = task.alm_square(task.make_alm(case["mm"]))
-        grew = [_counter(ctx, n) - v for n, v in zip(names, c0)]
-        eigen_after = _counter(ctx, b"opt_ml_eigen")
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_workspace_mib", 0))
+        grew = [ctx.counter(n) - v for n, v in zip(names, c0)]
+        eigen_after = ctx.get_option("ml_eigen")
     # capacity from what dmm_ml_workspace_bytes asked for: header + cap matrices + 1024 (the layout of the dense solvers:
     # A and two more matrices of the padded order, the right-hand side, 64 x 64 blocks and a few words per matrix)
     n, npad = 2 * tel.npairs, 128
@@ -307,7 +275,6 @@ def test_ml_pipelined_pass_reuses_its_slots_at_a_small_order(eigen, monkeypatch)
 def test_wiener_sky_side_vs_telescope_side():
     """Wiener: at high m (nsky_m < ntel) the sky-side system S^-1 + B^H Ni B is solved instead of the telescope-side
     one; both are the reference's own branches (mapmaker.py:267-278) and must agree with each other and the oracle."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import WienerMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import SyntheticProvider
@@ -325,14 +292,11 @@ def test_wiener_sky_side_vs_telescope_side():
     mm.vis[:] = mv
     mm.weight[:] = mw
     out = {}
-    try:
-        for mode in (0, 3):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", mode))
+    for mode in (0, 3):
+        with ctx.options(ml_shortcut=mode):
             task = WienerMapMaker(prior_amp=2.0, prior_tilt=0.75)
             task.setup(bt)
             out[mode] = task.alm_square(task.make_alm(mm))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
     beam = lambda m, f: osyn.beam_tile(606, m, f, tel.npairs, 4, lmax)  # noqa: E731
     ref = omm.solve_alm("wiener", beam, mv, mw, lmax, tel.mmax, list(range(nfreq)), prior_amp=2.0, prior_tilt=0.75)
     assert _rel(out[0], ref) < 1e-10
@@ -413,7 +377,6 @@ def test_ml_eigen_path_variants(variant):
     2 as 4 with full-matrix trailing updates, 3 QL forced to give up on every other matrix -> Jacobi fallback on the re-formed Gram matrices of those,
     0 the default (by batch size).
     Rank-deficient tiles, zero weights, telescope- and sky-side orders (64 ... 192) against the oracle's SVD."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import ArrayProvider
@@ -443,17 +406,12 @@ def test_ml_eigen_path_variants(variant):
     if "ref" not in _VARIANT_REF:  # the oracle's SVDs take most of the time: same inputs for every variant
         _VARIANT_REF["ref"] = omm.solve_alm("ml", beam, mv, mw, lmax, tel.mmax, list(range(nfreq)))
     ref = _VARIANT_REF["ref"]
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", variant))
-        e0 = _counter(ctx, b"ml_tiles_eigen")
+    with ctx.options(ml_shortcut=2, ml_eigen=variant):
+        e0 = ctx.counter(b"ml_tiles_eigen")
         task = MaximumLikelihoodMapMaker()
         task.setup(bt)
         out = task.alm_square(task.make_alm(mm))
-        assert _counter(ctx, b"ml_tiles_eigen") - e0 == nfreq * (lmax + 1)
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
+        assert ctx.counter(b"ml_tiles_eigen") - e0 == nfreq * (lmax + 1)
     assert _rel(out, ref) < 1e-8, variant
 
 
@@ -463,7 +421,6 @@ def test_ml_eigen_path_degenerate_tiles(variant):
     a tile with orthogonal rows of equal norm (G = c I: every eigenvalue equal, nothing to rotate), a tile with one
     non-zero row (rank 1) and a tile scaled by 1e-3 so that the absolute cut `acond` removes modes the relative one
     keeps.  All against the oracle's SVD."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import ArrayProvider
@@ -501,15 +458,10 @@ def test_ml_eigen_path_degenerate_tiles(variant):
     mm.vis[:] = mv
     mm.weight[:] = mw
     ref = omm.solve_alm("ml", beam, mv, mw, lmax, tel.mmax, [0])
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", variant))
+    with ctx.options(ml_shortcut=2, ml_eigen=variant):
         task = MaximumLikelihoodMapMaker()
         task.setup(bt)
         out = task.alm_square(task.make_alm(mm))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
     assert np.all(np.isfinite(out))
     assert np.all(out[..., 0] == 0)  # [freq, pol, l, m]
     for m in range(lmax + 1):
@@ -522,7 +474,6 @@ def test_ml_weights_over_eight_decades(variant):
     """Well-conditioned beam transfers but noise weights spread over 1 ... 1e-8 (one per baseline): the weighted
     matrix D B is ill conditioned, the certificate fails at low m, and the reference's cut drops the baselines whose
     weight is negligible.  Against the oracle's SVD of D B."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import SyntheticProvider
@@ -541,15 +492,12 @@ def test_ml_weights_over_eight_decades(variant):
     mm.weight[:] = mw
     beam = lambda m, f: osyn.beam_tile(909, m, f, tel.npairs, 4, lmax)  # noqa: E731
     ref = omm.solve_alm("ml", beam, mv, np.array(mw), lmax, tel.mmax, [0])
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", variant))
-        e0 = _counter(ctx, b"ml_tiles_eigen")
+    with ctx.options(ml_eigen=variant):
+        e0 = ctx.counter(b"ml_tiles_eigen")
         task = MaximumLikelihoodMapMaker()
         task.setup(bt)
         out = task.alm_square(task.make_alm(mm))
-        assert _counter(ctx, b"ml_tiles_eigen") - e0 > 0
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
+        assert ctx.counter(b"ml_tiles_eigen") - e0 > 0
     for m in range(lmax + 1):
         err = np.abs(out[..., m] - ref[..., m]).max() / np.abs(ref[..., m]).max()
         assert err < 1e-7, (m, err)
@@ -561,7 +509,6 @@ def test_ml_ill_conditioned_tiles(variant):
     the modes survive pinv_svd's relative cut at 1e-3.  The Gram route squares the condition number, so a kept mode
     sigma carries a relative error ~ eps (sigma_max / sigma)^2 <= 1e-10; agreement with the oracle's SVD of D B itself
     is asserted at 1e-7 of the solution's scale (far inside the 1e-5 map tolerance of the task)."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import ArrayProvider
@@ -594,16 +541,13 @@ def test_ml_ill_conditioned_tiles(variant):
     mm.vis[:] = mv
     mm.weight[:] = mw
     ref = omm.solve_alm("ml", beam, mv, mw, lmax, tel.mmax, [0])
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", variant))
-        d0, e0 = _counter(ctx, b"ml_tiles_direct"), _counter(ctx, b"ml_tiles_eigen")
+    with ctx.options(ml_eigen=variant):
+        d0, e0 = ctx.counter(b"ml_tiles_direct"), ctx.counter(b"ml_tiles_eigen")
         task = MaximumLikelihoodMapMaker()
         task.setup(bt)
         out = task.alm_square(task.make_alm(mm))
-        assert _counter(ctx, b"ml_tiles_direct") == d0  # no tile passes the full-rank certificate
-        assert _counter(ctx, b"ml_tiles_eigen") - e0 == lmax + 1
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
+        assert ctx.counter(b"ml_tiles_direct") == d0  # no tile passes the full-rank certificate
+        assert ctx.counter(b"ml_tiles_eigen") - e0 == lmax + 1
     for m in range(lmax + 1):
         err = np.abs(out[..., m] - ref[..., m]).max() / np.abs(ref[..., m]).max()
         assert err < 1e-7, (m, err)
@@ -614,7 +558,6 @@ def test_ml_rank_deficient_tiles_stay_on_the_tridiagonal_path():
     redundant baselines) against the oracle's SVD, every tile solved by the tridiagonal path itself.  (Small-order
     companion of tests/test_gpu_fullsize.py::test_cfg3_ml_rank_deficient_telescope_side_stays_on_the_tridiagonal_path,
     where clusters of hundreds of zeros made QL give up before its negligibility test got an absolute floor.)"""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import ArrayProvider
@@ -647,16 +590,13 @@ def test_ml_rank_deficient_tiles_stay_on_the_tridiagonal_path():
     mm.vis[:] = mv
     mm.weight[:] = mw
     ref = omm.solve_alm("ml", beam, mv, mw, lmax, tel.mmax, [0])
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 4))
-        e0, q0 = _counter(ctx, b"ml_tiles_eigen"), _counter(ctx, b"ml_tiles_ql_failed")
+    with ctx.options(ml_eigen=4):
+        e0, q0 = ctx.counter(b"ml_tiles_eigen"), ctx.counter(b"ml_tiles_ql_failed")
         task = MaximumLikelihoodMapMaker()
         task.setup(bt)
         out = task.alm_square(task.make_alm(mm))
-        assert _counter(ctx, b"ml_tiles_eigen") - e0 == lmax + 1
-        assert _counter(ctx, b"ml_tiles_ql_failed") == q0
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
+        assert ctx.counter(b"ml_tiles_eigen") - e0 == lmax + 1
+        assert ctx.counter(b"ml_tiles_ql_failed") == q0
     for m in range(lmax + 1):
         err = np.abs(out[..., m] - ref[..., m]).max() / np.abs(ref[..., m]).max()
         assert err < 1e-7, (m, err)

@@ -47,12 +47,9 @@ def _dirty(ctx, slab, mv, mw, alms, nofill):
     from draco_amd.device import ptr
 
     PA = C.c_void_p * len(alms)
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"dirty_nofill", int(nofill)))
-    try:
+    with ctx.options(dirty_nofill=int(nofill)):
         _lib.check(_lib.lib.dmm_dirty_run_multi(slab.plan, ptr(slab.pool), PA(*[ptr(x) for x in mv]), PA(*[ptr(x) for x in mw]),
                                                 PA(*[ptr(x) for x in alms]), len(alms)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"dirty_nofill", 0))
 
 
 def _alm2map(ctx, alm, lmax, nside):
@@ -62,11 +59,8 @@ def _alm2map(ctx, alm, lmax, nside):
     from draco_amd.device import ptr
 
     maps = torch.empty((NFREQ, 4, 12 * nside**2), dtype=torch.float64, device=ctx.device)
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_synth_form", 1))
-    try:
+    with ctx.options(sht_synth_form=1):
         _lib.check(_lib.lib.dmm_alm2map(ctx.handle, ptr(alm), NFREQ, 4, lmax, lmax, nside, ptr(maps)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_synth_form", 0))
     return maps
 
 

@@ -139,31 +139,6 @@ class Plan:
         return np.array_equal(_host(self.pool).view(np.uint8), self.pool_h.view(np.uint8))
 
 
-class options:
-    """``dmm_ctx_set_option`` of tuning options for a block; every one is back at 0 afterwards, whatever happened."""
-
-    def __init__(self, **opts):
-        self.opts = opts
-
-    def _set(self, name, value):
-        from draco_amd import _lib
-
-        _lib.check(_lib.lib.dmm_ctx_set_option(_ctx().handle, name.encode(), int(value)))
-
-    def __enter__(self):
-        try:
-            for k, v in self.opts.items():
-                self._set(k, v)
-        except BaseException:
-            self.__exit__()
-            raise
-        return self
-
-    def __exit__(self, *exc):
-        for k in self.opts:
-            self._set(k, 0)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # cases
 
@@ -392,9 +367,9 @@ def test_several_thousand_small_tiles(kind):
     with Plan(case) as plan:
         got = plan.dirty(_dev(mvis), _dev(mw))
         _note(dirty_family(case), dt.check_launch(got, exp, what=f"3904 tiles {kind}"))
-        with options(dirty_static=1):  # static striding over the same table: same sums, same bits
+        with _ctx().options(dirty_static=1):  # static striding over the same table: same sums, same bits
             assert np.array_equal(plan.dirty(_dev(mvis), _dev(mw)), got)
-        with options(grid_mult=8):
+        with _ctx().options(grid_mult=8):
             assert np.array_equal(plan.dirty(_dev(mvis), _dev(mw)), got)
         check_project(plan, np.random.default_rng(4201), f"3904 tiles {kind}")
 
@@ -591,7 +566,7 @@ def test_dirty_options_bit_identical_to_default(which, kind):
         base, (mvis, mw) = check_dirty(plan, rng, f"options default {which} {kind}")
         v, w = _dev(mvis), _dev(mw)
         for opts in DIRTY_OPTIONS:
-            with options(**opts):
+            with _ctx().options(**opts):
                 got = plan.dirty(v, w)
             assert np.array_equal(got, base), f"{_opt_id(opts)} on {which} {kind} differs from the default"
         assert np.array_equal(plan.dirty(v, w), base)  # options are back at 0
@@ -610,7 +585,7 @@ def test_dirty_multi_options_bit_identical_to_default(which, kind):
         single = [plan.dirty(v, w) for v, w in dev]
         _note(dirty_family(case), dt.check_launch(single[10], case.expected_alm(*days[10]), what=f"multi options day 10 {which} {kind}"))
         for opts in [{}] + DIRTY_OPTIONS:
-            with options(**opts):
+            with _ctx().options(**opts):
                 got = plan.dirty_multi([v for v, _ in dev], [w for _, w in dev])
             for d in range(11):
                 assert np.array_equal(got[d], single[d]), f"{_opt_id(opts) or 'default'} on {which} {kind}: day {d} differs"
@@ -628,12 +603,12 @@ def test_project_options(which):
         a = _dev(alm)
         exp = case.expected_vis(alm)
         for opts in ({"project_variant": 5}, {"project_variant": 6}, {"project_grid_mult": 2}, {"project_variant": 6, "project_grid_mult": 2}):
-            with options(**opts):
+            with _ctx().options(**opts):
                 got = plan.project(a)
             assert np.array_equal(got, base), f"{_opt_id(opts)} on {which} differs from the default"
         for v in (1, 2, 3, 4):
             for gm in (0, 2):
-                with options(project_variant=v, project_grid_mult=gm):
+                with _ctx().options(project_variant=v, project_grid_mult=gm):
                     got = plan.project(a)
                 _note("project c128", dt.check_launch(got, exp, what=f"project_variant={v} project_grid_mult={gm} on {which}"))
         assert np.array_equal(plan.project(a), base)
@@ -647,14 +622,14 @@ def test_project_options_complex64_and_full_layout():
     with Plan(case) as plan:
         base, alm = check_project(plan, rng, "project options c64")
         for opts in [{"project_variant": v} for v in range(1, 7)] + [{"project_grid_mult": 2}]:
-            with options(**opts):
+            with _ctx().options(**opts):
                 assert np.array_equal(plan.project(_dev(alm)), base), _opt_id(opts)
     full = make_case(rng, 20, 3, 70, 2, 71, [(0, 0), (69, 1), (33, 1), (6, 0)], "c128", dt.FULL)
     with Plan(full) as plan:
         base, alm = check_project(plan, rng, "project options full layout")
         exp = full.expected_vis(alm)
         for v in range(1, 7):
-            with options(project_variant=v):
+            with _ctx().options(project_variant=v):
                 got = plan.project(_dev(alm))
             _note("project c128", dt.check_launch(got, exp, what=f"project_variant={v} full layout"))
             if v >= 5:

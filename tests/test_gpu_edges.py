@@ -163,7 +163,7 @@ def test_abi_argument_errors_on_gpu():
     with pytest.raises(ValueError, match="out of range"):
         _lib.check(_lib.lib.dmm_solve_plan_create(ctx.handle, tiles, 1, 3, 4, 5, 1, 6, 1, 1, C.byref(h)))
     with pytest.raises(ValueError, match="unknown option"):
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"nope", 1))
+        ctx.set_option(b"nope", 1)
 
 
 def test_mask_mmode_data_golden(golden_dir):

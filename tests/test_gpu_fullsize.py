@@ -137,7 +137,6 @@ def test_cfg4_tile_wiener_and_ml_properties():
     """cfg-4/5 tile size (ntel = 1526 -> padded order 1536, nsky up to 4100): Wiener normal equations; ML on the
     telescope side (m = 0) and on the sky side (m = 900, order 500) satisfies the least-squares / minimum-norm
     conditions of the pseudo-inverse with nothing cut, and agrees with the eigen path."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker, WienerMapMaker
     from draco_amd.core.products import SyntheticProvider
     from draco_amd.device import Context
@@ -174,13 +173,8 @@ def test_cfg4_tile_wiener_and_ml_properties():
         else:  # overdetermined: normal equations
             assert np.abs(Bt.conj().T @ r).max() < 1e-9 * np.abs(Bt.conj().T @ (np.sqrt(nv) * vv)).max(), m
         for eig in (1, 4):  # blocked Jacobi; Householder tridiagonalisation + QL (order 1536: six column chunks per wave)
-            try:
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", eig))
+            with ctx.options(ml_shortcut=2, ml_eigen=eig):
                 a_eig = ml._solve_m(m, 0, v, Ni)
-            finally:
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
             assert _rel(a, a_eig) < 1e-9, (m, eig)
 
 
@@ -203,12 +197,9 @@ def test_cfg4_sht_roundtrip_nside512():
     alm = alm.contiguous()
     maps = ctx.empty((1, 4, 12 * nside * nside), np.float64)
     _lib.check(_lib.lib.dmm_alm2map(ctx.handle, ptr(alm), 1, 4, lmax, lmax, nside, ptr(maps)))
-    try:  # every ring through the direct sums
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 4))
+    with ctx.options(sht_variant=4):  # every ring through the direct sums
         maps_d = ctx.empty((1, 4, 12 * nside * nside), np.float64)
         _lib.check(_lib.lib.dmm_alm2map(ctx.handle, ptr(alm), 1, 4, lmax, lmax, nside, ptr(maps_d)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     assert float((maps - maps_d).abs().max()) < 1e-11 * float(maps_d.abs().max())
     back = ctx.empty((1, 4, lmax + 1, lmax + 1), np.complex128)
     _lib.check(_lib.lib.dmm_map2alm(ctx.handle, ptr(maps), 1, 4, lmax, lmax, nside, 3, ptr(back)))
@@ -241,14 +232,9 @@ def test_cfg3_ml_eigen_pass_mixes_pipelined_and_synchronous_batches():
     mw = torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=gen) * 30.0 + 5.0
     eng = SolveEngine(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
     out = {}
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        for eig in (0, 1):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", eig))
+    for eig in (0, 1):
+        with ctx.options(ml_shortcut=2, ml_eigen=eig):
             out[eig] = eng.solve("ml", mv, mw, [0], lmax).cpu().numpy()
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
     assert np.all(np.isfinite(out[0]))
     assert _rel(out[0], out[1]) < 1e-9
     # and the batched pass against the oracle's SVD on sampled rows: telescope side, near-square, sky side
@@ -260,7 +246,6 @@ def test_ml_tridiagonal_path_at_other_orders(nfeed_cyl, np_expected):
     """The kernel variants of the tridiagonal eigen path are chosen by matrix order: six column chunks per wave and two
     pending updates up to 1536, eight chunks and one up to 2048, full-matrix trailing sweeps beyond.  One telescope-side
     tile (m = 0) and one sky-side tile at each of three orders in those ranges, against the blocked Jacobi."""
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core.products import SyntheticProvider, TransitTelescope
     from draco_amd.device import Context
@@ -279,14 +264,9 @@ def test_ml_tridiagonal_path_at_other_orders(nfeed_cyl, np_expected):
         Ni = rng.uniform(0.5, 1.5, (2, tel.npairs)) * 10
         Ni[rng.uniform(size=Ni.shape) < 0.05] = 0
         out = {}
-        try:
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-            for eig in (1, 4):
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", eig))
+        for eig in (1, 4):
+            with ctx.options(ml_shortcut=2, ml_eigen=eig):
                 out[eig] = ml._solve_m(m, 0, v, Ni)
-        finally:
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_eigen", 0))
         assert np.all(np.isfinite(out[4]))
         assert _rel(out[4], out[1]) < 1e-9, (m, _rel(out[4], out[1]))
 
@@ -314,22 +294,12 @@ def test_cfg3_ml_rank_deficient_telescope_side_stays_on_the_tridiagonal_path():
     mw = torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=gen) * 30.0 + 5.0
     eng = SolveEngine(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
 
-    def counter(name):
-        import ctypes as C
-
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     ref = eng.solve("ml", mv, mw, [0], lmax).cpu().numpy()
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 3))
-        q0, e0 = counter(b"ml_tiles_ql_failed"), counter(b"ml_tiles_eigen")
+    with ctx.options(ml_shortcut=3):
+        q0, e0 = ctx.counter(b"ml_tiles_ql_failed"), ctx.counter(b"ml_tiles_eigen")
         out = eng.solve("ml", mv, mw, [0], lmax).cpu().numpy()
-        assert counter(b"ml_tiles_eigen") - e0 >= lmax - 323  # the rank-deficient tiles cannot pass the certificate
-        assert counter(b"ml_tiles_ql_failed") == q0
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
+        assert ctx.counter(b"ml_tiles_eigen") - e0 >= lmax - 323  # the rank-deficient tiles cannot pass the certificate
+        assert ctx.counter(b"ml_tiles_ql_failed") == q0
     assert np.all(np.isfinite(out))
     for m in (0, 200, 330, 400, 480, 510):
         assert _rel(out[..., m, :], ref[..., m, :]) < 1e-7, m
@@ -358,23 +328,13 @@ def test_cfg3_ml_low_pass_rate_scheduling_matches_the_eigen_only_pass():
     mw = (torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=gen) * 40.0 + 10.0) * spread
     eng = SolveEngine(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
 
-    def counter(name):
-        import ctypes as C
-
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
-    d0, e0, q0 = counter(b"ml_tiles_direct"), counter(b"ml_tiles_eigen"), counter(b"ml_tiles_ql_failed")
+    d0, e0, q0 = ctx.counter(b"ml_tiles_direct"), ctx.counter(b"ml_tiles_eigen"), ctx.counter(b"ml_tiles_ql_failed")
     out = eng.solve("ml", mv, mw, [0], lmax, acond=1e-4, rcond=1e-3).cpu().numpy()
-    nd, ne = counter(b"ml_tiles_direct") - d0, counter(b"ml_tiles_eigen") - e0
+    nd, ne = ctx.counter(b"ml_tiles_direct") - d0, ctx.counter(b"ml_tiles_eigen") - e0
     assert nd + ne == lmax + 1 and ne > nd  # every tile once; most of them decomposed
-    assert counter(b"ml_tiles_ql_failed") == q0
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
+    assert ctx.counter(b"ml_tiles_ql_failed") == q0
+    with ctx.options(ml_shortcut=2):
         ref = eng.solve("ml", mv, mw, [0], lmax, acond=1e-4, rcond=1e-3).cpu().numpy()
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
     assert np.all(np.isfinite(out))
     assert _rel(out, ref) < 1e-8
     # sampled rows of the scheduled pass against the oracle's SVD.  The weights span eight decades: modes just above the
@@ -392,8 +352,6 @@ def test_cfg3_ml_early_reject_chunk_runs_beside_full_direct_batches():
     full ones for the 648 telescope-side tiles); the weights of ten m near the square tiles span eight decades, so
     those 20 tiles are rejected in the FIRST direct batch and go to slot 0 under the full batches that follow.  The
     answer must be the one of the pass that decomposes every tile."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -412,28 +370,20 @@ def test_cfg3_ml_early_reject_chunk_runs_beside_full_direct_batches():
     spread = torch.pow(10.0, -8.0 * torch.rand((10, 1, 1, tel.npairs), dtype=torch.float64, device=ctx.device, generator=gen))
     mw[290:300] *= spread  # ten ill-conditioned m inside the first telescope-side batch (m = 323 downwards)
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     class FixedWorkspace(SolveEngine):
         def _offer_workspace(self, option, cap_mib):  # (the engine would offer half of the free HBM)
-            _lib.check(_lib.lib.dmm_ctx_set_option(self.ctx.handle, option, 8192))
+            self.ctx.set_option(option, 8192)
 
     eng = FixedWorkspace(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
-    try:
-        c0, e0, d0 = counter(b"ml_early_chunks"), counter(b"ml_tiles_eigen"), counter(b"ml_tiles_direct")
+    with ctx.options(ml_workspace_mib=8192):
+        c0, e0, d0 = ctx.counter(b"ml_early_chunks"), ctx.counter(b"ml_tiles_eigen"), ctx.counter(b"ml_tiles_direct")
         out = eng.solve("ml", mv, mw, [0, 1], lmax, acond=1e-4, rcond=1e-3).cpu().numpy()
-        early = counter(b"ml_early_chunks") - c0
-        ne, nd = counter(b"ml_tiles_eigen") - e0, counter(b"ml_tiles_direct") - d0
+        early = ctx.counter(b"ml_early_chunks") - c0
+        ne, nd = ctx.counter(b"ml_tiles_eigen") - e0, ctx.counter(b"ml_tiles_direct") - d0
         assert early >= 1, "the early-reject path was not taken: the test no longer covers what it is for"
         assert ne + nd == 2 * (lmax + 1) and 20 <= ne <= 70, (ne, nd)
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        ref = eng.solve("ml", mv, mw, [0, 1], lmax, acond=1e-4, rcond=1e-3).cpu().numpy()
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_workspace_mib", 0))
+        with ctx.options(ml_shortcut=2):
+            ref = eng.solve("ml", mv, mw, [0, 1], lmax, acond=1e-4, rcond=1e-3).cpu().numpy()
     assert np.all(np.isfinite(out))
     assert _rel(out, ref) < 1e-8
     # rows of both frequencies against the oracle's SVD: certified tiles, the ill-conditioned ones of the early chunk, sky side
@@ -446,8 +396,6 @@ def test_cfg3_ml_two_stage_reduction_against_the_one_stage_reduction():
     (dense -> band of half-width 8 on the matrix cores -> tridiagonal by bulge chasing in LDS, "ml_reduce" = 0, the
     default wherever the band fits the LDS) and one-stage Householder ("ml_reduce" = 1).  Telescope-side order 768 and
     every sky-side order from 704 down to 64; the library's kernel-class timers say which reduction ran."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -466,23 +414,11 @@ def test_cfg3_ml_two_stage_reduction_against_the_one_stage_reduction():
     mw[torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=gen) < 0.02] = 0.0
     eng = SolveEngine(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     out, spans = {}, {}
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        for red in (0, 1):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", red))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 1))
+    for red in (0, 1):
+        with ctx.options(ml_shortcut=2, ml_reduce=red, profile=1):
             out[red] = eng.solve("ml", mv, mw, [0], lmax).cpu().numpy()
-            spans[red] = (counter(b"prof_band_n"), counter(b"prof_tridiag_n"))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", 0))
+            spans[red] = (ctx.counter(b"prof_band_n"), ctx.counter(b"prof_tridiag_n"))
     assert spans[0][0] > 0 and spans[0][1] == 0, spans  # two-stage only
     assert spans[1][0] == 0 and spans[1][1] > 0, spans  # one-stage only
     assert np.all(np.isfinite(out[0]))
@@ -497,8 +433,6 @@ def test_ml_two_stage_reduction_at_the_largest_order_the_lds_takes():
     per matrix ("ml_reduce" = 3), as one kernel ("ml_reduce" = 5, in a `make EXTRA=-DDMM_AB` build: counter "build_ab"),
     with no update deferred ("ml_reduce" = 2: rounds 3-5's form), one-stage ("ml_reduce" = 1) -- and sampled rows against
     the oracle's SVD.  In a default build "ml_reduce" = 5 runs the default form: its output is the default's, bit for bit."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -518,23 +452,11 @@ def test_ml_two_stage_reduction_at_the_largest_order_the_lds_takes():
     mw[torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=gen) < 0.02] = 0.0
     eng = SolveEngine(bt, ctx, _lib.DMM_C128, _lib.DMM_B_PACKED)
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     out, spans = {}, {}
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 2))
-        for red in (0, 3, 5, 2, 1):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", red))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 1))
+    for red in (0, 3, 5, 2, 1):
+        with ctx.options(ml_shortcut=2, ml_reduce=red, profile=1):
             out[red] = eng.solve("ml", mv, mw, [0], lmax).cpu().numpy()
-            spans[red] = (counter(b"prof_band_n"), counter(b"prof_chase_n"), counter(b"prof_tridiag_n"))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"profile", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", 0))
+            spans[red] = (ctx.counter(b"prof_band_n"), ctx.counter(b"prof_chase_n"), ctx.counter(b"prof_tridiag_n"))
     for red in (0, 3, 5, 2):
         assert spans[red][0] > 0 and spans[red][1] > 0 and spans[red][2] == 0, spans  # two-stage only
     assert spans[1][0] == 0 and spans[1][2] > 0, spans  # one-stage only
@@ -542,7 +464,7 @@ def test_ml_two_stage_reduction_at_the_largest_order_the_lds_takes():
     assert _rel(out[0], out[1]) < 1e-9
     assert _rel(out[2], out[1]) < 1e-9
     assert _rel(out[3], out[1]) < 1e-9
-    if counter(b"build_ab"):
+    if ctx.counter(b"build_ab"):
         assert _rel(out[5], out[1]) < 1e-9
     else:
         assert np.array_equal(out[5], out[0])

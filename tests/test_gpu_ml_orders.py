@@ -19,7 +19,6 @@ relative.  A sample is only taken where the oracle's spectrum keeps its distance
 near it the rank itself is a rounding decision of either side.
 """
 
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -34,14 +33,6 @@ ACOND, RCOND = 1e-4, 1e-3
 
 def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def _counter(ctx, name):
-    from draco_amd import _lib
-
-    v = C.c_int64()
-    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-    return int(v.value)
 
 
 def _well_separated(sig, gap=1e-3):
@@ -97,23 +88,18 @@ class _Case:
 
         lib, h = _lib.lib, self.ctx.handle
         names = (b"ml_tiles_eigen", b"ml_tiles_direct", b"ml_tiles_ql_failed", b"ml_tiles_basis")
-        before = {k: _counter(self.ctx, k) for k in names}
+        before = {k: self.ctx.counter(k) for k in names}
         diag = torch.full((1, self.mmax + 1, 4), -1.0, dtype=torch.float64, device=self.ctx.device)
-        try:
-            for k, v in opts.items():
-                _lib.check(lib.dmm_ctx_set_option(h, k.encode(), v))
-            _lib.check(lib.dmm_ctx_set_option(h, b"profile", 1))
-            _lib.check(lib.dmm_ctx_set_ml_diag(h, ptr(diag)))
-            out = self.eng.solve("ml", self.mv, self.mw, [0], self.mmax).cpu().numpy()[0]
-            self.ctx.sync()
-            cnt = {k.decode(): _counter(self.ctx, k) - before[k] for k in names}
-            for k in (b"band", b"chase", b"tridiag"):
-                cnt[k.decode()] = _counter(self.ctx, b"prof_" + k + b"_n")
-        finally:
-            _lib.check(lib.dmm_ctx_set_ml_diag(h, None))
-            _lib.check(lib.dmm_ctx_set_option(h, b"profile", 0))
-            for k in opts:
-                _lib.check(lib.dmm_ctx_set_option(h, k.encode(), 0))
+        with self.ctx.options(**opts, profile=1):
+            try:
+                _lib.check(lib.dmm_ctx_set_ml_diag(h, ptr(diag)))
+                out = self.eng.solve("ml", self.mv, self.mw, [0], self.mmax).cpu().numpy()[0]
+                self.ctx.sync()
+                cnt = {k.decode(): self.ctx.counter(k) - before[k] for k in names}
+                for k in (b"band", b"chase", b"tridiag"):
+                    cnt[k.decode()] = self.ctx.counter(b"prof_" + k + b"_n")
+            finally:
+                _lib.check(lib.dmm_ctx_set_ml_diag(h, None))
         return out, diag.cpu().numpy()[0, :, 0].round().astype(int), cnt
 
     def oracle(self, m):
@@ -181,7 +167,7 @@ def test_ml_order_896_one_stage_telescope_side_two_stage_sky_side():
         _same(out[red], out[0], ranks[red], ranks[0])
     # telescope side (m 0, near-square 14), near-square sky side (15: order 896), two-stage orders 832, 704, 448, 128, 64
     c.check_oracle(out[0], ranks[0], (0, 14, 15, 30, 60, 120, 200, 222))
-    assert _counter(c.ctx, b"ml_two_stage_max_order") == 832
+    assert c.ctx.counter(b"ml_two_stage_max_order") == 832
 
 
 def test_ml_order_896_eigen_solvers_agree():
@@ -233,11 +219,11 @@ def test_ml_order_896_basis_route_declines_above_the_two_stage_limit():
         return out, diag.cpu().numpy()[0, :, 0]
 
     a_ref, r_ref = day(False)
-    b0 = _counter(c.ctx, b"ml_tiles_basis")
+    b0 = c.ctx.counter(b"ml_tiles_basis")
     a1, r1 = day(True)
     a2, r2 = day(True)  # (a second day: where a basis would be used, not built)
-    assert _counter(c.ctx, b"ml_tiles_basis") == b0
-    assert c.np_tel > _counter(c.ctx, b"ml_two_stage_max_order")
+    assert c.ctx.counter(b"ml_tiles_basis") == b0
+    assert c.np_tel > c.ctx.counter(b"ml_two_stage_max_order")
     assert np.all(np.isfinite(a1))
     for a, r in ((a1, r1), (a2, r2)):
         assert np.array_equal(r, r_ref)

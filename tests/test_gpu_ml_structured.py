@@ -66,8 +66,6 @@ def _setup(nfreq=2, zero_frac=0.02, seed=11, chan0=0, **screen):
     ("top", {"chan0": 254}, [(0, 0), (0, 60), (0, 250), (0, 322), (0, 330), (0, 420), (1, 100), (1, 380)]),
 ])
 def test_cfg3_ml_batched_pass_on_structured_tiles_against_the_oracle_svd(name, screen, sample):
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -82,32 +80,24 @@ def test_cfg3_ml_batched_pass_on_structured_tiles_against_the_oracle_svd(name, s
     task = MaximumLikelihoodMapMaker(nside=64, pool_bytes=nfreq * per_f + (1 << 20))
     task.setup(bt)
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     diag = torch.full((nfreq, n_m, 4), -1.0, dtype=torch.float64, device=ctx.device)
-    e0, d0, z0 = counter(b"ml_tiles_eigen"), counter(b"ml_tiles_direct"), counter(b"ml_tiles_null")
-    st0, sc0 = counter(b"ml_tiles_stopped"), counter(b"ml_stop_cols")
+    e0, d0, z0 = ctx.counter(b"ml_tiles_eigen"), ctx.counter(b"ml_tiles_direct"), ctx.counter(b"ml_tiles_null")
+    st0, sc0 = ctx.counter(b"ml_tiles_stopped"), ctx.counter(b"ml_stop_cols")
     _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, ptr(diag)))
     try:
         alm = task.make_alm(mm)  # the batched default pass (certificate probe, deferred eigen pass, two-stage reduction with its rank stop)
         ctx.sync()
     finally:
         _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, None))
-    n_stop, stop_cols = counter(b"ml_tiles_stopped") - st0, counter(b"ml_stop_cols") - sc0
-    n_eig, n_dir, n_null = counter(b"ml_tiles_eigen") - e0, counter(b"ml_tiles_direct") - d0, counter(b"ml_tiles_null") - z0
+    n_stop, stop_cols = ctx.counter(b"ml_tiles_stopped") - st0, ctx.counter(b"ml_stop_cols") - sc0
+    n_eig, n_dir, n_null = ctx.counter(b"ml_tiles_eigen") - e0, ctx.counter(b"ml_tiles_direct") - d0, ctx.counter(b"ml_tiles_null") - z0
     assert n_eig + n_dir + n_null == nfreq * n_m
     # the null certificate is a shortcut, never a different answer: switched off, the same tiles are decomposed to the same zeros
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_null", 1))
-    try:
-        e1 = counter(b"ml_tiles_eigen")
+    with ctx.options(ml_null=1):
+        e1 = ctx.counter(b"ml_tiles_eigen")
         alm_off = task.make_alm(mm)
         ctx.sync()
-        assert counter(b"ml_tiles_eigen") - e1 == n_eig + n_null
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_null", 0))
+        assert ctx.counter(b"ml_tiles_eigen") - e1 == n_eig + n_null
     # (not bit for bit everywhere: with fewer tiles the sky-side lists pair up differently and a tile may be reduced at
     # another padded order; the tiles the certificate answered are exact zeros either way)
     alm = alm.cpu().numpy()
@@ -198,8 +188,6 @@ def test_rank_stop_of_the_band_reduction_changes_no_rank_and_no_solution():
     """The rank stop (herm_band.h: trailing trace <= 1e-13 of lambda_max's lower bound) cuts the reduction of a Gram matrix
     off where what is left is below pinv_svd's cut by seven decades (mapmaker.py:296).  On and off must keep the same
     modes on every tile and give the same a_lm; on well-conditioned tiles it never fires and the pass is bit-identical."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -212,27 +200,19 @@ def test_rank_stop_of_the_band_reduction_changes_no_rank_and_no_solution():
     ctx, tel, bt, mm, mv, mw, per_f = _setup(nfreq, seed=13)
     n_m = tel.lmax + 1
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     def run(provider, stop, shortcut=0):
         task = MaximumLikelihoodMapMaker(nside=64, pool_bytes=nfreq * per_f + (1 << 20))
         task.setup(provider)
         diag = torch.full((nfreq, n_m, 4), -1.0, dtype=torch.float64, device=ctx.device)
-        s0, c0 = counter(b"ml_tiles_stopped"), counter(b"ml_stop_cols")
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_rank_stop", stop))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", shortcut))
-        _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, ptr(diag)))
-        try:
-            alm = task.make_alm(mm)
-            ctx.sync()
-        finally:
-            _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, None))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_rank_stop", 0))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", 0))
-        return alm.cpu().numpy(), diag.cpu().numpy(), counter(b"ml_tiles_stopped") - s0, counter(b"ml_stop_cols") - c0
+        s0, c0 = ctx.counter(b"ml_tiles_stopped"), ctx.counter(b"ml_stop_cols")
+        with ctx.options(ml_rank_stop=stop, ml_shortcut=shortcut):
+            _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, ptr(diag)))
+            try:
+                alm = task.make_alm(mm)
+                ctx.sync()
+            finally:
+                _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, None))
+        return alm.cpu().numpy(), diag.cpu().numpy(), ctx.counter(b"ml_tiles_stopped") - s0, ctx.counter(b"ml_stop_cols") - c0
 
     a_on, d_on, n_on, cols_on = run(bt, 0)
     a_off, d_off, n_off, _ = run(bt, 1)
@@ -265,22 +245,14 @@ def test_resident_beam_gram_products_give_bit_identical_days():
     (mapmaker.py:190-198 whitens B with them); with the products B B^H kept beside the resident B block the second day's
     matrices are formed by the Gram kernel's own scaling -- every a_lm must equal the uncached pass bit for bit, on the day
     that fills the cache and on the days that use it, also after the B block changed hands."""
-    import ctypes as C
-
     import torch
 
-    from draco_amd import _lib
     from draco_amd.analysis import _solve
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
 
     nfreq = 2
     ctx, tel, bt, mm, mv, mw, per_f = _setup(nfreq, seed=15)
-
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
 
     gen = torch.Generator(device=ctx.device).manual_seed(99)
     days = [mm]
@@ -297,36 +269,36 @@ def test_resident_beam_gram_products_give_bit_identical_days():
     ref = [plain.make_alm(d).cpu().numpy() for d in days]
     cached = MaximumLikelihoodMapMaker(nside=64, pool_bytes=nfreq * per_f + (1 << 20), cache_beam_gram=True)
     cached.setup(bt)
-    c0, e0 = counter(b"ml_gram_cached"), counter(b"ml_tiles_eigen")
+    c0, e0 = ctx.counter(b"ml_gram_cached"), ctx.counter(b"ml_tiles_eigen")
     a0 = cached.make_alm(days[0]).cpu().numpy()  # fills the cache
-    assert counter(b"ml_gram_cached") == c0
-    n_eig = counter(b"ml_tiles_eigen") - e0
+    assert ctx.counter(b"ml_gram_cached") == c0
+    n_eig = ctx.counter(b"ml_tiles_eigen") - e0
     a1 = cached.make_alm(days[1]).cpu().numpy()  # every telescope-side Gram matrix from its resident product
-    n_cached = counter(b"ml_gram_cached") - c0
+    n_cached = ctx.counter(b"ml_gram_cached") - c0
     n_tel = sum(1 for m in range(tel.lmax + 1) if 4 * (tel.lmax + 1 - m) >= 2 * tel.npairs) * nfreq
     assert 0 < n_cached <= n_tel and n_cached > 0.5 * min(n_eig, n_tel)
     assert np.array_equal(a0, ref[0]) and np.array_equal(a1, ref[1])
     # the B block is given back and filled again: the engine starts the cache over (no stale product survives)
     _solve.release_pools()
-    c1 = counter(b"ml_gram_cached")
+    c1 = ctx.counter(b"ml_gram_cached")
     a2 = cached.make_alm(days[2]).cpu().numpy()
-    assert counter(b"ml_gram_cached") == c1
+    assert ctx.counter(b"ml_gram_cached") == c1
     assert np.array_equal(a2, ref[2])
     a2b = cached.make_alm(days[2]).cpu().numpy()
-    assert counter(b"ml_gram_cached") > c1 and np.array_equal(a2b, ref[2])
+    assert ctx.counter(b"ml_gram_cached") > c1 and np.array_equal(a2b, ref[2])
     # D days from one pass over B (`make_alm_many`): the products computed for the first day of a group serve the others
     _solve.release_pools()
-    c2 = counter(b"ml_gram_cached")
+    c2 = ctx.counter(b"ml_gram_cached")
     many = [a.cpu().numpy() for a in cached.make_alm_many(days)]
-    assert counter(b"ml_gram_cached") > c2
+    assert ctx.counter(b"ml_gram_cached") > c2
     for a, r in zip(many, ref):
         assert np.array_equal(a, r)
     # ... and with the singular bases instead (`cache_beam_basis`): the solver's own resolution, not bit for bit
     based = MaximumLikelihoodMapMaker(nside=64, pool_bytes=nfreq * per_f + (1 << 20), cache_beam_basis=True)
     based.setup(bt)
-    b0 = counter(b"ml_tiles_basis")
+    b0 = ctx.counter(b"ml_tiles_basis")
     many_b = [a.cpu().numpy() for a in based.make_alm_many(days)]
-    assert counter(b"ml_tiles_basis") > b0 and based._engine.basis_builds == 1
+    assert ctx.counter(b"ml_tiles_basis") > b0 and based._engine.basis_builds == 1
     for a, r in zip(many_b, ref):
         assert np.abs(a - r).max() < 2e-8 * np.abs(r).max()
 
@@ -334,21 +306,13 @@ def test_resident_beam_gram_products_give_bit_identical_days():
 def test_resident_beam_gram_products_for_wiener_too():
     """The Wiener maker's telescope-side systems ``I + D (B S B^H) D`` (mapmaker.py:267-272) from resident products
     ``B S B^H``: bit-identical a_lm on the filling day and after; another prior starts the cache over."""
-    import ctypes as C
-
     import torch
 
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import WienerMapMaker
     from draco_amd.core import containers
 
     nfreq = 2
     ctx, tel, bt, mm, mv, mw, per_f = _setup(nfreq, seed=16)
-
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
 
     gen = torch.Generator(device=ctx.device).manual_seed(7)
     v = torch.randn(mv.shape, dtype=torch.complex128, device=ctx.device, generator=gen)
@@ -363,21 +327,21 @@ def test_resident_beam_gram_products_for_wiener_too():
     ref = [plain.make_alm(d).cpu().numpy() for d in (mm, day2)]
     cached = WienerMapMaker(nside=64, pool_bytes=pool, cache_beam_gram=True)
     cached.setup(bt)
-    c0 = counter(b"ml_gram_cached")
+    c0 = ctx.counter(b"ml_gram_cached")
     a0 = cached.make_alm(mm).cpu().numpy()
-    assert counter(b"ml_gram_cached") == c0
+    assert ctx.counter(b"ml_gram_cached") == c0
     a1 = cached.make_alm(day2).cpu().numpy()
     n_tel = sum(1 for m in range(tel.lmax + 1) if 4 * (tel.lmax + 1 - m) >= 2 * tel.npairs) * nfreq
-    assert counter(b"ml_gram_cached") - c0 == n_tel
+    assert ctx.counter(b"ml_gram_cached") - c0 == n_tel
     assert np.array_equal(a0, ref[0]) and np.array_equal(a1, ref[1])
     # another prior: other products -- the cache starts over, and the answer is that prior's
     other = WienerMapMaker(nside=64, pool_bytes=pool, prior_tilt=1.0)
     other.setup(bt)
     ref_o = other.make_alm(day2).cpu().numpy()
     cached.prior_tilt = 1.0
-    c1 = counter(b"ml_gram_cached")
+    c1 = ctx.counter(b"ml_gram_cached")
     a2 = cached.make_alm(day2).cpu().numpy()
-    assert counter(b"ml_gram_cached") == c1 and np.array_equal(a2, ref_o)
+    assert ctx.counter(b"ml_gram_cached") == c1 and np.array_equal(a2, ref_o)
 
 
 @pytest.mark.parametrize("chan0", [0, 254])
@@ -386,8 +350,6 @@ def test_resident_beam_bases_keep_the_same_modes_and_agree_with_the_oracle_svd(c
     pseudo-inverse (mapmaker.py:190-201, 287-300) is that of the r x r matrix ``Sigma U^H N^-1 U Sigma``.  Against the
     full-order pass on the same structured tiles: the same modes kept on every tile, a_lm within the solver's resolution;
     sampled tiles against the oracle's SVD; a second day (other weights) through the same resident bases."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -398,11 +360,6 @@ def test_resident_beam_bases_keep_the_same_modes_and_agree_with_the_oracle_svd(c
     nfreq = 1
     ctx, tel, bt, mm, mv, mw, per_f = _setup(nfreq, seed=17, chan0=chan0)
     n_m = tel.lmax + 1
-
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
 
     gen = torch.Generator(device=ctx.device).manual_seed(5)
     v2 = torch.randn(mv.shape, dtype=torch.complex128, device=ctx.device, generator=gen)
@@ -430,9 +387,9 @@ def test_resident_beam_bases_keep_the_same_modes_and_agree_with_the_oracle_svd(c
     worst = 0.0
     for day, vh, wh in ((mm, mv, mw), (day2, v2, w2)):
         a_ref, d_ref = run(plain, day)
-        b0 = counter(b"ml_tiles_basis")
+        b0 = ctx.counter(b"ml_tiles_basis")
         a_bs, d_bs = run(based, day)
-        n_bs = counter(b"ml_tiles_basis") - b0
+        n_bs = ctx.counter(b"ml_tiles_basis") - b0
         dec = d_ref[..., 0] >= 0
         n_tel_dec = int(dec[0, : sum(1 for m in range(n_m) if 4 * (n_m - m) >= 2 * tel.npairs)].sum())
         assert n_bs >= 0.9 * n_tel_dec > 0, (n_bs, n_tel_dec)
@@ -459,8 +416,6 @@ def test_resident_beam_bases_small_telescope_where_the_basis_would_meet_the_redu
     (ntel = 566) whose ranks reach ~400 at the top of the band: the chunks whose largest rank lies above 384 must take the
     full-order path (``solve_dense.hip``: the fit check), every tile keeps the modes of the plain pass, a_lm agrees, and the
     tiles of highest rank agree with the oracle's SVD."""
-    import ctypes as C
-
     import torch
 
     from draco_amd import _lib
@@ -483,11 +438,6 @@ def test_resident_beam_bases_small_telescope_where_the_basis_would_meet_the_redu
     mm.attach("vis", mv)
     mm.attach("vis_weight", mw)
     per_f = sum(2 * tel.npairs * 4 * (lmax + 1 - m) for m in range(lmax + 1)) * 16
-
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
 
     def run(task):
         diag = torch.full((1, lmax + 1, 4), -1.0, dtype=torch.float64, device=ctx.device)
@@ -514,9 +464,9 @@ def test_resident_beam_bases_small_telescope_where_the_basis_would_meet_the_redu
     offer = eng._offer_workspace
     eng._offer_workspace = lambda option, cap_mib: offer(option, min(cap_mib, 1024))
     run(based)  # (builds the bases)
-    b0 = counter(b"ml_tiles_basis")
+    b0 = ctx.counter(b"ml_tiles_basis")
     a_bs, d_bs = run(based)
-    n_bs = counter(b"ml_tiles_basis") - b0
+    n_bs = ctx.counter(b"ml_tiles_basis") - b0
     n_tel = sum(1 for m in range(lmax + 1) if 4 * (lmax + 1 - m) >= 2 * tel.npairs and ranks[m] >= 0)
     # the chunks that hold the high-rank tiles keep the full-order path -- without the fit check they took the basis route and
     # the top ranks came out wrong --, the chunks of lower rank take the basis route: the fit check is tested from both sides
@@ -538,11 +488,8 @@ def test_resident_beam_bases_weight_guard_is_taken_per_day():
     the caching allocator normally produces for a new day's tensor; staged here by writing through ``.data``, which does
     not bump the counter), but the non-zero ones span eight decades: the day must take the full-order path
     (``ml_tiles_basis`` does not grow) and agree with the plain maker."""
-    import ctypes as C
-
     import torch
 
-    from draco_amd import _lib
     from draco_amd.analysis.mapmaker import MaximumLikelihoodMapMaker
     from draco_amd.core import containers
     from draco_amd.core.products import BeamScreenProvider, TransitTelescope
@@ -560,11 +507,6 @@ def test_resident_beam_bases_weight_guard_is_taken_per_day():
     g = torch.Generator(device=ctx.device).manual_seed(31)
     w = (torch.rand(shape, dtype=torch.float64, device=ctx.device, generator=g) + 0.5) * 2e4
 
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
-
     def day(task, w):
         mm = containers.MModes(mmax=lmax, freq=tel.frequencies, stack=tel.npairs, allocate=False)
         mm.attach("vis", mv)
@@ -577,14 +519,14 @@ def test_resident_beam_bases_weight_guard_is_taken_per_day():
     based.setup(bt)
     key1 = (w.data_ptr(), w._version)
     day(based, w)  # builds the bases
-    b0 = counter(b"ml_tiles_basis")
+    b0 = ctx.counter(b"ml_tiles_basis")
     day(based, w)
-    assert counter(b"ml_tiles_basis") > b0  # an ordinary day takes the basis route
+    assert ctx.counter(b"ml_tiles_basis") > b0  # an ordinary day takes the basis route
     w.data[..., :3] *= 1e-8
     assert (w.data_ptr(), w._version) == key1
-    b1 = counter(b"ml_tiles_basis")
+    b1 = ctx.counter(b"ml_tiles_basis")
     a2 = day(based, w)
-    assert counter(b"ml_tiles_basis") == b1, "a day whose weights span 1e8 kept the truncated-basis route"
+    assert ctx.counter(b"ml_tiles_basis") == b1, "a day whose weights span 1e8 kept the truncated-basis route"
     plain = MaximumLikelihoodMapMaker(nside=64, pool_bytes=per_f + (1 << 20))
     plain.setup(bt)
     a_ref = day(plain, w)
@@ -623,9 +565,8 @@ def test_stage1_forms_keep_the_same_modes_on_structured_tiles():
     task = MaximumLikelihoodMapMaker(nside=64, pool_bytes=per_f + (1 << 20))
     task.setup(bt)
     out, ranks = {}, {}
-    try:
-        for red in (0, 3, 5, 2):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", red))
+    for red in (0, 3, 5, 2):
+        with ctx.options(ml_reduce=red):
             diag = torch.full((1, lmax + 1, 4), -1.0, dtype=torch.float64, device=ctx.device)
             _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, ptr(diag)))
             try:
@@ -634,18 +575,12 @@ def test_stage1_forms_keep_the_same_modes_on_structured_tiles():
             finally:
                 _lib.check(_lib.lib.dmm_ctx_set_ml_diag(ctx.handle, None))
             ranks[red] = diag.cpu().numpy()[0, :, 0]
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_reduce", 0))
     assert ranks[0].max() > 32  # (tiles that are really decomposed and truncated)
     scale = np.abs(out[2]).max()
     for red in (0, 3, 5):
         assert np.array_equal(ranks[red], ranks[2]), red
         assert np.abs(out[red] - out[2]).max() < 2e-8 * scale, (red, np.abs(out[red] - out[2]).max() / scale)
-    import ctypes
-
-    v = ctypes.c_int64()
-    _lib.check(_lib.lib.dmm_ctx_get_counter(ctx.handle, b"build_ab", ctypes.byref(v)))
-    if not v.value:
+    if not ctx.counter(b"build_ab"):
         assert np.array_equal(out[5], out[0])
     m = int(np.argmax(ranks[0]))
     ref, rank_o, _ = omm.ml_solve_with_spectrum(bt.beam_m(m, fi=0), mv.cpu().numpy()[m, :, 0], mw.cpu().numpy()[m, :, 0])

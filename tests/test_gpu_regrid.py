@@ -269,7 +269,6 @@ def test_chain_regrid_to_dirty_map():
 def test_row_chunks_give_the_same_result():
     """The factor rows go through a scratch sized by the `regrid_workspace_mib` option; with 1 MiB every wave of 64
     rows is a chunk (launch) of its own, and the result is bit for bit the one-chunk result."""
-    from draco_amd import _lib
     from draco_amd.device import Context
 
     rng = np.random.default_rng(21)
@@ -279,9 +278,6 @@ def test_row_chunks_give_the_same_result():
     w = rng.uniform(0.0, 2.0, (nrow, nt)).astype(np.float32)
     _, x0, nw0 = _regrid(vis, w, times, samples, 0.0, 1.0, 5)
     ctx = Context.get()
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"regrid_workspace_mib", 1))
-    try:
+    with ctx.options(regrid_workspace_mib=1):
         _, x1, nw1 = _regrid(vis, w, times, samples, 0.0, 1.0, 5)
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"regrid_workspace_mib", 0))
     assert np.array_equal(x0, x1) and np.array_equal(nw0, nw1) and np.abs(x0[-1]).max() > 0

@@ -238,9 +238,8 @@ def _single_pass_against_three_kernels(nm, nel, new, npol, nfreq):
     eps = ctx.to_device(np.full((nfreq, nm), 1e-2), np.float64)
     win = torch.rand((nfreq, nm, nel), dtype=torch.float32, device=ctx.device, generator=gen)
     out = {}
-    try:
-        for variant in (0, 1, 2):  # 0: single pass, 16 elevations per block; 2: single pass, 8 per block; 1: three kernels
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ringmap_variant", variant))
+    for variant in (0, 1, 2):  # 0: single pass, 16 elevations per block; 2: single pass, 8 per block; 1: three kernels
+        with ctx.options(ringmap_variant=variant):
             for mode in (0, 1, 2):
                 rmap = ctx.zeros((1, npol, nfreq, nra, nel), np.float64)
                 rwgt = ctx.zeros((npol, nfreq, nra, nel), np.float64)
@@ -248,8 +247,6 @@ def _single_pass_against_three_kernels(nm, nel, new, npol, nfreq):
                 _lib.check(_lib.lib.dmm_ringmap_deconvolve(ctx.handle, nm, nm, npol, nfreq, new, nel, nra, mode, 0, 0, ptr(hv), ptr(hw), ptr(bv),
                                                            ptr(table), ptr(eps), ptr(win), ptr(rmap), ptr(rwgt), ptr(rdbp), None))
                 out[variant, mode] = [x.cpu().numpy() for x in (rmap, rwgt, rdbp)]
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ringmap_variant", 0))
     for mode in (0, 1, 2):
         for v in (0, 2):
             for a, b in zip(out[v, mode], out[1, mode]):

@@ -119,18 +119,14 @@ def test_ring_fft_vs_direct_sums(nside, lmax, npol):
     Covers every Bluestein class (M = 256 ... 2048 at nside 256), rings shorter than mmax
     (folding modulo nphi) and both transforms; both evaluate the same sums, so 1e-12.
     """
-    from draco_amd import _lib
     from draco_amd.device import Context
 
     ctx = Context.get()
     rng = np.random.default_rng(nside)
     alm = _rand_alm(rng, 2, npol, lmax)
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 4))
+    with ctx.options(sht_variant=4):
         m_direct = _alm2map_gpu(alm, nside)
         a_direct = _map2alm_gpu(m_direct, lmax, lmax, 0)
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     m_fft = _alm2map_gpu(alm, nside)
     a_fft = _map2alm_gpu(m_direct, lmax, lmax, 0)
     assert np.abs(m_fft - m_direct).max() < 1e-12 * np.abs(m_direct).max()
@@ -143,19 +139,15 @@ def test_legendre_synthesis_kernels_agree(nside, lmax, nf):
     kernel with 4 or 8 frequencies per block) evaluate the same sums -- 1e-12 of the map's scale apart (the pipelined form
     builds F1 / F2 with another association and reads lambda_{l-1} as 0 at the step a ring's scale reaches 1: < 2^-60 of
     the ring's values) -- with ragged frequency groups, chunks and ring tiles."""
-    from draco_amd import _lib
     from draco_amd.device import Context
 
     ctx = Context.get()
     rng = np.random.default_rng(nside + nf)
     alm = _rand_alm(rng, nf, 4, lmax)
     maps = {}
-    try:
-        for variant in (0, 128, 64):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+    for variant in (0, 128, 64):
+        with ctx.options(sht_variant=variant):
             maps[variant] = _alm2map_gpu(alm, nside)
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     ref = maps[64]
     scale = np.abs(ref).max()
     for variant in (0, 128, 64):
@@ -172,7 +164,6 @@ def test_legendre_analysis_kernels_agree(nside, lmax, nf):
     frequency group and lmax + 1 - m ragged against the 32-step chunk (also pinned to the oracle); 256 ring pairs, exactly
     one pass, with the rescaling path at high m near the poles; 512 pairs, two passes (the second adds into the a_lm of
     the first).  Entries l < m must be exact zeros in both forms."""
-    from draco_amd import _lib
     from draco_amd.device import Context
 
     ctx = Context.get()
@@ -181,12 +172,9 @@ def test_legendre_analysis_kernels_agree(nside, lmax, nf):
     upper = np.triu(np.ones((lmax + 1, lmax + 1), bool), 1)  # [l, m] with l < m
     for niter in (0, 1):
         alm = {}
-        try:
-            for variant in (0, 8):
-                _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+        for variant in (0, 8):
+            with ctx.options(sht_variant=variant):
                 alm[variant] = _map2alm_gpu(maps, lmax, lmax, niter)
-        finally:
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
         scale = np.abs(alm[8]).max()
         diff = np.abs(alm[0] - alm[8]).max() / scale
         print(f"legendre analysis forms nside={nside} lmax={lmax} nf={nf} niter={niter}: {diff:.3e} of max|alm|")

@@ -97,11 +97,8 @@ def _alm2map(c, alm=None, variant=0, ctx=None, whole=False):
     ctx = _ctx(ctx)
     a_dev = ctx.to_device(c.alm if alm is None else alm, np.complex128)
     out = _nan(ctx, (c.nf, c.npol, 12 * c.nside * c.nside), np.float64)
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+    with ctx.options(sht_variant=variant):
         _lib.check(_lib.lib.dmm_alm2map(ctx.handle, ptr(a_dev), c.nf, c.npol, c.lmax, c.mmax, c.nside, ptr(out)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     ctx.sync()
     if whole:
         return out.cpu().numpy()
@@ -120,11 +117,8 @@ def _map2alm(c, niter, maps=None, variant=0, ctx=None, nan_ok=False):
     m_dev = ctx.zeros((c.nf, c.npol, 12 * c.nside * c.nside), np.float64)
     m_dev[:, :, torch.from_numpy(c.pix).to(m_dev.device)] = ctx.to_device(c.maps if maps is None else maps, np.float64)
     out = _nan(ctx, (c.nf, c.npol, c.mmax + 1, c.lmax + 1), np.complex128)
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+    with ctx.options(sht_variant=variant):
         _lib.check(_lib.lib.dmm_map2alm(ctx.handle, ptr(m_dev), c.nf, c.npol, c.lmax, c.mmax, c.nside, niter, ptr(out)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     ctx.sync()
     assert nan_ok or bool(torch.isfinite(torch.view_as_real(out)).all()), "a_lm is not finite everywhere"
     return out.cpu().numpy()

@@ -35,11 +35,8 @@ def _alm2map(ctx, a_dev, nfreq, lmax, nside, variant):
     from draco_amd.device import ptr
 
     out = ctx.empty((nfreq, 4, 12 * nside * nside), np.float64)
-    try:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", variant))
+    with ctx.options(sht_variant=variant):
         _lib.check(_lib.lib.dmm_alm2map(ctx.handle, ptr(a_dev), nfreq, 4, lmax, lmax, nside, ptr(out)))
-    finally:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"sht_variant", 0))
     return out.cpu().numpy()
 
 

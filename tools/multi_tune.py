@@ -56,20 +56,17 @@ def main():
 
     for variant in ((0,) if c64 else (0, 1, 2, 3, 4)):
         for gm in ((1,) if c64 else (1, 2)):
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"dirty_variant", variant))
-            _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"grid_mult", gm))
-            for D in (1, 2, 4, 8):
-                if variant and D == 1:
-                    continue
-                if gm == 2 and D == 8:
-                    continue  # (two blocks of 97 KB do not fit a CU's LDS)
-                ms_ = run(D)
-                row = {"variant": variant, "grid_mult": gm, "D": D, "ms": ms_, "ms_per_day": ms_ / D, "hbm_frac": slab.b_bytes / ms_ / 1e6 / 8000.0,
-                       "f64_frac": 8.0 * D * slab.b_bytes / (8 if c64 else 16) / ms_ / 1e9 / 78.6}
-                out["rows"].append(row)
-                print(json.dumps(row), file=sys.stderr, flush=True)
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"dirty_variant", 0))
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"grid_mult", 0))
+            with ctx.options(dirty_variant=variant, grid_mult=gm):
+                for D in (1, 2, 4, 8):
+                    if variant and D == 1:
+                        continue
+                    if gm == 2 and D == 8:
+                        continue  # (two blocks of 97 KB do not fit a CU's LDS)
+                    ms_ = run(D)
+                    row = {"variant": variant, "grid_mult": gm, "D": D, "ms": ms_, "ms_per_day": ms_ / D, "hbm_frac": slab.b_bytes / ms_ / 1e6 / 8000.0,
+                           "f64_frac": 8.0 * D * slab.b_bytes / (8 if c64 else 16) / ms_ / 1e9 / 78.6}
+                    out["rows"].append(row)
+                    print(json.dumps(row), file=sys.stderr, flush=True)
     print(json.dumps(out))
 
 

@@ -31,15 +31,14 @@ def main():
     eng.project(alm, list(range(nf)), lmax)
     ctx.sync()
     for var, gm in [(v, g) for v in (0, 5) for g in (1, 2, 3)]:  # 4 = the row-per-wave form shipped before; 0 = row groups of 8
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"project_grid_mult", gm))
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"project_variant", var))
-        ts = []
-        for _ in range(4):
-            ctx.timer_start()
-            eng.project(alm, list(range(nf)), lmax)
-            ts.append(ctx.timer_stop())
-        t = float(np.median(ts[1:]))
-        print(json.dumps({"config": cfgn, "nfreq": nf, "variant": var, "grid_mult": gm, "ms": t, "B_GB": eng.last_b_bytes / 1e9, "TBs": eng.last_b_bytes / t / 1e9}))
+        with ctx.options(project_grid_mult=gm, project_variant=var):
+            ts = []
+            for _ in range(4):
+                ctx.timer_start()
+                eng.project(alm, list(range(nf)), lmax)
+                ts.append(ctx.timer_stop())
+            t = float(np.median(ts[1:]))
+            print(json.dumps({"config": cfgn, "nfreq": nf, "variant": var, "grid_mult": gm, "ms": t, "B_GB": eng.last_b_bytes / 1e9, "TBs": eng.last_b_bytes / t / 1e9}))
 
 
 if __name__ == "__main__":

@@ -11,7 +11,6 @@ rank's frequencies -- a PROJECTION (no collective inside the timed region; RCCL 
     python tools/rank_share.py [--timed-freqs 8] [--pool 4] > gpurun_out/rank_share.json
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -46,11 +45,6 @@ def main():
     lib = _lib.lib
     HBM = 8000.0  # GB/s (guide)
     FP64 = 78.6e12
-
-    def counter(name):
-        v = C.c_int64()
-        _lib.check(lib.dmm_ctx_get_counter(ctx.handle, name, C.byref(v)))
-        return int(v.value)
 
     def wall(fn, reps=2):
         ts = []
@@ -125,10 +119,9 @@ def main():
             wm = WienerMapMaker(nside=nside, pool_bytes=pool_bytes)
             wm.setup(bt)
             wm.process(mm)
-            _lib.check(lib.dmm_ctx_set_option(ctx.handle, b"profile", 1))
-            _, t_w = wall(lambda: wm.process(mm), reps=1)
-            span_ms = counter(b"prof_solve_us") / 1e3
-            _lib.check(lib.dmm_ctx_set_option(ctx.handle, b"profile", 0))
+            with ctx.options(profile=1):
+                _, t_w = wall(lambda: wm.process(mm), reps=1)
+                span_ms = ctx.counter(b"prof_solve_us") / 1e3
             ntel = 2 * tel.npairs
             flops = 0.0
             for m in range(lmax + 1):  # Hermitian half of the smaller Gram matrix + Cholesky

@@ -168,42 +168,41 @@ def main():
     from draco_amd.util import regrid
 
     ctx = Context.get()
-    if args.workspace_mib:
-        _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"regrid_workspace_mib", args.workspace_mib))
-    rng = np.random.default_rng(1)
-    gen = torch.Generator(device=ctx.device).manual_seed(1)
-    kw, pad = 5, 25
-    grid = np.arange(-pad, args.samples + pad, dtype=np.float64) / args.samples
-    for nt in args.nt:
-        t = np.sort(np.linspace(-0.005, 1.005, nt) + rng.uniform(-0.4, 0.4, nt) * 1.01 / nt)
-        t = t[((t < 0.31) | (t > 0.33)) & ((t < 0.70) | (t > 0.705))]
-        n = len(t)
-        vis = torch.randn((args.rows, n, 2), dtype=torch.float32, device=ctx.device, generator=gen)
-        vis = torch.view_as_complex(vis)
-        w = torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
-        w *= torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) > 0.2
-        plan = regrid.RegridPlan(ctx, grid, t, kw)
-        ms = windows(ctx, lambda: regrid.band_wiener(ctx, plan, vis, w, 1e-3, pad, args.samples), args.windows, args.reps)
-        nbytes = args.rows * 12 * (n + args.samples)
-        med = float(np.median(ms))
-        print(json.dumps({"case": "regrid", "rows": args.rows, "nt": n, "samples": args.samples, "ms": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
-                          "GBps": round(nbytes / med / 1e6, 1), "frac_peak": round(nbytes / med * 1e3 / PEAK, 4), "hbm_floor_ms": round(nbytes / PEAK * 1e3, 3)}), flush=True)
-        ctx.sync()
-        plan.close()
-        del vis, w
-    # one stacker update (inverse variance, with sample variance)
-    n = args.rows * args.samples
-    dv = torch.view_as_complex(torch.randn((n, 2), dtype=torch.float32, device=ctx.device, generator=gen))
-    dw = torch.rand(n, dtype=torch.float32, device=ctx.device, generator=gen)
-    sv, sw, ns = ctx.zeros((n,), np.complex64), ctx.zeros((n,), np.float32), ctx.zeros((n,), np.int16)
-    sq, var = ctx.zeros((n,), np.float32), ctx.zeros((3, n), np.float32)
-    for with_var in (0, 1):
-        fn = lambda: _lib.check(_lib.lib.dmm_sidereal_stack_add(ctx.handle, 1, with_var, ptr(dv), ptr(dw), None, ptr(sv), ptr(sw), ptr(ns), ptr(sq), ptr(var), n))  # noqa: E731
-        ms = windows(ctx, fn, args.windows, 4)
-        nbytes = n * (12 + 2 * 14 + (2 * 16 if with_var else 0))
-        med = float(np.median(ms))
-        print(json.dumps({"case": "stack_add", "with_variance": with_var, "elements": n, "ms": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
-                          "GBps": round(nbytes / med / 1e6, 1), "frac_peak": round(nbytes / med * 1e3 / PEAK, 4)}), flush=True)
+    with ctx.options(regrid_workspace_mib=args.workspace_mib):
+        rng = np.random.default_rng(1)
+        gen = torch.Generator(device=ctx.device).manual_seed(1)
+        kw, pad = 5, 25
+        grid = np.arange(-pad, args.samples + pad, dtype=np.float64) / args.samples
+        for nt in args.nt:
+            t = np.sort(np.linspace(-0.005, 1.005, nt) + rng.uniform(-0.4, 0.4, nt) * 1.01 / nt)
+            t = t[((t < 0.31) | (t > 0.33)) & ((t < 0.70) | (t > 0.705))]
+            n = len(t)
+            vis = torch.randn((args.rows, n, 2), dtype=torch.float32, device=ctx.device, generator=gen)
+            vis = torch.view_as_complex(vis)
+            w = torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
+            w *= torch.rand((args.rows, n), dtype=torch.float32, device=ctx.device, generator=gen) > 0.2
+            plan = regrid.RegridPlan(ctx, grid, t, kw)
+            ms = windows(ctx, lambda: regrid.band_wiener(ctx, plan, vis, w, 1e-3, pad, args.samples), args.windows, args.reps)
+            nbytes = args.rows * 12 * (n + args.samples)
+            med = float(np.median(ms))
+            print(json.dumps({"case": "regrid", "rows": args.rows, "nt": n, "samples": args.samples, "ms": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                              "GBps": round(nbytes / med / 1e6, 1), "frac_peak": round(nbytes / med * 1e3 / PEAK, 4), "hbm_floor_ms": round(nbytes / PEAK * 1e3, 3)}), flush=True)
+            ctx.sync()
+            plan.close()
+            del vis, w
+        # one stacker update (inverse variance, with sample variance)
+        n = args.rows * args.samples
+        dv = torch.view_as_complex(torch.randn((n, 2), dtype=torch.float32, device=ctx.device, generator=gen))
+        dw = torch.rand(n, dtype=torch.float32, device=ctx.device, generator=gen)
+        sv, sw, ns = ctx.zeros((n,), np.complex64), ctx.zeros((n,), np.float32), ctx.zeros((n,), np.int16)
+        sq, var = ctx.zeros((n,), np.float32), ctx.zeros((3, n), np.float32)
+        for with_var in (0, 1):
+            fn = lambda: _lib.check(_lib.lib.dmm_sidereal_stack_add(ctx.handle, 1, with_var, ptr(dv), ptr(dw), None, ptr(sv), ptr(sw), ptr(ns), ptr(sq), ptr(var), n))  # noqa: E731
+            ms = windows(ctx, fn, args.windows, 4)
+            nbytes = n * (12 + 2 * 14 + (2 * 16 if with_var else 0))
+            med = float(np.median(ms))
+            print(json.dumps({"case": "stack_add", "with_variance": with_var, "elements": n, "ms": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                              "GBps": round(nbytes / med / 1e6, 1), "frac_peak": round(nbytes / med * 1e3 / PEAK, 4)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 
     python tools/step_ab.py [complex128|complex64] [variants=0,7] [rounds=5] [option=dirty_variant]
 
-    `option` is any dmm_ctx_set_option name (dirty_variant, grid_mult ...); `variants` its values.
+    `option` is any context option (dirty_variant, grid_mult ...); `variants` its values.
 """
 import json
 import os
@@ -19,13 +19,12 @@ def main():
     import torch
 
     import bench
-    from draco_amd import _lib
     from draco_amd import workloads as wl
 
     dtype = sys.argv[1] if len(sys.argv) > 1 else "complex128"
     variants = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "0,7").split(",")]
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-    option = (sys.argv[4] if len(sys.argv) > 4 else "dirty_variant").encode()
+    option = sys.argv[4] if len(sys.argv) > 4 else "dirty_variant"
     job = bench.Job(wl.CONFIGS[3], 0, 1, "weak", dtype, 0)
     job.step()
     torch.cuda.synchronize()
@@ -34,18 +33,18 @@ def main():
     res = {v: {"step_ms": [], "launch_in_step_ms": [], "launch_alone_ms": []} for v in variants}
     for _ in range(rounds):
         for v in variants:
-            _lib.check(_lib.lib.dmm_ctx_set_option(job.ctx.handle, option, v))
-            ms, n = job.timed_launches(job.to_alm)
-            res[v]["launch_alone_ms"].append(ms)
-            eng = job.dm._get_engine()
-            eng.launch_events = []
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            job.step()
-            torch.cuda.synchronize()
-            res[v]["step_ms"].append((time.perf_counter() - t0) * 1e3)
-            res[v]["launch_in_step_ms"].append(float(np.mean([a.elapsed_time(b) for a, b, _, _ in eng.launch_events])))
-            eng.launch_events = None
+            with job.ctx.options(**{option: v}):
+                ms, n = job.timed_launches(job.to_alm)
+                res[v]["launch_alone_ms"].append(ms)
+                eng = job.dm._get_engine()
+                eng.launch_events = []
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                job.step()
+                torch.cuda.synchronize()
+                res[v]["step_ms"].append((time.perf_counter() - t0) * 1e3)
+                res[v]["launch_in_step_ms"].append(float(np.mean([a.elapsed_time(b) for a, b, _, _ in eng.launch_events])))
+                eng.launch_events = None
     for v in variants:
         r = {k: float(np.median(x)) for k, x in res[v].items()}
         r["variant"] = v

@@ -50,14 +50,12 @@ def main():
     times = {k: [] for k in combos}
     for rnd in range(7):
         for v, g, st in combos:
-            _lib.check(lib.dmm_ctx_set_option(ctx.handle, b"dirty_variant", v))
-            _lib.check(lib.dmm_ctx_set_option(ctx.handle, b"grid_mult", g))
-            _lib.check(lib.dmm_ctx_set_option(ctx.handle, b"dirty_static", st))
-            eng.launch_events = []
-            dm.make_alm(mm)
-            torch.cuda.synchronize()
-            times[(v, g, st)].append(sum(a.elapsed_time(b) for a, b, _, _ in eng.launch_events))
-            eng.launch_events = None
+            with ctx.options(dirty_variant=v, grid_mult=g, dirty_static=st):
+                eng.launch_events = []
+                dm.make_alm(mm)
+                torch.cuda.synchronize()
+                times[(v, g, st)].append(sum(a.elapsed_time(b) for a, b, _, _ in eng.launch_events))
+                eng.launch_events = None
     res = []
     for (v, g, st), ts in times.items():
         ts = np.array(ts[1:])

@@ -31,14 +31,14 @@ def main():
     vis = torch.randn((nf, tel.npairs, cfg["nra"]), dtype=torch.complex64, device=ctx.device, generator=gen)
     w = torch.rand((nf, tel.npairs, cfg["nra"]), dtype=torch.float32, device=ctx.device, generator=gen) + 0.5
     mv, mw = mmode_forward(ctx, vis, w, cfg["lmax"])
-    _lib.check(_lib.lib.dmm_ctx_set_option(ctx.handle, b"ml_shortcut", side))
-    for _ in range(2):
-        ctx.sync()
-        t0 = time.perf_counter()
-        eng.solve(kind, mv, mw, list(range(nf)), cfg["lmax"], prior_amp=1.0, prior_tilt=0.5)
-        ctx.sync()
-        dt = time.perf_counter() - t0
-    print(f"{kind} cfg{cfgn} nf={nf}: {dt*1e3:.1f} ms, {dt*1e3/(nf*(cfg['lmax']+1)):.4f} ms per solve")
+    with ctx.options(ml_shortcut=side):
+        for _ in range(2):
+            ctx.sync()
+            t0 = time.perf_counter()
+            eng.solve(kind, mv, mw, list(range(nf)), cfg["lmax"], prior_amp=1.0, prior_tilt=0.5)
+            ctx.sync()
+            dt = time.perf_counter() - t0
+        print(f"{kind} cfg{cfgn} nf={nf}: {dt*1e3:.1f} ms, {dt*1e3/(nf*(cfg['lmax']+1)):.4f} ms per solve")
 
 
 if __name__ == "__main__":
