@@ -47,6 +47,7 @@ DMM_PS_MAX_BINS = 4096
 DMM_STACK_SRC_CHUNK, DMM_STACK_MAX_FREQ = 256, 2048
 DMM_STACK3D_INPUT, DMM_STACK3D_DEC, DMM_STACK3D_PATCH = 0, 1, 2
 DMM_WD_MAX_FREQ = 1024
+DMM_NRML_MAX_CHAN, DMM_NRML_MAX_DELAY = 1024, 2048
 
 
 class DmmError(RuntimeError):
@@ -71,6 +72,10 @@ class dmm_dayenu_side(C.Structure):
 
 class dmm_delay_view(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("stride_sample", C.c_int64), ("stride_freq", C.c_int64), ("stride_fold", C.c_int64 * 4)]
+
+
+class dmm_nrml_ws(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("chan", "tw", "wv", "Nm", "Xe", "nsv", "Ci", "S", "sh", "G", "D", "U", "Y", "R", "t", "cix", "PQ")]
 
 
 if not os.path.exists(LIB_PATH):
@@ -152,6 +157,10 @@ _SIGS = {
     "dmm_delay_project": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_delay_solve": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_delay_store": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_nrml_start": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 15),
+    "dmm_nrml_eval": (_i, [_vp, _i, _i, _i, C.POINTER(dmm_nrml_ws), _vp, _d, _d, _vp, _vp, _vp]),
+    "dmm_nrml_hessian": (_i, [_vp, _i, _i, _i, C.POINTER(dmm_nrml_ws), _i, _vp, _vp]),
+    "dmm_nrml_direction": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_mfilter_mask": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "dmm_mfilter_cov": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_mfilter_pack": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -6,6 +6,7 @@ Drop-in for the frequency-to-delay transforms of ``draco/analysis/delay.py``:
 * :func:`fourier_matrix_r2c`, :func:`fourier_matrix_c2r`, :func:`fourier_matrix_c2c`, :func:`fourier_matrix`   ``delay.py:1480-1613``
 * :class:`DelaySpectrumFFT`, :class:`DelaySpectrumWienerFilter`, :class:`DelaySpectrumWienerFilterIteratePS`   ``delay.py:347-1053``
 * :class:`DelaySpectrumToPowerSpectrum`                                                  ``delay.py:1061-1106``
+* :class:`DelayPowerSpectrumBase`, :class:`DelayPowerSpectrumNRML`                        ``delay.py:744-818, 1114-1215, 1270-1301``
 
 Same names, config attributes, defaults and ``setup`` / ``process`` signatures.  The arithmetic runs in
 ``libdraco_amd.so`` (``csrc/delay.hip``), batched over baselines: a prepare pass (the ``time_frac`` / ``freq_frac``
@@ -22,8 +23,9 @@ may be 1 ... 2048.
 The transform needs the whole band in one process: frequency sharding does not apply to these tasks.
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``use_average_weights=False`` (the reference's
-Wiener function cannot take per-sample weights either) and ``scale_freq=True``; not provided: the Gibbs, NRML and
-cross-spectrum estimators and ``DelayFilter`` / ``DelayFilterBase``.  (The ``DelayTransformOperator`` container and the
+Wiener function cannot take per-sample weights either) and ``scale_freq=True``; not provided: the Gibbs and
+cross-spectrum estimators and ``DelayFilter`` / ``DelayFilterBase``.  The NRML estimator's optimiser and evaluators are in
+:mod:`draco_amd.analysis.delayopt`.  (The ``DelayTransformOperator`` container and the
 Wiener delay transform of a filtered ring map that fills it are in ``draco_amd.analysis.powerspec``.)
 """
 
@@ -498,6 +500,155 @@ class DelaySpectrumWienerFilterIteratePS(DelaySpectrumWienerFilter):
         return super().process(ss)
 
 
+def nrml_evaluators(ctx, data_v, weight_v, fold_n, nbase, nsample, channel_ind, ndelay, window, *, remove_mean, time_frac, freq_frac, weight_boost, workspace_mib=1024):
+    """The NRML problem of ``nbase`` baselines in batches: yields ``(b0, evaluator)``, a
+    :class:`~draco_amd.analysis.delayopt.DeviceEvaluator` over the baselines ``b0 ...`` whose model and starting spectrum
+    ``S0`` come from the prepare pass (the cuts, the means, the averaged weights) on the device.  ``window``: a name or
+    ``None``; it is evaluated at ``channel_ind / ndelay``."""
+    from .delayopt import MAX_CHAN, MAX_DELAY, DeviceEvaluator, matern_prior
+
+    nchan = int(len(channel_ind))
+    if not (1 <= nchan <= MAX_CHAN and 1 <= ndelay <= MAX_DELAY):
+        raise ValueError(f"NRML: {nchan} channels and {ndelay} delays, the kernels take at most {MAX_CHAN} and {MAX_DELAY}")
+    if nsample > 65535:
+        raise ValueError(f"NRML: {nsample} samples, the kernels take at most 65535")
+    chan = np.ascontiguousarray(channel_ind, dtype=np.int32)
+    chan_d = ctx.to_device(chan)
+    ones_d = ctx.to_device(np.ones(nchan, dtype=np.float64))
+    Ci_d = ctx.to_device(matern_prior(ndelay))  # one inversion and one upload for all batches
+    win = _window_coef(np.asarray(channel_ind) / ndelay, window)
+    fold = (C.c_int64 * max(1, len(fold_n)))(*[int(x) for x in fold_n])
+    per = max(1, min(65535, (int(workspace_mib) << 20) // DeviceEvaluator.bytes_per_baseline(ndelay, nchan, nsample)))
+    for b0 in range(0, nbase, per):
+        nb = min(per, nbase - b0)
+        Xp = ctx.empty((nb, nsample + 1, 2 * nchan), np.float64)
+        nzt = ctx.empty((nb, nsample), np.uint8)
+        status = ctx.empty((nb,), np.int32)
+        Xd = ctx.empty((nb, nsample, 2 * nchan), np.float64)
+        nzt_d, status_d = ctx.empty((nb, nsample), np.uint8), ctx.empty((nb,), np.int32)
+        # (the complex time domain and a unit coefficient, twice: with wiener = 1 the last row of Xp is twice the averaged
+        # weight and status is the skip word; with wiener = 0 the rows of Xd are the mean-removed data themselves, and
+        # its status, which also reports cut channels, is not used)
+        for wiener, X, t, st in ((1, Xp, nzt, status), (0, Xd, nzt_d, status_d)):
+            _lib.check(
+                _lib.lib.dmm_delay_prepare(
+                    ctx.handle, ndelay, nchan, nsample, nb, b0, len(fold_n), fold, C.byref(data_v), C.byref(weight_v), 1, wiener, int(bool(remove_mean)), float(time_frac), float(freq_frac),
+                    float(weight_boost), ptr(ones_d), ptr(chan_d), ptr(X), ptr(t), ptr(st),
+                )
+            )
+        ev = DeviceEvaluator.from_prepared(ctx, ndelay, chan, win, Xp, Xd, nzt, status, Ci=Ci_d)
+        ctx.uses(Xp, Xd, nzt, status, nzt_d, status_d)
+        yield b0, ev
+    ctx.uses(chan_d, ones_d, Ci_d)
+
+
+class DelayPowerSpectrumBase(DelayTransformBase):
+    """What the delay power spectrum estimators share (``delay.py:744-818``, ``1114-1215``): the output container, a
+    :class:`~draco_amd.core.containers.DelaySpectrum`.
+
+    Attributes
+    ----------
+    nsamp : int
+        The number of samples to compute for each power spectrum.  Default 1.
+    save_samples : bool
+        Add ``spectrum_samples [sample, baseline, delay]``, every sample of the chain.  Default False.
+    save_spectrum_mask : bool
+        Add ``spectrum_mask [baseline]``, set where a baseline was skipped or the estimator did not succeed.
+        Default False.
+    """
+
+    _config_names = DelayTransformBase._config_names + ("nsamp", "save_samples")
+    nsamp = 1
+    save_samples = False
+
+    def _create_output(self, ss, delays, coord_axes):
+        """The baseline axis is the folded axis's own index map when one axis is folded, otherwise a count."""
+        if isinstance(coord_axes, np.ndarray):
+            bl = coord_axes
+        elif len(coord_axes) == 1:
+            bl = ss.index_map[coord_axes[0]]
+        else:
+            bl = int(np.prod([len(ss.index_map[ax]) for ax in coord_axes]))
+        out = containers.DelaySpectrum(baseline=bl, delay=delays, sample=self.nsamp, attrs_from=ss, allocate=False)
+        if isinstance(coord_axes, list):
+            for ax in coord_axes:
+                out.create_index_map(ax, ss.index_map[ax])
+            out.attrs["baseline_axes"] = coord_axes
+        out.attrs["freq"] = np.asarray(ss.freq)
+        return out
+
+
+class DelayPowerSpectrumNRML(DelayPowerSpectrumBase):
+    """Estimate the delay power spectrum by NRML (``delay.py:1270-1301``): per baseline the maximum a posteriori of a
+    Gaussian likelihood in ``log S`` under a Matern Gaussian-process prior, found by scipy's Newton-CG algorithm run
+    for all baselines of a batch in lock step with every evaluation on the GPU
+    (:mod:`draco_amd.analysis.delayopt`).
+
+    Attributes
+    ----------
+    nsamp : int
+        The cap on the number of iterations (and the length of the ``sample`` axis).
+    maxpost_tol : float
+        The convergence tolerance of the optimiser (its ``xtol``).  Default 1e-3; below it the reference's own iterates
+        are decided by rounding in the line search.
+
+    ``spectrum [baseline, delay]`` (on the device) is ``fftshift`` of the last iterate; ``spectrum_samples[-k:, b]``
+    holds the ``k`` iterates of baseline ``b``, the start first, not shifted, zeros before them; ``spectrum_mask[b]``
+    is set where the baseline was skipped by the cuts or the optimiser did not succeed (a covariance that is not
+    positive definite included: nothing is raised).  A baseline that runs to the cap has ``nsamp + 1`` iterates: the
+    reference would assign them into ``nsamp`` slots and raise; here the last ``nsamp`` are kept.
+    ``complex_timedomain`` acts through the delay grid only, as in the reference.
+    """
+
+    _config_names = DelayPowerSpectrumBase._config_names + ("maxpost_tol",)
+    maxpost_tol = 1e-3
+
+    def process(self, ss):
+        from .delayopt import newton_cg
+
+        self._check()
+        delays, channel_ind = self._calculate_delays(ss)
+        ndelay = len(delays)
+        ss.redistribute("freq")
+        name, axes, waxes, fold = self._resolve(ss)
+        fold_n = [len(ss.index_map[ax]) for ax in fold]
+        nbase = int(np.prod(fold_n)) if fold_n else 1
+        nsample = len(ss.index_map[self.sample_axis])
+        ctx = Context.get()
+        data, weight, data_v, weight_v, fold_n = self._prepare_inputs(ss, ctx, name, axes, waxes, fold)
+        out = self._create_output(ss, delays, fold)
+        spectrum = np.zeros((nbase, ndelay))
+        samples = np.zeros((self.nsamp, nbase, ndelay)) if self.save_samples else None
+        mask = np.zeros(nbase, dtype=bool)
+        batches = nrml_evaluators(ctx, data_v, weight_v, fold_n, nbase, nsample, channel_ind, ndelay, self.window if self.apply_window else None, remove_mean=self.remove_mean,
+                                  time_frac=self.time_frac, freq_frac=self.freq_frac, weight_boost=self.weight_boost, workspace_mib=self.workspace_mib)
+        for b0, ev in batches:
+            live = ev.base == 0
+            mask[b0 : b0 + ev.nb] = ~live
+            if not live.any():
+                continue
+            with np.errstate(divide="ignore"):
+                x0 = np.where(live[:, None], np.log(ev.S0.cpu().numpy()), 0.0)
+            for i, r in enumerate(newton_cg(ev, x0, maxiter=self.nsamp, xtol=self.maxpost_tol, active=live)):
+                if not live[i]:
+                    continue
+                its = np.exp(np.array(r["x"]))
+                spectrum[b0 + i] = np.fft.fftshift(its[-1])
+                mask[b0 + i] = not r["success"]
+                if samples is not None:
+                    keep = its[-self.nsamp :]
+                    samples[-len(keep) :, b0 + i] = keep
+        ctx.uses(data, weight)
+        out.attach("spectrum", ctx.to_device(spectrum))
+        if samples is not None:
+            out.add_dataset("spectrum_samples", allocate=False)
+            out.datasets["spectrum_samples"] = containers.Dataset(host=samples, attrs={"axis": ["sample", "baseline", "delay"]})
+        if self.save_spectrum_mask:
+            out.add_dataset("spectrum_mask", allocate=False)
+            out.datasets["spectrum_mask"] = containers.Dataset(host=mask, attrs={"axis": ["baseline"]})
+        return out
+
+
 class DelaySpectrumToPowerSpectrum(ContainerTask):
     """Compute a delay power spectrum from a delay spectrum (``delay.py:1061-1106``): the variance over the sample
     axis, restricted to the unmasked samples.  A baseline with every sample masked gives zero and is flagged in the
@@ -525,6 +676,8 @@ class DelaySpectrumToPowerSpectrum(ContainerTask):
 
 
 __all__ = [
+    "DelayPowerSpectrumBase",
+    "DelayPowerSpectrumNRML",
     "DelaySpectrumFFT",
     "DelaySpectrumToPowerSpectrum",
     "DelaySpectrumWienerFilter",

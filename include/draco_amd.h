@@ -619,6 +619,47 @@ int dmm_delay_solve(dmm_ctx* ctx, int order, int complex_td, int nsample, int nb
 int dmm_delay_store(dmm_ctx* ctx, int ndelay, int complex_td, int nsample, int nrow, int nbase, const double* Y, const uint8_t* nzt,
                     const int32_t* status, void* spectrum, uint8_t* mask);
 
+/* Delay power spectrum by NRML (draco/analysis/delayopt.py:61-355, delay.py:1270-1301), csrc/nrml.hip: value, gradient,
+ * Hessian and Newton-CG direction of the maximum a posteriori problem in x = log S, batched over baselines (at most
+ * 65535 per call).  All arrays [dev], float64.  nchan = n <= 1024 channels, ndelay = N <= 2048 delays.  A complex
+ * n-vector is held as the real 2n-vector [Re ; Im], a Hermitian matrix as its real embedding [[A, -B], [B, A]] of
+ * order 2n.  Every call leaves a baseline alone whose status word (the DMM_DELAY_* values) is set.
+ *
+ * dmm_nrml_start: from two calls of dmm_delay_prepare with complex_td = 1 and coef = 1: Xp [nbase][nsample + 1][2 n],
+ * nzt and status of wiener = 1 (its last row is twice the averaged weight) and Xd [nbase][nsample][2 n] of wiener = 0
+ * (the mean-removed data themselves).  win [n] is the window at chan / N.  Writes tw [N][2] = (cos, sin)(2 pi m / N), wv [nbase][n] (the window, zero on a
+ * channel without weight), Nm [nbase][n] (the noise variance), Xe [nbase][2n][2n] (the covariance of the windowed
+ * data over the retained samples), nsv [nbase] (their number) and S0 [nbase][N], the starting spectrum: the variance
+ * over the samples of the unwindowed data of the channels with |w| > 1e-3 max |w|, transformed to delay.  Scratch: work
+ * [nbase][3][nsample][2 n], F2 [2 n][2 N], Z [nbase][nsample][2 N].
+ *
+ * dmm_nrml_eval: value [nbase] and grad [nbase][N] at x [nbase][N]; the likelihood sees x clipped to [lo, hi], the
+ * prior (Ci [N][N], the inverse kernel) sees x.  Leaves U, Y (= C^-1 U in its first N rows) and R in the workspace.
+ * A non-positive pivot sets status to DMM_DELAY_NOT_POSDEF.  Workspace: S [nbase][N], sh [nbase][N][2], G and D
+ * [nbase][2n][2n], U and R [nbase][N][2n], Y [nbase][N + n][2n], t and cix [nbase][N].
+ *
+ * dmm_nrml_hessian: H [nbase][N][N] (symmetric, both triangles) from that workspace, with the reference's Re(P_ab^2)
+ * as first term; exact = 0 gives the Fisher form.
+ * P and Q are formed by matrix products into the planes PQ [nbase][4][N][N] (Re P, Im P, Re Q, Im Q) of the workspace
+ * and combined element-wise.
+ *
+ * dmm_nrml_direction: scipy's truncated conjugate gradient for H p = -g, p [nbase][N]; info [nbase][2] = (passes, flag),
+ * flag 3 when the 20 N passes ran out. */
+typedef struct dmm_nrml_ws {
+  const int32_t* chan;
+  const double *tw, *wv, *Nm, *Xe, *nsv, *Ci;
+  double *S, *sh, *G, *D, *U, *Y, *R, *t, *cix, *PQ;
+} dmm_nrml_ws;
+int dmm_nrml_start(dmm_ctx* ctx, int ndelay, int nchan, int nsample, int nbase, const int32_t* chan, const double* win,
+                   const double* Xp, const double* Xd, const uint8_t* nzt, const int32_t* status, double* work, double* F2, double* Z, double* tw,
+                   double* wv, double* Nm, double* Xe, double* nsv, double* S0);
+int dmm_nrml_eval(dmm_ctx* ctx, int ndelay, int nchan, int nbase, const dmm_nrml_ws* ws, const double* x, double lo, double hi,
+                  int32_t* status, double* value, double* grad);
+int dmm_nrml_hessian(dmm_ctx* ctx, int ndelay, int nchan, int nbase, const dmm_nrml_ws* ws, int exact, const int32_t* status,
+                     double* H);
+int dmm_nrml_direction(dmm_ctx* ctx, int ndelay, int nbase, const double* H, const double* g, const int32_t* status, double* p,
+                       int32_t* info);
+
 /* DAYENU m-mode filter along right ascension (draco/analysis/dayenu.py:977-1122, 1235-1427), csrc/mfilter.hip.  All
  * arrays [dev]; the order nra is 1 ... 4096 in every call, matrices are batched, at most 65535 per call.
  *
