@@ -31,6 +31,7 @@ DMM_STACK_UNIFORM, DMM_STACK_INVERSE_VARIANCE = 0, 1
 DMM_REBIN_UNIFORM, DMM_REBIN_INVERSE_VARIANCE = 0, 1
 DMM_DAYENU_F32, DMM_DAYENU_F64 = 0, 1
 DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
+DMM_EW_TABLE, DMM_EW_INVERSE_VARIANCE = 0, 1
 DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
 DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
 DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
@@ -152,6 +153,12 @@ _SIGS = {
     "dmm_dayenu_build": (_i,[_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_dayenu_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
     "dmm_dayenu_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, C.POINTER(dmm_dayenu_side), C.POINTER(dmm_dayenu_side)]),
+    "dmm_dayenu_hybrid_mask": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "dmm_dayenu_hybrid_save": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "dmm_dayenu_hybrid_cov": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "dmm_ew_coef": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_ew_scale": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmm_ew_average": (_i, [_vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
     "dmm_delay_fourier": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dmm_delay_prepare": (_i, [_vp, _i, _i, _i, _i, _i64, _i, C.POINTER(_i64), C.POINTER(dmm_delay_view), C.POINTER(dmm_delay_view), _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "dmm_delay_project": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -6,6 +6,7 @@ Drop-in for ``draco/analysis/dayenu.py``:
 * :func:`delay_filter`, :func:`highpass_delay_filter`   ``dayenu.py:1125-1232``
 * :class:`DayenuDelayFilter`      ``dayenu.py:20-193``   (``SiderealStream`` / ``TimeStream``)
 * :class:`DayenuDelayFilterMap`   ``dayenu.py:776-975``  (``RingMap``)
+* :class:`DayenuDelayFilterHybridVis`  ``dayenu.py:407-572`` (``HybridVisStream``; keeps ``filter`` and ``freq_cov``)
 * :class:`DayenuMFilter`          ``dayenu.py:977-1122`` (``SiderealStream``)
 * :func:`bandpass_mmode_filter`, :func:`lowpass_mmode_filter`, :func:`highpass_mmode_filter`, :func:`instantaneous_m`
   ``dayenu.py:1235-1427``
@@ -30,7 +31,9 @@ The filter needs the whole band in one process: frequency sharding does not appl
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``single_mask=False`` (a filter per time
 sample), off-centre (complex) stop bands, the ``DelayCutoff`` file of the ring-map task (HDF5), and the reference's
-``DayenuDelayFilterFixedCutoff`` and hybrid-visibility variants.
+``DayenuDelayFilterFixedCutoff``, ``ApplyDelayFilterHybridVis`` and ``ApplyDelayFilterHybridVisSingleSource`` (applying
+a stored per-sample filter needs kernels of its own) and, of the hybrid-visibility task, ``elevation_vis_weight``
+streams and MPI redistribution.
 """
 
 from __future__ import annotations
@@ -342,6 +345,170 @@ class DayenuDelayFilterMap(_DayenuTask):
 
 
 
+def _group_rows(flags):
+    """``(masks [nuniq, n], index [nrow])`` of the distinct non-empty rows of ``flags [nrow, n]`` (bytes, 0 or 1); the
+    index of an empty row is -1.  The rows are packed into 64-bit words and sorted: ``numpy.unique(axis=0)`` on byte
+    rows costs tens of milliseconds for the 8192 samples of a stream."""
+    index = np.full(flags.shape[0], -1, dtype=np.int64)
+    valid = np.flatnonzero(flags.any(axis=1))
+    if valid.size == 0:
+        return np.zeros((0, flags.shape[1]), dtype=np.uint8), index
+    bits = np.packbits(flags[valid], axis=1)
+    words = np.zeros((valid.size, -(-bits.shape[1] // 8) * 8), dtype=np.uint8)
+    words[:, : bits.shape[1]] = bits
+    words = words.view(np.uint64)
+    order = np.lexsort(words.T[::-1])
+    first = np.ones(valid.size, dtype=bool)
+    first[1:] = np.any(words[order[1:]] != words[order[:-1]], axis=1)
+    index[valid[order]] = np.cumsum(first) - 1
+    return flags[valid[order[first]]], index
+
+
+class DayenuDelayFilterHybridVis(ContainerTask):
+    """Apply a DAYENU high-pass delay filter to hybrid beamformed visibilities (``dayenu.py:407-572``).
+
+    Attributes
+    ----------
+    tauw : float or array [nstopband]
+        The half width of the stop-band region in micro-seconds.  Default 0.4.
+    tauc : float or array [nstopband]
+        The centre of the stop-band region in micro-seconds.  Default 0; anything else raises ``NotImplementedError``.
+    epsilon : float or array [nstopband]
+        The stop-band rejection.  Default 1e-12.
+    atten_threshold : float
+        Mask any frequency where the diagonal element of the filter is not above this fraction of the median over the
+        unmasked frequencies.  Default 0.0 (off).
+    apply_filter : bool
+        Apply the filter that was generated.  If False, ``save_filter`` must be True.  Default True.
+    save_filter : bool
+        Save the filter to the ``filter`` dataset of the stream.  Default False.
+    calculate_cov : bool
+        Calculate the frequency-frequency noise covariance due to filtering, ``freq_cov = NF diag(1 / weight) NF^T``
+        from the weights before filtering.  Default False.  As in the reference it is left zero without ``apply_filter``.
+    workspace_mib : int
+        Device memory the filters of one batch (and their factorisation scratch) may take.  Default 1024.
+
+    Works in place and returns the input container; ``vis``, ``vis_weight``, ``filter`` and ``freq_cov`` stay on the
+    device.  There is one filter per ``(ew, ra)`` sample, from the channels whose weight is positive in every
+    polarisation; all polarisations and elevations of the sample use it, and samples with the same mask share one
+    build.  A sample with no such channel is skipped; one whose factorisation fails is logged, loses its weight (with
+    ``apply_filter``) and keeps zero ``filter`` and ``freq_cov``.  The whole band must be in this process.
+    """
+
+    _config_names = ("tauw", "tauc", "epsilon", "atten_threshold", "apply_filter", "save_filter", "calculate_cov", "workspace_mib")
+    tauw = 0.4
+    tauc = 0.0
+    epsilon = 1e-12
+    atten_threshold = 0.0
+    apply_filter = True
+    save_filter = False
+    calculate_cov = False
+    workspace_mib = 1024
+
+    def read_config(self, params):
+        params = dict(params)
+        for k in ("tauw", "tauc", "epsilon"):  # (the reference's proptype is numpy.atleast_1d)
+            if k in params:
+                setattr(self, k, np.atleast_1d(np.asarray(params.pop(k), dtype=np.float64)))
+        super().read_config(params)
+
+    def setup(self):
+        """Check that `save_filter` and `apply_filter` are set."""
+        if not self.apply_filter and not self.save_filter:
+            raise RuntimeError("At least one of `save_filter` and `apply_filter` must be True.")
+
+    def process(self, stream):
+        """Filter out delays from a HybridVisStream, in place."""
+        bands = _bands(self.tauw, self.tauc, self.epsilon)  # (NotImplementedError for a non-zero tauc)
+        stream.redistribute(["ra", "time"])
+        ctx = Context.get()
+        lib = _lib.lib
+        freq = np.ascontiguousarray(stream.freq[:], dtype=np.float64)
+        vis = _dev_dataset(stream.vis, ctx, np.complex64)
+        weight = _dev_dataset(stream.weight, ctx, np.float32)
+        npol, nfreq, new, nel, nra = (int(s) for s in vis.shape)
+        if tuple(weight.shape) != (npol, nfreq, new, nra) or freq.size != nfreq:
+            raise ValueError(f"vis {tuple(vis.shape)}, vis_weight {tuple(weight.shape)} and {freq.size} frequencies do not match")
+        if not 1 <= nfreq <= MAX_ORDER:
+            raise ValueError(f"{type(self).__name__}: {nfreq} frequencies, the kernels take 1 ... {MAX_ORDER}")
+        check_eigenvalue_cut(freq, bands)
+        if not self.apply_filter:
+            self.log.debug("Filter will be generated but not applied.")
+        nitem = new * nra
+        kept = {}
+        for name, on in (("filter", self.save_filter), ("freq_cov", self.calculate_cov)):
+            if on:
+                if name not in stream.datasets:
+                    stream.add_dataset(name)
+                kept[name] = ctx.empty((npol, nfreq, nfreq, new, nra), np.float64)
+
+        # flag[f] = all_pol(weight > 0) per (ew, ra) sample; samples with the same mask share one filter
+        flag_d = ctx.empty((nfreq, new, nra), np.uint8)
+        _lib.check(lib.dmm_dayenu_hybrid_mask(ctx.handle, npol, nfreq, new, nra, ptr(weight), ptr(flag_d)))
+        flags = np.ascontiguousarray(flag_d.cpu().numpy().reshape(nfreq, nitem).T)
+        ctx.uses(flag_d)
+        masks, imat = _group_rows(flags)
+        valid = np.flatnonzero(imat >= 0)
+        nuniq = masks.shape[0]
+        self.log.debug(f"{nitem} (ew, ra) samples, {valid.size} to filter, {nuniq} distinct filters.")
+        if nuniq == 0 or not self.apply_filter:
+            for name, t in kept.items():
+                if nuniq == 0 or name == "freq_cov":
+                    t.zero_()
+
+        freq_d = ctx.to_device(freq)
+        group = _GROUP[_lib.DMM_DAYENU_F32]
+        wide = 2 * nra  # the real and imaginary parts of a sample are two adjacent items with the same filter
+        per = max(1, min(65535, (int(self.workspace_mib) << 20) // (16 * nfreq * nfreq)))
+        for m0 in range(0, nuniq, per):
+            m1 = min(nuniq, m0 + per)
+            nf, status = build_filters(ctx, freq_d, np.repeat(bands[np.newaxis], m1 - m0, axis=0), masks[m0:m1])
+            sel = np.flatnonzero((imat >= m0) & (imat < m1))
+            local = np.full(nitem, -1, dtype=np.int32)
+            local[sel] = imat[sel] - m0
+            for it in sel[status[local[sel]] != 0]:
+                self.log.error(
+                    f"Failed to factorise the covariance while processing ew {it // nra}, ra {it % nra}\n"
+                    f"Percentage unmasked frequencies:  {100 * flags[it].mean():0.1f}"
+                )
+                local[it] = -2
+            local_d = ctx.to_device(local)
+            skip = 0 if m0 == 0 else 1  # the first batch also zeroes the samples that have no filter
+            if self.save_filter:
+                _lib.check(lib.dmm_dayenu_hybrid_save(ctx.handle, npol, nfreq, new, nra, ptr(nf), m1 - m0, ptr(local_d), skip, ptr(kept["filter"])))
+            if self.calculate_cov and self.apply_filter:
+                _lib.check(lib.dmm_dayenu_hybrid_cov(ctx.handle, npol, nfreq, new, nra, ptr(nf), m1 - m0, ptr(local_d), ptr(weight), skip, ptr(kept["freq_cov"])))
+            if self.apply_filter:
+                atten_d = None
+                if self.atten_threshold > 0.0:
+                    diag = torch.diagonal(nf, dim1=1, dim2=2).cpu().numpy()
+                    low = np.zeros(diag.shape, dtype=np.uint8)
+                    for m in range(m1 - m0):
+                        if status[m] == 0:
+                            low[m] = diag[m] > (self.atten_threshold * np.median(diag[m][diag[m] > 0.0]))
+                    atten_d = ctx.to_device(low)
+                ngw, ngd = (nra + group - 1) // group, (wide + group - 1) // group
+                uw = np.unique((sel // nra) * ngw + (sel % nra) // group).astype(np.int32)
+                ud = np.unique((sel // nra) * ngd + (2 * (sel % nra)) // group).astype(np.int32)
+                wide_d = ctx.to_device(np.repeat(local, 2))
+                uw_d, ud_d = ctx.to_device(uw), ctx.to_device(ud)
+                vr = torch.view_as_real(vis)
+                for pp in range(npol):
+                    data = _side(vr[pp], nel, 2 * new * nel * nra, 2 * nra, 1, 2 * nel * nra)
+                    wside = _side(weight[pp], 1, new * nra, 0, 1, nra)
+                    apply_filters(ctx, _lib.DMM_DAYENU_F32, _lib.DMM_DAYENU_ITEMS, nfreq, wide, new, nf, wide_d, None, ud_d, len(ud), data, None)
+                    apply_filters(ctx, _lib.DMM_DAYENU_F32, _lib.DMM_DAYENU_ITEMS, nfreq, nra, new, nf, local_d, atten_d, uw_d, len(uw), None, wside)
+                ctx.uses(atten_d, wide_d, uw_d, ud_d)
+            ctx.uses(nf, local_d)
+        ctx.uses(freq_d)
+        stream.vis.set_device(vis)
+        stream.weight.set_device(weight)
+        for name, t in kept.items():
+            stream.attach(name, t)
+        stream.redistribute("freq")
+        return stream
+
+
 def instantaneous_m(ha, lat, dec, u, v, w=0.0):
     """The instantaneous fringe rate (``dayenu.py:1399-1427``), on the host.
 
@@ -586,6 +753,7 @@ class DayenuMFilter(ContainerTask):
 
 __all__ = [
     "DayenuDelayFilter",
+    "DayenuDelayFilterHybridVis",
     "DayenuDelayFilterMap",
     "DayenuMFilter",
     "bandpass_mmode_filter",

@@ -295,6 +295,69 @@ TikhonovRingMapMakerExternal = TikhonovRingMapMaker
 WienerRingMapMakerExternal = WienerRingMapMaker
 
 
+class RADependentWeights(ContainerTask):
+    """Re-establish an RA dependence to the ``weight`` dataset of a deconvolved ringmap (``ringmapmaker.py:1202-1315``).
+
+    This RA dependence was lost in the round-trip m-mode transform.  ``process(hybrid_vis, ringmap)`` scales
+    ``ringmap.weight`` in place by ``sum_ew w_ew^2 <var>_ra inz(sum_ew w_ew^2 var)``, ``var`` the inverse of the hybrid
+    visibilities' weights and ``w_ew`` the east-west weights the ring-map maker recorded in the ``weight_ew`` and
+    ``exclude_cyl`` attributes.  If the hybrid visibilities carry a delay filter's ``filter`` (and, unless the scheme is
+    ``inverse_variance``, ``freq_cov``), their east-west averages ``[pol, freq, freq_sum, ra]`` are added to the ring
+    map.  Everything is computed in float64 and stays on the device (``csrc/dayenu_hybrid.hip``).
+    """
+
+    def process(self, hybrid_vis, ringmap):
+        """Scale the ringmap weights by the RA dependence of the hybrid visibility weights."""
+        exclude_cyl = ringmap.attrs.get("exclude_cyl", None)
+        weight_scheme = ringmap.attrs.get("weight_ew", None)
+        if (exclude_cyl is None) or (weight_scheme is None):
+            raise RuntimeError(
+                "The ring map maker must save `weight_ew` and `exclude_cyl` config parameters to the container attributes in order to "
+                "reconstruct the RA dependence of the noise."
+            )
+        weight_scheme = str(weight_scheme)
+        if weight_scheme not in ("natural", "uniform", "inverse_variance"):
+            raise ValueError(f"RADependentWeights: unknown weight_ew {weight_scheme!r}")
+        for dset in ("complex_filter", "complex_freq_cov"):
+            if dset in hybrid_vis:
+                raise NotImplementedError(f"RADependentWeights: the dataset {dset!r} is not supported (complex filters)")
+        todo = [d for d in ("filter", "freq_cov") if d in hybrid_vis and not (d == "freq_cov" and weight_scheme == "inverse_variance")]
+
+        hybrid_vis.redistribute("freq")
+        ringmap.redistribute("freq")
+        ctx = Context.get()
+        lib = _lib.lib
+        hw = _dev_dataset(hybrid_vis.weight, ctx, np.float32)
+        rw = _dev_dataset(ringmap.weight, ctx, np.float64)
+        npol, nfreq, n_ew, nra = (int(s) for s in hw.shape)
+        if tuple(rw.shape[:3]) != (npol, nfreq, nra):
+            raise ValueError(f"ring map weight {tuple(rw.shape)} does not match the hybrid visibilities' weight {tuple(hw.shape)}")
+        nel = int(rw.shape[3])
+
+        # the weights that were used to average over the EW baselines
+        table = np.ones(n_ew) if weight_scheme != "natural" else (n_ew - np.arange(n_ew)).astype(np.float64)
+        for cyl in np.atleast_1d(np.asarray(exclude_cyl, dtype=np.int64)).reshape(-1):
+            table[cyl] = 0.0
+        scheme = _lib.DMM_EW_INVERSE_VARIANCE if weight_scheme == "inverse_variance" else _lib.DMM_EW_TABLE
+        table_d = ctx.to_device(table)
+        coef = {"filter": ctx.empty((npol, nfreq, n_ew), np.float64), "freq_cov": ctx.empty((npol, nfreq, n_ew), np.float64)}
+        w2, num = ctx.empty((npol, nfreq, n_ew), np.float64), ctx.empty((npol, nfreq), np.float64)
+        _lib.check(lib.dmm_ew_coef(ctx.handle, npol, nfreq, n_ew, nra, scheme, ptr(table_d), ptr(hw), ptr(coef["filter"]), ptr(coef["freq_cov"]), ptr(w2), ptr(num)))
+        _lib.check(lib.dmm_ew_scale(ctx.handle, npol, nfreq, n_ew, nra, nel, ptr(hw), ptr(w2), ptr(num), ptr(rw)))
+        ringmap.weight.set_device(rw)
+
+        for dset in todo:
+            src = _dev_dataset(hybrid_vis[dset], ctx, np.float64)
+            if tuple(src.shape) != (npol, nfreq, nfreq, n_ew, nra):
+                raise ValueError(f"{dset} {tuple(src.shape)} does not match the hybrid visibilities")
+            out = ctx.empty((npol, nfreq, nfreq, nra), np.float64)
+            _lib.check(lib.dmm_ew_average(ctx.handle, npol * nfreq * nfreq, nfreq, n_ew, nra, ptr(coef[dset]), ptr(src), ptr(out)))
+            ringmap.add_dataset(dset)
+            ringmap.attach(dset, out)
+        ctx.uses(table_d, w2, num, *coef.values())
+        return ringmap
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # The ring-map chain MakeVisGrid -> BeamformNS -> BeamformEW (``ringmapmaker.py:38-534``): BeamformNS's output is what
 # MModeTransform turns into the HybridVisMModes the deconvolving makers above consume; BeamformEW makes the plain ring map.

@@ -484,9 +484,12 @@ class MModes(MContainer, _FreqMixin, _VisMixin):
 
 class HybridVisStream(ContainerBase, _FreqMixin, _VisMixin):
     """NS-beamformed visibilities: ``vis [pol, freq, ew, el, ra]`` c64, ``vis_weight [pol, freq, ew, ra]`` f32
-    (``containers.py:1389-1428``; the optional datasets of the reference are not carried)."""
+    (``containers.py:1389-1428``); optional ``dirty_beam``, ``effective_ra``, ``nsample`` and, from a delay filter that
+    kept them, ``filter`` and ``freq_cov`` ``[pol, freq, freq_sum, ew, ra]`` float64 (``containers.py:1459-1488``) via
+    :meth:`add_dataset`; the ``freq_sum`` axis is a copy of ``freq``.  The complex forms of the last two are not
+    provided."""
 
-    _axes = ("pol", "freq", "ew", "el", "ra")
+    _axes = ("pol", "freq", "freq_sum", "ew", "el", "ra")
     _dataset_spec = {
         "vis": {"axes": ["pol", "freq", "ew", "el", "ra"], "dtype": np.complex64},
         "vis_weight": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
@@ -497,11 +500,31 @@ class HybridVisStream(ContainerBase, _FreqMixin, _VisMixin):
         # what SiderealRebinner adds (containers.py:1439-1458)
         "effective_ra": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
         "nsample": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
+        # what DayenuDelayFilterHybridVis keeps (containers.py:1459-1488)
+        "filter": {"axes": ["pol", "freq", "freq_sum", "ew", "ra"], "dtype": np.float64},
+        "freq_cov": {"axes": ["pol", "freq", "freq_sum", "ew", "ra"], "dtype": np.float64},
     }
+    _complex_datasets = ("complex_filter", "complex_freq_cov")
 
     @property
     def ra(self):
         return self.index_map["ra"]
+
+    @property
+    def filter(self):
+        return self._optional("filter")
+
+    @property
+    def freq_cov(self):
+        return self._optional("freq_cov")
+
+    @property
+    def complex_filter(self):
+        raise NotImplementedError("HybridVisStream: complex filters are not supported")
+
+    @property
+    def complex_freq_cov(self):
+        raise NotImplementedError("HybridVisStream: complex noise covariances are not supported")
 
     @property
     def effective_ra(self):
@@ -518,7 +541,12 @@ class HybridVisStream(ContainerBase, _FreqMixin, _VisMixin):
         super().__init__(ra=ra, **kwargs)
 
     def add_dataset(self, name, allocate=False):
+        if name in self._complex_datasets:
+            raise NotImplementedError(f"HybridVisStream: the dataset {name!r} is not provided (complex filters are not supported)")
         self._dataset_spec[name] = self._optional_spec[name]
+        if "freq_sum" in self._optional_spec[name]["axes"] and "freq_sum" not in self.index_map:
+            self.index_map["freq_sum"] = self.index_map["freq"]  # (a copy of the frequency axis: the second index of a matrix)
+            self.index_attrs.setdefault("freq_sum", {})
         if allocate:
             self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=self._optional_spec[name]["dtype"]))
 

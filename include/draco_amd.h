@@ -571,6 +571,40 @@ int dmm_dayenu_apply(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner,
                      const int32_t* item_matrix, const uint8_t* atten, const int32_t* units, int64_t nunit,
                      const dmm_dayenu_side* data, const dmm_dayenu_side* weight);
 
+/* DAYENU filter of hybrid beam-formed visibilities (draco/analysis/dayenu.py:407-572) and the east-west averages of
+ * RADependentWeights (draco/analysis/ringmapmaker.py:1202-1315), csrc/dayenu_hybrid.hip.  All arrays [dev]; weight is
+ * the stream's vis_weight [npol][nfreq][new][nra] float32, and there is one filter per (ew, ra) sample: item_matrix
+ * [new][nra] int32 indexes nf [nmat][nfreq][nfreq] float64 (negative or >= nmat: no filter).  The filters come from
+ * dmm_dayenu_build and are applied with dmm_dayenu_apply (DMM_DAYENU_F32, DMM_DAYENU_ITEMS: items along ra).
+ *
+ * dmm_dayenu_hybrid_mask: flag [nfreq][new][nra] bytes = all_pol(weight > 0).  The weights are not changed.
+ *
+ * dmm_dayenu_hybrid_save: out [npol][nfreq][nfreq][new][nra] float64 = nf[item_matrix[x][t]][f][f'] for every pol.
+ * dmm_dayenu_hybrid_cov: out (same shape) = sum_k nf[m][f][k] nf[m][f'][k] inz(weight[p][k][x][t]), m =
+ * item_matrix[x][t], inz taken in float32, the sum in float64 on the matrix cores in an order that depends on the
+ * sample alone; symmetric in (f, f') bit for bit.
+ * Both: a sample without a filter is stored as zero if skip_negative is 0 and left untouched otherwise (the later
+ * launches of a build in batches).
+ *
+ * dmm_ew_coef, per (pol, freq): mean [x] = mean_ra inz(weight); w [x] = table[x] (DMM_EW_TABLE: the natural or uniform
+ * weights, excluded baselines zero) or inz(mean[x]) table[x] (DMM_EW_INVERSE_VARIANCE: table 1 or 0); coef_filter
+ * [npol][nfreq][new] = w inz(sum w), coef_cov = w^2 inz((sum w)^2), w2 = w^2, num [npol][nfreq] = sum w^2 mean.
+ * 1 <= new <= 64.
+ * dmm_ew_scale: ringmap_weight [npol][nfreq][nra][nel] float64 *= num inz(sum_x w2[x] inz(weight[p][f][x][t])).
+ * dmm_ew_average: out [nrow][nra] = sum_x coef[row / rows_per_coef][x] in[row][x][t], float64, in ew order (one
+ * rounding per product and per addition). */
+enum { DMM_EW_TABLE = 0, DMM_EW_INVERSE_VARIANCE = 1 };
+int dmm_dayenu_hybrid_mask(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, const float* weight, uint8_t* flag);
+int dmm_dayenu_hybrid_save(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, const double* nf, int nmat, const int32_t* item_matrix,
+                           int skip_negative, double* out);
+int dmm_dayenu_hybrid_cov(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, const double* nf, int nmat, const int32_t* item_matrix,
+                          const float* weight, int skip_negative, double* out);
+int dmm_ew_coef(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int scheme, const double* table, const float* weight,
+                double* coef_filter, double* coef_cov, double* w2, double* num);
+int dmm_ew_scale(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int nel, const float* weight, const double* w2, const double* num,
+                 double* ringmap_weight);
+int dmm_ew_average(dmm_ctx* ctx, int64_t nrow, int64_t rows_per_coef, int new_, int nra, const double* coef, const double* in, double* out);
+
 /* Delay spectrum estimators (draco/analysis/delay.py:347-1106, 2102-2201), csrc/delay.hip.  All arrays [dev] unless
  * noted, everything float64.  ndelay = N; order = N in the real time domain, 2 N (alternating real and imaginary) in
  * the complex one; nchan channels with indices chan [nchan] int32 in the full set; baselines are batched, at most
