@@ -7,6 +7,7 @@ Drop-in for ``draco/analysis/dayenu.py``:
 * :class:`DayenuDelayFilter`      ``dayenu.py:20-193``   (``SiderealStream`` / ``TimeStream``)
 * :class:`DayenuDelayFilterMap`   ``dayenu.py:776-975``  (``RingMap``)
 * :class:`DayenuDelayFilterHybridVis`  ``dayenu.py:407-572`` (``HybridVisStream``; keeps ``filter`` and ``freq_cov``)
+* :class:`ApplyDelayFilterHybridVis`, :class:`ApplyDelayFilterHybridVisSingleSource`  ``dayenu.py:575-773``
 * :class:`DayenuMFilter`          ``dayenu.py:977-1122`` (``SiderealStream``)
 * :func:`bandpass_mmode_filter`, :func:`lowpass_mmode_filter`, :func:`highpass_mmode_filter`, :func:`instantaneous_m`
   ``dayenu.py:1235-1427``
@@ -30,10 +31,13 @@ different filter.
 The filter needs the whole band in one process: frequency sharding does not apply to these two tasks.
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``single_mask=False`` (a filter per time
-sample), off-centre (complex) stop bands, the ``DelayCutoff`` file of the ring-map task (HDF5), and the reference's
-``DayenuDelayFilterFixedCutoff``, ``ApplyDelayFilterHybridVis`` and ``ApplyDelayFilterHybridVisSingleSource`` (applying
-a stored per-sample filter needs kernels of its own) and, of the hybrid-visibility task, ``elevation_vis_weight``
+sample), off-centre (complex) stop bands and stored complex filters, the ``DelayCutoff`` file of the ring-map task
+(HDF5), the reference's ``DayenuDelayFilterFixedCutoff`` and, of the hybrid-visibility tasks, ``elevation_vis_weight``
 streams and MPI redistribution.
+
+:class:`ApplyDelayFilterHybridVis` and :class:`ApplyDelayFilterHybridVisSingleSource` (``dayenu.py:575-773``) apply a
+filter that :class:`DayenuDelayFilterHybridVis` left on a stream to another stream (``csrc/hyfores.hip``); every
+sample has a matrix of its own there, so the product is a per-lane one along RA, not the shared-matrix GEMM above.
 """
 
 from __future__ import annotations
@@ -507,6 +511,163 @@ class DayenuDelayFilterHybridVis(ContainerTask):
             stream.attach(name, t)
         stream.redistribute("freq")
         return stream
+
+
+_MISMATCH = (
+    ("freq", "Frequencies do not match for hybrid visibilities."),
+    ("el", "Elevations do not match for hybrid visibilities."),
+    ("ew", "EW baselines do not match for hybrid visibilities."),
+    ("pol", "Polarisations do not match for hybrid visibilities."),
+    ("ra", "Right Ascension do not match for hybrid visibilities."),
+)
+
+
+def check_hybrid_match(source, hv):
+    """The reference's five ``ValueError`` s (``dayenu.py:621-635``)."""
+    for ax, msg in _MISMATCH:
+        a, b = (s.freq if ax == "freq" else s.index_map[ax] for s in (source, hv))
+        if not np.array_equal(a, b):
+            raise ValueError(msg)
+
+
+def check_real_filter(source):
+    """``NotImplementedError`` for a stored complex filter, ``KeyError`` where there is none."""
+    if "complex_filter" in source.datasets:
+        raise NotImplementedError("stored complex filters (off-centre stop bands) are not supported")
+    if "filter" not in source.datasets:
+        raise KeyError("Dataset 'filter' not initialised.")
+    if np.dtype(source.datasets["filter"].dtype).kind == "c":
+        raise NotImplementedError("stored complex filters (off-centre stop bands) are not supported")
+
+
+def stored_filter(source, ctx, shape):
+    """The real ``filter`` dataset of ``source`` on the device; ``shape`` is that of the visibilities it is applied to."""
+    check_real_filter(source)
+    filt = _dev_dataset(source.datasets["filter"], ctx, np.float64)
+    npol, nfreq, new, nel, nra = shape
+    if tuple(filt.shape) != (npol, nfreq, nfreq, new, nra):
+        raise ValueError(f"filter {tuple(filt.shape)} does not match visibilities {tuple(shape)}")
+    if not 1 <= nfreq <= MAX_ORDER:
+        raise ValueError(f"{nfreq} frequencies, the kernels take 1 ... {MAX_ORDER}")
+    return filt
+
+
+def attenuation_flags(ctx, filt, atten_threshold):
+    """``[pol, freq, ew, ra]`` bytes on the device: ``|F[f, f]| > atten_threshold x median`` over the non-zero
+    ``|F[f, f]|`` of the sample (1 everywhere for a sample whose diagonal is zero).  The diagonal, 1 / nfreq of the
+    filter, is gathered on the device; the median is ``numpy.median`` on the host, as the reference's."""
+    diag = torch.diagonal(filt, dim1=1, dim2=2).abs().cpu().numpy()  # [pol, ew, ra, freq]
+    nonzero = diag > 0.0
+    some = nonzero.any(axis=-1, keepdims=True)
+    # (the median of the non-zero entries of a row: NaN marks the others; a row without any gets a 1 in their place)
+    med = np.nanmedian(np.where(nonzero | ~some, np.where(some, diag, 1.0), np.nan), axis=-1, keepdims=True)
+    low = np.where(some, diag > atten_threshold * med, True)
+    return ctx.to_device(np.ascontiguousarray(np.moveaxis(low, -1, 1)).astype(np.uint8))
+
+
+def apply_stored_filter(ctx, vis, weight, filt, gain=None, atten_threshold=0.0, atten_vis=False, keep_input=True, want_weight=True, want_cov=False):
+    """``(vis_out, weight_out, freq_cov, status, atten)`` of ``dmm_hybrid_filter_apply`` (``include/draco_amd.h``):
+    device tensors, ``None`` for what was not asked for; ``status [pol, ew, ra]`` bytes.  ``gain [pol, ew, freq]``
+    complex128 (host) takes ``1 - gain`` out of the data first."""
+    npol, nfreq, new, nel, nra = (int(s) for s in vis.shape)
+    atten = attenuation_flags(ctx, filt, atten_threshold) if atten_threshold > 0.0 else None
+    gain_d = None if gain is None else ctx.to_device(np.ascontiguousarray(gain, dtype=np.complex128))
+    vis_out = ctx.empty(vis.shape, np.complex64)
+    weight_out = ctx.empty(weight.shape, np.float32) if want_weight else None
+    cov = ctx.empty(filt.shape, np.float64) if want_cov else None
+    bits = ctx.empty((npol, new, nra), np.int32)
+    status = ctx.empty((npol, new, nra), np.uint8)
+    _lib.check(
+        _lib.lib.dmm_hybrid_filter_apply(ctx.handle, npol, nfreq, new, nel, nra, ptr(filt), ptr(vis), ptr(weight), ptr(gain_d), ptr(atten), int(bool(atten_vis)), int(bool(keep_input)),
+                                         ptr(vis_out), ptr(weight_out), ptr(cov), ptr(bits), ptr(status))
+    )
+    ctx.uses(gain_d, bits)
+    return vis_out, weight_out, cov, status, atten
+
+
+def log_filter_status(log, ctx, status, weight, filt):
+    """The reference's warning for every missing-frequency sample (``dayenu.py:692-698``), from the status bytes."""
+    st = status.cpu().numpy()
+    for p, x, t in np.argwhere(st == _lib.DMM_HFA_MISSING_FREQ):
+        flag = weight[p, :, x, t].cpu().numpy() > 0.0
+        valid = (filt[p, :, :, x, t] != 0.0).any(dim=0).cpu().numpy()
+        log.warning(f"Missing the following frequencies that were assumed valid during filter generation: {np.flatnonzero(valid & ~flag)}")
+    return st
+
+
+class ApplyDelayFilterHybridVis(ContainerTask):
+    """Apply a previously saved filter to hybrid beamformed visibilities (``dayenu.py:575-739``): how the 21-cm
+    simulation gets the data's foreground filter.
+
+    Attributes
+    ----------
+    atten_threshold : float
+        Mask any frequency where the diagonal element of the filter is not above this fraction of the median over the
+        non-zero diagonal elements.  Default 0.0 (off).
+    calculate_cov : bool
+        Calculate the frequency-frequency noise covariance due to filtering.  Default False.
+    copy_weight : bool
+        Do not propagate the weights through the filter; copy ``vis_weight`` (and ``freq_cov``) from the container the
+        filter came from.  Default False.
+    copy_tag : bool
+        Copy the tag from the container the filter came from.  Default False.
+
+    Works in place and returns ``hv``; ``vis``, ``vis_weight`` and ``freq_cov`` stay on the device, and ``source.filter``
+    is read where it is.  The flag of a sample is per polarisation (``weight[p, :, x, t] > 0``).  A sample with no flag
+    set is skipped; one whose filter is entirely zero loses its weight; one with a column of the filter non-zero where
+    its flag is not set loses its weight, keeps its data and is logged.  Complex filters raise ``NotImplementedError``.
+    """
+
+    _config_names = ("atten_threshold", "calculate_cov", "copy_weight", "copy_tag")
+    atten_threshold = 0.0
+    calculate_cov = False
+    copy_weight = False
+    copy_tag = False
+
+    def process(self, hv, source):
+        """Apply the stored DAYENU filter of ``source`` to ``hv``."""
+        check_hybrid_match(source, hv)
+        check_real_filter(source)
+        if self.copy_tag:
+            hv.attrs["tag"] = source.attrs["tag"]
+        ctx = Context.get()
+        vis = _dev_dataset(hv.vis, ctx, np.complex64)
+        weight = _dev_dataset(hv.weight, ctx, np.float32)
+        filt = stored_filter(source, ctx, vis.shape)
+        if self.calculate_cov and "freq_cov" not in hv.datasets:
+            hv.add_dataset("freq_cov")
+        own = not self.copy_weight
+        vis_out, weight_out, cov, status, _ = apply_stored_filter(ctx, vis, weight, filt, atten_threshold=self.atten_threshold if own else 0.0, want_weight=own,
+                                                                  want_cov=self.calculate_cov and own)
+        log_filter_status(self.log, ctx, status, weight, filt)
+        if self.copy_weight:
+            weight_out = _dev_dataset(source.weight, ctx, np.float32).clone()
+            if self.calculate_cov:
+                cov = _dev_dataset(source.freq_cov, ctx, np.float64).clone()
+        hv.vis.set_device(vis_out)
+        hv.weight.set_device(weight_out)
+        if self.calculate_cov:
+            hv.attach("freq_cov", cov)
+        return hv
+
+
+class ApplyDelayFilterHybridVisSingleSource(ApplyDelayFilterHybridVis):
+    """:class:`ApplyDelayFilterHybridVis` with one filter, given to ``setup``, for every stream (``dayenu.py:742-773``)."""
+
+    def setup(self, source):
+        """Set the stream whose DAYENU filter is applied."""
+        self.source = source
+
+    def process(self, hv):
+        """Apply the stored DAYENU filter to ``hv``."""
+        return super().process(hv, self.source)
+
+
+class DayenuDelayFilterFixedCutoff(ContainerTask):
+    """Not provided (``dayenu.py:196-404``)."""
+
+    def __init__(self, **params):
+        raise NotImplementedError("DayenuDelayFilterFixedCutoff is not provided")
 
 
 def instantaneous_m(ha, lat, dec, u, v, w=0.0):

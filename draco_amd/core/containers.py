@@ -1212,6 +1212,79 @@ class SiderealRFIMaskByPol(SiderealRFIMask):
     _dataset_spec = {"mask": {"axes": ["pol", "freq", "ra"], "dtype": np.bool_}}
 
 
+class RingMapMask(_RaAxisMixin, ContainerBase, _FreqMixin, _MaskMixin):
+    """Mask of bad ring-map pixels: ``mask [pol, freq, ra, el]`` bool (``containers.py:1730-1748``)."""
+
+    _axes = ("pol", "freq", "ra", "el")
+    _dataset_spec = {"mask": {"axes": ["pol", "freq", "ra", "el"], "dtype": np.bool_}}
+
+
+class _BandpassMixin:
+    @property
+    def pol(self):
+        return self.index_map["pol"]
+
+    @property
+    def bandpass(self):
+        return self.datasets["bandpass"]
+
+    @property
+    def window(self):
+        return self.datasets["window"]
+
+    @property
+    def comp_bandpass(self):
+        return self.datasets["comp_bandpass"]
+
+    @property
+    def sval(self):
+        return self.datasets["sval"]
+
+
+class VisBandpassWindow(ContainerBase, _FreqMixin, _BandpassMixin):
+    """Bandpass gains estimated by HyFoReS and their window: ``bandpass [pol, freq]``, ``window [pol, freq, freq]``
+    complex128 (``containers.py:3172-3201``).  Kilobytes: host resident."""
+
+    _axes = ("pol", "freq")
+    _dataset_spec = {
+        "bandpass": {"axes": ["pol", "freq"], "dtype": np.complex128},
+        "window": {"axes": ["pol", "freq", "freq"], "dtype": np.complex128},
+    }
+
+
+class VisBandpassCompensate(ContainerBase, _FreqMixin, _BandpassMixin):
+    """Window-compensated bandpass gains: ``comp_bandpass`` and ``sval [pol, freq]`` complex128
+    (``containers.py:3204-3233``)."""
+
+    _axes = ("pol", "freq")
+    _dataset_spec = {
+        "comp_bandpass": {"axes": ["pol", "freq"], "dtype": np.complex128},
+        "sval": {"axes": ["pol", "freq"], "dtype": np.complex128},
+    }
+
+
+class VisBandpassWindowBaseline(VisBandpassWindow):
+    """:class:`VisBandpassWindow` per east-west baseline: ``bandpass [pol, ew, freq]``, ``window [pol, ew, freq, freq]``
+    complex128 (``containers.py:3236-3264``)."""
+
+    _axes = ("pol", "ew", "freq")
+    _dataset_spec = {
+        "bandpass": {"axes": ["pol", "ew", "freq"], "dtype": np.complex128},
+        "window": {"axes": ["pol", "ew", "freq", "freq"], "dtype": np.complex128},
+    }
+
+
+class VisBandpassCompensateBaseline(VisBandpassCompensate):
+    """:class:`VisBandpassCompensate` per east-west baseline: ``comp_bandpass`` and ``sval [pol, ew, freq]`` complex128
+    (``containers.py:3267-3295``); the clean task sets the attributes ``rank [pol, ew]`` and ``cutoff``."""
+
+    _axes = ("pol", "ew", "freq")
+    _dataset_spec = {
+        "comp_bandpass": {"axes": ["pol", "ew", "freq"], "dtype": np.complex128},
+        "sval": {"axes": ["pol", "ew", "freq"], "dtype": np.complex128},
+    }
+
+
 def _all_containers():
     found, todo = [], [ContainerBase]
     while todo:

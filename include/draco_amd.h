@@ -605,6 +605,41 @@ int dmm_ew_scale(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int nel, 
                  double* ringmap_weight);
 int dmm_ew_average(dmm_ctx* ctx, int64_t nrow, int64_t rows_per_coef, int new_, int nra, const double* coef, const double* in, double* out);
 
+/* Stored per-sample delay filters on hybrid visibilities (draco/analysis/dayenu.py:575-773) and the HyFoReS bandpass
+ * estimate (draco/analysis/hyforesbandpass.py), csrc/hyfores.hip.  All arrays [dev]: filter / freq_cov
+ * [npol][nfreq][nfreq][new][nra] float64 (real filters only), vis / post / vis_out [npol][nfreq][new][nel][nra]
+ * complex64, weight / weight_out [npol][nfreq][new][nra] float32.  1 <= nfreq <= 1024, npol * new <= 65535,
+ * nel <= 65535.  Every sum is float64 in an order fixed by the shapes: two calls agree bit for bit.
+ *
+ * dmm_hybrid_filter_apply, per (pol, ew, ra) sample with flag[k] = weight[k] > 0 (per polarisation):
+ *   status [npol][new][nra] bytes = DMM_HFA_SKIPPED (no flag set), DMM_HFA_ZERO_FILTER (the filter is entirely zero),
+ *   DMM_HFA_MISSING_FREQ (a column k of the filter is non-zero where flag[k] is not set) or DMM_HFA_OK;
+ *   OK:  vis_out[f][l] = sum_k filter[f][k] d[k] vis[k][l], rounded to complex64 at the end; d = 1 - gain[p][x][k]
+ *        (gain [npol][new][nfreq] complex128) or 1 where gain is NULL; with var[k] = inz(weight[k]) |d[k]|^2 (inz in
+ *        float32): weight_out[f] = inz(sum_k filter[f][k]^2 var[k]) atten[f] and freq_cov[f][f'] = sum_k (filter[f][k]
+ *        filter[f'][k]) var[k], symmetric bit for bit; atten [npol][nfreq][new][nra] bytes (0 or 1) or NULL, applied to
+ *        vis_out too if atten_vis is set;
+ *   otherwise: vis_out = vis (keep_input set) or 0, freq_cov = 0, weight_out = weight (skipped) or 0.
+ *   weight_out and freq_cov may be NULL (not computed).  Works out of place: vis_out != vis, weight_out != weight.
+ *   bits [npol][new][nra] uint32 is scratch.
+ *
+ * The estimate, with m[f][l][t] = (weight[f][t] > 0) && elm[l] && !pix[p][f][l][t] (elm [nel] bytes, pix
+ * [npol][nfreq][nel][nra] bytes or NULL), g = (vis - post) m and s = post m formed in float64:
+ * dmm_hyfores_gain: yn [npol][new][nfreq] complex128 = sum_{l, t} conj(g) s, d [npol][new][nfreq] float64 =
+ *   sum_{l, t} |g|^2.
+ * dmm_hyfores_window: window [npol][new][nfreq][nfreq] complex128, [f][f'] = sum_t filter[f][f'][t] sum_l conj(g[f][l][t])
+ *   g[f'][l][t]; partial is scratch of ceil(nra / DMM_HYFORES_RUN) * npol * new * nfreq * nfreq complex128: the sums of
+ *   each run of RA, added in run order by a second pass. */
+enum { DMM_HFA_OK = 0, DMM_HFA_SKIPPED = 1, DMM_HFA_ZERO_FILTER = 2, DMM_HFA_MISSING_FREQ = 3 };
+#define DMM_HYFORES_RUN 64
+int dmm_hybrid_filter_apply(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int nra, const double* filter, const void* vis, const float* weight,
+                            const double* gain, const uint8_t* atten, int atten_vis, int keep_input, void* vis_out, float* weight_out, double* freq_cov,
+                            uint32_t* bits, uint8_t* status);
+int dmm_hyfores_gain(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int nra, const void* vis, const void* post, const float* weight,
+                     const uint8_t* elm, const uint8_t* pix, double* yn, double* d);
+int dmm_hyfores_window(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int nra, const double* filter, const void* vis, const void* post,
+                       const float* weight, const uint8_t* elm, const uint8_t* pix, double* partial, double* window);
+
 /* Delay spectrum estimators (draco/analysis/delay.py:347-1106, 2102-2201), csrc/delay.hip.  All arrays [dev] unless
  * noted, everything float64.  ndelay = N; order = N in the real time domain, 2 N (alternating real and imaginary) in
  * the complex one; nchan channels with indices chan [nchan] int32 in the full set; baselines are batched, at most
