@@ -34,6 +34,7 @@ DMM_DAYENU_COLS, DMM_DAYENU_ITEMS = 0, 1
 DMM_EW_TABLE, DMM_EW_INVERSE_VARIANCE = 0, 1
 DMM_HFA_OK, DMM_HFA_SKIPPED, DMM_HFA_ZERO_FILTER, DMM_HFA_MISSING_FREQ = 0, 1, 2, 3
 DMM_HYFORES_RUN = 64
+DMM_NOISE_OK, DMM_NOISE_NOT_POSDEF = 0, 1
 DMM_DELAY_F32, DMM_DELAY_F64, DMM_DELAY_C64, DMM_DELAY_C128 = 0, 1, 2, 3
 DMM_DELAY_OK, DMM_DELAY_SKIPPED, DMM_DELAY_NOT_POSDEF, DMM_DELAY_CUT = 0, 1, 2, 3
 DMM_MFILTER_UNTOUCHED, DMM_MFILTER_WEIGHT_ONLY, DMM_MFILTER_FILTER = 0, 1, 2
@@ -164,6 +165,12 @@ _SIGS = {
     "dmm_hybrid_filter_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_hyfores_gain": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmm_hyfores_window": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_noisemodel_pack": (_i, [_vp, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_noisemodel_factor": (_i, [_vp, _i, _i, _vp, _vp]),
+    "dmm_noisemodel_store": (_i, [_vp, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
+    "dmm_noisemodel_weight": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_noise_colour": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmm_noise_hermitian": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "dmm_delay_fourier": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dmm_delay_prepare": (_i, [_vp, _i, _i, _i, _i, _i64, _i, C.POINTER(_i64), C.POINTER(dmm_delay_view), C.POINTER(dmm_delay_view), _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "dmm_delay_project": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

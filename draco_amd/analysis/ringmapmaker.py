@@ -16,13 +16,14 @@ from __future__ import annotations
 
 import numpy as np
 import scipy.constants
+import torch
 
 from .. import _lib
 from ..core import containers, io
 from ..core.task import ContainerTask
 from ..device import Context, ptr
 from ..util import tools
-from .transform import _dev_dataset
+from .transform import TelescopeStreamMixIn, _dev_dataset
 
 _WINDOW_COEF = {
     "uniform": (1, 0, 0, 0),
@@ -679,4 +680,193 @@ class RingMapMaker(ContainerTask):
         out = sstream
         for t in self._tasks:
             out = t.process(out)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Noise models that reproduce the statistics of the hybrid beam-formed visibilities (``ringmapmaker.py:1318-1712``):
+# sidereal weights (ReconstructVisWeight) and the Cholesky factors of the frequency-frequency covariance
+# (ReconstructVisFreqCov), which ``synthesis.noise`` turns into noise realisations on the baseline grid.
+class ReconstructVisNoiseBase(TelescopeStreamMixIn, ContainerTask):
+    """Shared logic of the two reconstructions (``ringmapmaker.py:1318-1514``): the beamforming parameters from the
+    attributes ``BeamformNS`` wrote, the layout and redundancy of the baselines, and the north-south window.  These are
+    ``[pol, freq, nx, ny]`` at most and stay on the host in float64 with the reference's expressions.  Abstract:
+    subclasses define ``_fill_output``.  One process holds the whole band and RA axis (no MPI distribution)."""
+
+    def process(self, hv):
+        self._parse_attrs(hv.attrs)
+        freq = self._redistribute_input(hv)
+        layout = self._compute_layout(hv)
+        window = self._compute_window(freq, layout)
+        return self._fill_output(hv, window, layout)
+
+    def _parse_attrs(self, attrs):
+        self.weight = str(attrs["beamform_ns_weight"])
+        if self.weight == "inverse_variance":
+            raise ValueError("Weight scheme inverse_variance not supported.")
+        self.include_auto = bool(attrs["beamform_ns_include_auto"])
+        self.scaled = bool(attrs["beamform_ns_scaled"])
+        self.freqmin = float(attrs["beamform_ns_freqmin"])
+        self.nsmax = float(attrs["beamform_ns_nsmax"])
+        self.wvmin = scipy.constants.c * 1e-6 / self.freqmin
+
+    def _redistribute_input(self, hv):
+        comm = getattr(hv, "comm", None)
+        if comm is not None and getattr(comm, "size", 1) > 1:
+            raise NotImplementedError(f"{type(self).__name__} runs with the whole band and RA axis in one process (no MPI distribution)")
+        return np.asarray(hv.freq, dtype=np.float64)
+
+    def _compute_layout(self, hv):
+        """Layout and redundancy of the baselines (``ringmapmaker.py:1375-1463``), the reference's dictionary."""
+        tel = self.telescope
+        # the pair whose polarisations and separation a stack entry's data carry: `prodstack` where the telescope has
+        # one (a conjugated representative swapped, as MakeVisGrid reads it), else `uniquepairs` (a driftscan telescope's
+        # are the same thing)
+        ps = getattr(tel, "prodstack", None)
+        pairs = np.asarray(tel.uniquepairs) if ps is None else np.stack([np.asarray(ps["input_a"], dtype=np.int64), np.asarray(ps["input_b"], dtype=np.int64)], axis=1)
+        polprod = np.asarray(tel.polarisation)[pairs]
+        polpair = np.char.add(polprod[:, 0], polprod[:, 1])
+        polpair, pind = np.unique(polpair, return_inverse=True)
+        pol = np.asarray(hv.index_map["pol"])
+        npol = pol.size
+        pol_lookup = {str(key): ind for ind, key in enumerate(pol)}
+        pol_remap = np.array([pol_lookup.get(str(pstr), -1) for pstr in polpair[pind]])
+        pol_flag = pol_remap >= 0
+        xind, yind, min_xsep, min_ysep = find_grid_indices(tel.baselines)
+        baseline_flag = np.abs(yind * min_ysep) <= (self.nsmax + 0.5 * min_ysep)
+        ny = 2 * np.abs(yind).max() + 1
+        nspos = np.fft.fftfreq(ny, d=(1.0 / (ny * min_ysep)))
+        vis_pos_x = np.arange(np.max(np.abs(xind)) + 1) * min_xsep
+        ewpos = np.asarray(hv.index_map["ew"])
+        nx = ewpos.size
+        if not np.array_equal(vis_pos_x, ewpos):
+            raise RuntimeError("Downselected ew axis not currently supported.")
+        flag = pol_flag & baseline_flag
+        xind, yind, pind = xind[flag], yind[flag], pol_remap[flag]
+        pconjmap = np.unique([str(p)[1] + str(p)[0] for p in pol], return_inverse=True)[1]
+        input_flags = np.all(np.asarray(tel.feedmask), axis=-1, keepdims=True)
+        nbaseline = tools.calculate_redundancy(input_flags, self.bt_prod, self.bt_rev["stack"], self.bt_stack.size)[:, 0]
+        nbaseline_valid = nbaseline[flag]
+        nbaseline_grid = np.zeros((npol, nx, ny), dtype=float)
+        nbaseline_grid[pind, xind, yind] = nbaseline_valid
+        intra = np.flatnonzero(xind == 0)
+        nbaseline_grid[pconjmap[pind[intra]], 0, -yind[intra]] = nbaseline_valid[intra]
+        return {"xind": xind, "yind": yind, "pind": pind, "ewpos": ewpos, "nspos": nspos, "nbaseline_grid": nbaseline_grid, "nbaseline": nbaseline, "flag": flag,
+                "pconjmap": pconjmap, "npol": npol, "nx": nx, "ny": ny}
+
+    def _compute_window(self, freq, layout):
+        """The normalised window ``[npol, nfreq, nx, ny]`` as a function of north-south baseline (``:1465-1506``)."""
+        freq = np.asarray(freq, dtype=np.float64)
+        window = np.empty((layout["npol"], freq.size, layout["nx"], layout["ny"]), dtype=float)
+        if self.weight == "natural":
+            window[:] = layout["nbaseline_grid"][:, np.newaxis]
+        else:
+            wavelength = scipy.constants.c * 1e-6 / freq
+            for ff, wv in enumerate(wavelength):
+                vpos = layout["nspos"] / wv
+                vmax = self.nsmax / self.wvmin if self.scaled else self.nsmax / wv
+                x = 0.5 * (vpos / vmax + 1)
+                window[:, ff, :, :] = window_generalised_full(x, window=self.weight)
+        if self.include_auto:  # (the reference's own condition, ringmapmaker.py:1501)
+            window[:, :, 0, 0] = 0.0
+        norm = np.sum(window, axis=-1, keepdims=True)
+        return window * tools.invert_no_zero(norm)
+
+    def _fill_output(self, hv, window, layout):
+        raise NotImplementedError("_fill_output must be implemented in subclass.")
+
+
+def weight_noise_factor(window, layout):
+    """``[pol, freq, ew]``: ``sum_ns window^2 inz(nbaseline_grid)`` (``ringmapmaker.py:1580-1583``)."""
+    return np.sum(window**2 * tools.invert_no_zero(layout["nbaseline_grid"][:, np.newaxis]), axis=-1)
+
+
+def cov_noise_factor(window, layout):
+    """``[pol, freq, freq_sum, ew]``: ``sum_ns window[f] window[f'] inz(nbaseline_grid)`` (``ringmapmaker.py:1671-1690``)."""
+    inv_nb = tools.invert_no_zero(layout["nbaseline_grid"][:, np.newaxis])
+    npol, nfreq, nx, _ = window.shape
+    noise_factor = np.empty((npol, nfreq, nfreq, nx), dtype=float)
+    for ff in range(nfreq):
+        noise_factor[:, ff] = np.sum(window[:, ff, np.newaxis] * window * inv_nb, axis=-1)
+    return noise_factor
+
+
+class ReconstructVisWeight(ReconstructVisNoiseBase):
+    """A ``SiderealStream`` with zero visibilities and the weights that, beam-formed north-south, give back the weights of
+    the input ``HybridVisStream`` (``ringmapmaker.py:1517-1601``):
+    ``vis_weight[f, stack, ra] = nbaseline (hv.weight noise_factor)[pind, f, xind, ra]`` where the stack entry takes part,
+    0 elsewhere, the products in float64 and rounded once to float32, filled on the device (``dmm_noisemodel_weight``)
+    from ``hv.weight`` wherever it lies."""
+
+    def _fill_output(self, hv, window, layout):
+        ctx = Context.get()
+        ss = containers.SiderealStream(axes_from=hv, attrs_from=hv, input=self.telescope.input_index, prod=self.bt_prod, stack=self.bt_stack,
+                                       reverse_map_stack=self.bt_rev, comm=hv.comm, allocate=False)
+        hw = _dev_dataset(hv.weight, ctx, np.float32)
+        npol, nfreq, nx, nra = (int(s) for s in hw.shape)
+        nstack = int(self.bt_stack.size)
+        nf = weight_noise_factor(window, layout)
+        cell = np.full(nstack, -1, dtype=np.int32)
+        cell[layout["flag"]] = layout["pind"] * nx + layout["xind"] % nx  # (a negative index wraps as NumPy's does)
+        nb = np.where(layout["flag"], layout["nbaseline"], 0.0).astype(np.float32).astype(np.float64)  # (through the float32 dataset)
+        tabs = [ctx.to_device(np.ascontiguousarray(nf, dtype=np.float64)), ctx.to_device(cell), ctx.to_device(nb)]
+        wss = ctx.empty((nfreq, nstack, nra), np.float32)
+        _lib.check(_lib.lib.dmm_noisemodel_weight(ctx.handle, npol, nfreq, nx, nra, nstack, ptr(hw.contiguous()), *(ptr(t) for t in tabs), ptr(wss)))
+        ctx.uses(*tabs)
+        ss.attach("vis", ctx.zeros((nfreq, nstack, nra), np.complex64))
+        ss.attach("vis_weight", wss)
+        return ss
+
+
+class ReconstructVisFreqCov(ReconstructVisNoiseBase):
+    """A ``FreqNoiseModel`` with the lower Cholesky factor of the frequency-frequency covariance of every
+    ``(pol, ew, ra)`` sample, scaled to the beamforming window and the redundancy (``ringmapmaker.py:1604-1712``), and
+    ``weight = 1 / diag`` of the scaled covariance; channels whose weight is not positive are left out (zero rows and
+    columns).  ``freq_cov`` and ``weight`` of the result are device resident: the samples are packed into
+    matrix-contiguous form, factored in batches and stored (``csrc/noisemodel.hip``).  A sample that is not positive
+    definite raises ``numpy.linalg.LinAlgError`` naming the first ``(pol, ew, ra)``.
+
+    Attributes
+    ----------
+    workspace_mib : int
+        Device memory the packed matrices of one batch may take (at most 65535 matrices per batch).  The result does not
+        depend on it.  Default 1024.
+    """
+
+    _config_names = ("workspace_mib",)
+    workspace_mib = 1024
+
+    def _fill_output(self, hv, window, layout):
+        if "complex_freq_cov" in hv.datasets:
+            raise NotImplementedError("ReconstructVisFreqCov: the dataset 'complex_freq_cov' is not supported (complex covariances)")
+        ctx = Context.get()
+        out = containers.FreqNoiseModel(axes_from=hv, attrs_from=hv, ns=layout["nspos"], comm=hv.comm, allocate=False)
+        out.add_dataset("freq_cov")
+        out.datasets["redundancy"] = containers.Dataset(host=layout["nbaseline_grid"].astype(np.int32), attrs={"axis": ["pol", "ew", "ns"]})
+        cov_in = _dev_dataset(hv.freq_cov, ctx, np.float64).contiguous()
+        hw = _dev_dataset(hv.weight, ctx, np.float32).contiguous()
+        npol, nfreq, _, nx, nra = (int(s) for s in cov_in.shape)
+        if tuple(hw.shape) != (npol, nfreq, nx, nra):
+            raise ValueError(f"vis_weight {tuple(hw.shape)} does not match freq_cov {tuple(cov_in.shape)}")
+        scale = ctx.to_device(np.ascontiguousarray(tools.invert_no_zero(cov_noise_factor(window, layout))))
+        chol = ctx.empty((npol, nx, nra, nfreq, nfreq), np.float64)
+        weight_out = ctx.empty((npol, nfreq, nx, nra), np.float32)
+        total = npol * nx * nra
+        chunk = int(max(1, min(65535, total, (int(self.workspace_mib) << 20) // (8 * nfreq * nfreq))))
+        G = ctx.empty((chunk, nfreq, nfreq), np.float64)
+        status = ctx.empty((total,), np.int32)
+        lib = _lib.lib
+        for s0 in range(0, total, chunk):
+            ns = min(chunk, total - s0)
+            st = status[s0 : s0 + ns]
+            _lib.check(lib.dmm_noisemodel_pack(ctx.handle, npol, nfreq, nx, nra, s0, ns, ptr(cov_in), ptr(scale), ptr(hw), ptr(G), ptr(weight_out)))
+            _lib.check(lib.dmm_noisemodel_factor(ctx.handle, nfreq, ns, ptr(G), ptr(st)))
+            _lib.check(lib.dmm_noisemodel_store(ctx.handle, npol, nfreq, nx, nra, s0, ns, ptr(G), ptr(hw), ptr(st), ptr(chol)))
+        bad = torch.nonzero(status)
+        if bad.numel():
+            s = int(bad[0, 0])
+            raise np.linalg.LinAlgError(f"Matrix is not positive definite at (pol, ew, ra) = ({s // (nx * nra)}, {(s // nra) % nx}, {s % nra})")
+        ctx.uses(scale, G)
+        out.attach("freq_cov", chol)
+        out.attach("weight", weight_out)
         return out

@@ -584,6 +584,58 @@ class VisGridStream(ContainerBase, _FreqMixin, _VisMixin):
         raise KeyError("Dataset 'redundancy' not initialised.")
 
 
+class FreqNoiseModel(ContainerBase, _FreqMixin):
+    """Cholesky factors of the frequency-frequency noise covariance, for noise realisations on the baseline grid
+    (``containers.py:1777-1837``): ``redundancy [pol, ew, ns]`` int32, ``weight [pol, freq, ew, ra]`` float32 and,
+    through :meth:`add_dataset`, ``freq_cov [pol, ew, ra, freq, freq_sum]`` float64, the lower factor of every
+    ``(pol, ew, ra)`` sample as one contiguous matrix; the ``freq_sum`` axis is a copy of ``freq``.  The complex form is
+    not provided."""
+
+    _axes = ("pol", "freq", "freq_sum", "ew", "ns", "ra")
+    _dataset_spec = {
+        "redundancy": {"axes": ["pol", "ew", "ns"], "dtype": np.int32},
+        "weight": {"axes": ["pol", "freq", "ew", "ra"], "dtype": np.float32},
+    }
+    _optional_spec = {"freq_cov": {"axes": ["pol", "ew", "ra", "freq", "freq_sum"], "dtype": np.float64}}
+    _complex_datasets = ("complex_freq_cov",)
+
+    def __init__(self, ra=None, **kwargs):
+        if isinstance(ra, (int, np.integer)):
+            ra = np.linspace(0.0, 360.0, int(ra), endpoint=False)
+        self._dataset_spec = dict(type(self)._dataset_spec)
+        super().__init__(ra=ra, **kwargs)
+
+    def add_dataset(self, name, allocate=False):
+        if name in self._complex_datasets:
+            raise NotImplementedError(f"FreqNoiseModel: the dataset {name!r} is not provided (complex covariances are not supported)")
+        self._dataset_spec[name] = self._optional_spec[name]
+        if "freq_sum" not in self.index_map:
+            self.index_map["freq_sum"] = self.index_map["freq"]  # (a copy of the frequency axis: the second index of a matrix)
+            self.index_attrs.setdefault("freq_sum", {})
+        if allocate:
+            self.datasets[name] = Dataset(host=np.zeros(self.dataset_shape(name), dtype=self._optional_spec[name]["dtype"]))
+
+    @property
+    def ra(self):
+        return self.index_map["ra"]
+
+    @property
+    def redundancy(self):
+        return self.datasets["redundancy"]
+
+    @property
+    def weight(self):
+        return self.datasets["weight"]
+
+    @property
+    def freq_cov(self):
+        return self._optional("freq_cov")
+
+    @property
+    def complex_freq_cov(self):
+        raise NotImplementedError("FreqNoiseModel: complex noise covariances are not supported")
+
+
 class HybridVisMModes(MContainer, _FreqMixin, _VisMixin):
     """m-mode transformed hybrid visibilities: ``vis [m, msign, pol, freq, ew, el]`` **complex64**,
     ``vis_weight [m, msign, pol, freq, ew]`` **float32** (``containers.py:1550-1574``)."""

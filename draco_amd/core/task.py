@@ -15,6 +15,10 @@ class PipelineStopIteration(Exception):
     """Raised by a task's ``process`` when it has nothing more to produce (caput's ``PipelineStopIteration`` [3P])."""
 
 
+class CaputConfigError(Exception):
+    """A task's configuration does not fit what it was given (caput's ``config.CaputConfigError`` [3P])."""
+
+
 class ContainerTask:
     _config_names: tuple = ()
 

@@ -640,6 +640,43 @@ int dmm_hyfores_gain(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int n
 int dmm_hyfores_window(dmm_ctx* ctx, int npol, int nfreq, int new_, int nel, int nra, const double* filter, const void* vis, const void* post,
                        const float* weight, const uint8_t* elm, const uint8_t* pix, double* partial, double* window);
 
+/* Frequency-correlated noise (draco/analysis/ringmapmaker.py:1318-1712, draco/synthesis/noise.py:377-470),
+ * csrc/noisemodel.hip.  All arrays [dev].  cov [npol][nfreq][nfreq][new][nra] float64 (real covariances only), scale
+ * [npol][nfreq][nfreq][new] float64, weight / weight_out [npol][nfreq][new][nra] float32.  1 <= nfreq <= 1024,
+ * npol * new <= 65535.  A sample is s = (pol new + ew) nra + ra; a call takes the nsample <= 65535 samples from `first`
+ * on, and no result depends on how the samples are split over calls.  A channel is valid where weight > 0.
+ *
+ * dmm_noisemodel_pack: G [nsample][nfreq][nfreq], upper triangle only: G[i][j] = cov[j][i] scale[j][i] (the input's lower
+ *   triangle) where i and j are valid, the identity's entry where one is not; weight_out[f] = inz(G[f][f]) rounded to
+ *   float32, 0 on invalid channels.
+ * dmm_noisemodel_factor: G = U^T U in place (upper triangle); status [nsample] int32 is cleared, then set to
+ *   DMM_NOISE_NOT_POSDEF where a pivot is not positive.
+ * dmm_noisemodel_store: freq_cov [npol][new][nra][nfreq][nfreq] (the whole array; the call writes its samples):
+ *   [r][c] = U[c][r] for c <= r both valid, 0 elsewhere and in every sample whose status is set.
+ * dmm_noisemodel_weight: vis_weight [nfreq][nstack][nra] float32 = float(nbaseline[stack] (double(weight[p][f][x][ra])
+ *   noise_factor[p][f][x])) with p new + x = cell[stack] (int32), 0 where cell[stack] < 0; noise_factor [npol][nfreq][new]
+ *   and nbaseline [nstack] float64.
+ * dmm_noise_colour, for the slab (pol, ew): vis[pol][f][ew][ns][ra] = (sum_{k <= f} chol[pol][ew][ra][f][k] z[ra][k][ns])
+ *   inv_sqrt_red[pol][ew][ns], z [nra][nfreq][nns] complex64, sums in float64 with k ascending, rounded once to
+ *   complex64 (chol is taken as lower triangular: its strict upper triangle is not read);
+ *   vis_weight[pol][f][ew][ns][ra] = float(double(weight[pol][f][ew][ra]) redundancy[pol][ew][ns]).  chol is
+ *   the whole [npol][new][nra][nfreq][nfreq] array, vis / vis_weight the whole [npol][nfreq][new][nns][nra] arrays,
+ *   redundancy int32 and inv_sqrt_red float64 [npol][new][nns].
+ * dmm_noise_hermitian, in place on ew = 0, nns odd: vis[pconj[p]][f][0][nns - k][ra] = conj(vis[p][f][0][k][ra]) for
+ *   k = 1 ... nns / 2, and where pconj[p] == p the auto k = 0 becomes (sqrt(2) Re, 0) in float32; pconj [npol] int32 with
+ *   entries in 0 ... npol - 1; npol * nfreq <= 65535. */
+enum { DMM_NOISE_OK = 0, DMM_NOISE_NOT_POSDEF = 1 };
+int dmm_noisemodel_pack(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int64_t first, int nsample, const double* cov, const double* scale, const float* weight,
+                        double* G, float* weight_out);
+int dmm_noisemodel_factor(dmm_ctx* ctx, int nfreq, int nsample, double* G, int32_t* status);
+int dmm_noisemodel_store(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int64_t first, int nsample, const double* G, const float* weight, const int32_t* status,
+                         double* freq_cov);
+int dmm_noisemodel_weight(dmm_ctx* ctx, int npol, int nfreq, int new_, int nra, int nstack, const float* weight, const double* noise_factor, const int32_t* cell,
+                          const double* nbaseline, float* vis_weight);
+int dmm_noise_colour(dmm_ctx* ctx, int npol, int nfreq, int new_, int nns, int nra, int pol, int ew, const double* chol, const void* z, const float* weight,
+                     const int32_t* redundancy, const double* inv_sqrt_red, void* vis, float* vis_weight);
+int dmm_noise_hermitian(dmm_ctx* ctx, int npol, int nfreq, int new_, int nns, int nra, const int32_t* pconj, void* vis);
+
 /* Delay spectrum estimators (draco/analysis/delay.py:347-1106, 2102-2201), csrc/delay.hip.  All arrays [dev] unless
  * noted, everything float64.  ndelay = N; order = N in the real time domain, 2 N (alternating real and imaginary) in
  * the complex one; nchan channels with indices chan [nchan] int32 in the full set; baselines are batched, at most
