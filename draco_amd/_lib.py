@@ -156,6 +156,8 @@ _SIGS = {
     "dmm_dayenu_build": (_i,[_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dmm_dayenu_mask": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
     "dmm_dayenu_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, C.POINTER(dmm_dayenu_side), C.POINTER(dmm_dayenu_side)]),
+    "dmm_nullfilter_build": (_i, [_vp, _i, _i, _i, _vp, _i, _d] + [_vp] * 9),
+    "dmm_nullfilter_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(dmm_dayenu_side), _vp]),
     "dmm_dayenu_hybrid_mask": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dmm_dayenu_hybrid_save": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "dmm_dayenu_hybrid_cov": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),

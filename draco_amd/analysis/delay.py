@@ -7,6 +7,7 @@ Drop-in for the frequency-to-delay transforms of ``draco/analysis/delay.py``:
 * :class:`DelaySpectrumFFT`, :class:`DelaySpectrumWienerFilter`, :class:`DelaySpectrumWienerFilterIteratePS`   ``delay.py:347-1053``
 * :class:`DelaySpectrumToPowerSpectrum`                                                  ``delay.py:1061-1106``
 * :class:`DelayPowerSpectrumBase`, :class:`DelayPowerSpectrumNRML`                        ``delay.py:744-818, 1114-1215, 1270-1301``
+* :class:`DelayFilter`, :class:`DelayFilterBase` (the delay null-space filter)             ``delay.py:29-339``
 
 Same names, config attributes, defaults and ``setup`` / ``process`` signatures.  The arithmetic runs in
 ``libdraco_amd.so`` (``csrc/delay.hip``), batched over baselines: a prepare pass (the ``time_frac`` / ``freq_frac``
@@ -24,9 +25,15 @@ The transform needs the whole band in one process: frequency sharding does not a
 
 Out of scope (``NotImplementedError`` where a parameter asks for it): ``use_average_weights=False`` (the reference's
 Wiener function cannot take per-sample weights either) and ``scale_freq=True``; not provided: the Gibbs and
-cross-spectrum estimators and ``DelayFilter`` / ``DelayFilterBase``.  The NRML estimator's optimiser and evaluators are in
+cross-spectrum estimators.  The NRML estimator's optimiser and evaluators are in
 :mod:`draco_amd.analysis.delayopt`.  (The ``DelayTransformOperator`` container and the
 Wiener delay transform of a filtered ring map that fills it are in ``draco_amd.analysis.powerspec``.)
+
+The two filter tasks project every item (a stack entry, an ``el`` of a ring map) onto the null space of the
+delays below its cut: a mask pass and a batched Jacobi SVD in ``csrc/nullfilter.hip`` (``draco_amd.util.filters``),
+then the in-place product of ``csrc/dayenu.hip``; the datasets stay on the device.  Of ``DelayFilterBase``'s four
+default containers the ``HybridVisMModes`` / ``m`` and ``GridBeam`` / ``theta`` layouts, and any non-default ``axis``,
+raise ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -34,13 +41,14 @@ from __future__ import annotations
 import ctypes as C
 
 import numpy as np
+import scipy.constants
 import torch
 
 from .. import _lib
-from ..core import containers
+from ..core import containers, io
 from ..core.task import ContainerTask
 from ..device import Context, ptr
-from ..util import tools
+from ..util import filters, tools
 from .transform import _dev_dataset
 
 MAX_ORDER = 2048
@@ -690,3 +698,239 @@ __all__ = [
     "fourier_matrix_c2r",
     "fourier_matrix_r2c",
 ]
+
+
+# ---- the delay null-space filter (``delay.py:29-339``)
+
+
+def null_filter_plan(freq, cuts, flags):
+    """Which filters a container needs: ``(cut [nuniq], num_modes [nuniq], mask [nuniq, nfreq], index [nitem])``.
+
+    ``cuts [nitem]``: the delay cut of every item in micro-seconds, ``flags [nitem, nfreq]``: its frequency mask.
+    ``num_modes = int(4 ptp(freq) cut + 0.5)``, as the DAYENU paper recommends and the reference uses.  Items with equal
+    ``(cut, mask)`` share one filter, numbered in order of first use."""
+    freq = np.asarray(freq, dtype=np.float64)
+    bandwidth = np.ptp(freq)
+    keys, cut_u, k_u, mask_u = {}, [], [], []
+    index = np.empty(len(cuts), dtype=np.int64)
+    for it, cut in enumerate(cuts):
+        key = (float(cut), flags[it].tobytes())
+        if key not in keys:
+            keys[key] = len(cut_u)
+            cut_u.append(float(cut))
+            k_u.append(int(4.0 * bandwidth * float(cut) + 0.5))
+            mask_u.append(flags[it])
+        index[it] = keys[key]
+    return np.asarray(cut_u), np.asarray(k_u, dtype=np.int64), np.asarray(mask_u, dtype=np.uint8).reshape(len(cut_u), freq.size), index
+
+
+class _NullFilterTask(ContainerTask):
+    """What the two tasks share: mask pass, filter sharing, batched build, apply."""
+
+    _config_names = ("delay_cut", "window", "workspace_mib")
+    delay_cut = 0.1
+    window = False
+    workspace_mib = 1024  # device memory the filters of one batch and their factors may take
+
+    def _filter(self, ctx, dtype, wdtype, layout, freq, cuts, ninner, nouter, datas, weight, join=False):
+        """``cuts [nouter * ninner]``: delay cut of every item.  ``datas``: one side per beam; ``weight``: the side the
+        masks come from, multiplied by them in place; ``join``: the ``nouter`` items of one inner index are one item of the
+        reference (one mask pair from the samples of all of them)."""
+        from .dayenu import _GROUP, apply_filters
+
+        freq = np.ascontiguousarray(freq, dtype=np.float64)
+        nfreq, nitem = freq.size, ninner * nouter
+        if not 1 <= nfreq <= filters.NULL_MAX_ORDER:
+            raise ValueError(f"{type(self).__name__}: {nfreq} frequencies, the kernels take 1 ... {filters.NULL_MAX_ORDER}")
+        flag_d = ctx.empty((nouter, ninner, nfreq), np.uint8)
+        _lib.check(_lib.lib.dmm_nullfilter_mask(ctx.handle, wdtype, layout, nfreq, ninner, nouter, int(join), C.byref(weight), ptr(flag_d)))
+        flags = flag_d.cpu().numpy().reshape(nitem, nfreq)
+        ctx.uses(flag_d)
+        cut_u, k_u, mask_u, imat = null_filter_plan(freq, cuts, flags)
+        nuniq = len(cut_u)
+        self.log.debug(f"{nitem} items, {nuniq} distinct filters.")
+        if nuniq == 0:
+            return
+        window = filters.null_filter_window(freq, self.window)
+        freq_d = ctx.to_device(freq)
+        group = _GROUP[dtype]
+        ngroup = (ninner + group - 1) // group
+        per = max(1, min(65535, (int(self.workspace_mib) << 20) // (8 * nfreq * (nfreq + int(k_u.max())))))
+        for m0 in range(0, nuniq, per):
+            m1 = min(nuniq, m0 + per)
+            nf, status, _, _ = filters.build_null_filters(ctx, freq_d, cut_u[m0:m1], k_u[m0:m1], mask_u[m0:m1], window, workspace_mib=self.workspace_mib)
+            sel = np.flatnonzero((imat >= m0) & (imat < m1))
+            if status.any():
+                bad = sel[status[imat[sel] - m0] != 0][0]
+                raise RuntimeError(f"Failed to converge while processing baseline {bad % ninner}")
+            local = np.full(nitem, -1, dtype=np.int32)
+            local[sel] = imat[sel] - m0
+            if layout == _lib.DMM_DAYENU_COLS:
+                units = sel.astype(np.int32)
+            else:
+                units = np.unique((sel // ninner) * ngroup + (sel % ninner) // group).astype(np.int32)
+            units_d, local_d = ctx.to_device(units), ctx.to_device(local)
+            for data in datas:
+                apply_filters(ctx, dtype, layout, nfreq, ninner, nouter, nf, local_d, None, units_d, len(units), data, None)
+            ctx.uses(nf, units_d, local_d)
+        ctx.uses(freq_d)
+
+
+def _real_code(t):
+    return _lib.DMM_DAYENU_F64 if t.dtype in (torch.float64, torch.complex128) else _lib.DMM_DAYENU_F32
+
+
+class DelayFilter(_NullFilterTask):
+    """Remove delays less than a given threshold (``delay.py:29-153``).
+
+    The data are projected onto the null space that is orthogonal to any mode at low delays.  For this to work best
+    the zero entries of the weights should factorise in frequency and time for each baseline.
+
+    Attributes
+    ----------
+    delay_cut : float
+        Delay value to filter at, in micro-seconds.  Default 0.1.
+    za_cut : float
+        Sine of the maximum zenith angle included in baseline-dependent delay filtering.  Default 1.0 (the horizon);
+        zero turns the baseline-dependent cut off.
+    extra_cut : float
+        Increase the delay threshold beyond the baseline-dependent term.  Default 0.
+    weight_tol : float
+        Unused, as in the reference.  Default 1e-4.
+    telescope_orientation : one of ('NS', 'EW', 'none')
+        Whether the baseline-dependent delay cut is based on the north-south component, the east-west component or the
+        full baseline length.  Default 'NS'.
+    window : bool
+        Apply the window function to the data when applying the filter.  Default False.
+
+    The delay cut applied is ``max(za_cut * baseline / c + extra_cut, delay_cut)``.  Works in place on a
+    ``SiderealStream`` or ``TimeStream`` and returns it with device-resident ``vis`` (complex64, or complex128 if it
+    came so) and ``vis_weight``.  Per stack entry the frequencies, and the samples, with the most positive weights stay
+    (``f_mask``, ``t_mask``); the weights are multiplied by both masks.  Entries with the same cut and ``f_mask`` share
+    one filter.  ``RuntimeError`` if the SVD of a filter does not converge.  The whole band must be in this process.
+    """
+
+    _config_names = ("za_cut", "extra_cut", "weight_tol", "telescope_orientation")
+    za_cut = 1.0
+    extra_cut = 0.0
+    weight_tol = 1e-4
+    telescope_orientation = "NS"
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.telescope_orientation not in ("NS", "EW", "none"):
+            raise ValueError(f"telescope_orientation must be 'NS', 'EW' or 'none', not {self.telescope_orientation!r}")
+
+    def setup(self, telescope):
+        """Set the telescope needed to obtain baselines."""
+        self.telescope = io.get_telescope(telescope)
+
+    def _cuts(self, prod):
+        """The delay cut of every stack entry, in micro-seconds."""
+        pos = self.telescope.feedpositions
+        baselines = pos[np.asarray(prod["input_a"], dtype=np.int64)] - pos[np.asarray(prod["input_b"], dtype=np.int64)]
+        if self.telescope_orientation == "NS":
+            baselines = abs(baselines[:, 1])  # Y baseline
+        elif self.telescope_orientation == "EW":
+            baselines = abs(baselines[:, 0])  # X baseline
+        else:
+            baselines = np.linalg.norm(baselines, axis=-1)  # Norm
+        return np.maximum(self.za_cut * baselines / scipy.constants.c * 1e6 + self.extra_cut, self.delay_cut)
+
+    def process(self, ss):
+        """Filter out delays from a SiderealStream or TimeStream, in place."""
+        from .dayenu import _side
+
+        ss.redistribute(["input", "prod", "stack"])
+        ctx = Context.get()
+        cuts = self._cuts(ss.prodstack)
+        vis = _dev_dataset(ss.vis, ctx, np.complex128 if np.dtype(ss.vis.dtype) == np.complex128 else np.complex64)
+        weight = _dev_dataset(ss.weight, ctx, np.float32)
+        nfreq, nstack, nt = (int(s) for s in vis.shape)
+        if len(cuts) != nstack:
+            raise ValueError(f"{len(cuts)} products for {nstack} stack entries")
+        data = _side(vis, 2 * nt, 2 * nstack * nt, 1, 2 * nt, 0)
+        wside = _side(weight, nt, nstack * nt, 1, nt, 0)
+        self._filter(ctx, _real_code(vis), _lib.DMM_DAYENU_F32, _lib.DMM_DAYENU_COLS, ss.freq[:], cuts, nstack, 1, [data], wside)
+        ss.vis.set_device(vis)
+        ss.weight.set_device(weight)
+        return ss
+
+
+class DelayFilterBase(_NullFilterTask):
+    """Remove delays less than a given threshold (``delay.py:156-339``).
+
+    Attributes
+    ----------
+    delay_cut : float
+        Delay value to filter at, in micro-seconds.  Default 0.1.
+    window : bool
+        Apply the window function to the data when applying the filter.  Default False.
+    axis : str
+        The main axis to iterate over; the delay cut can be varied for each element of it (:meth:`_delay_cut`).  If not
+        set, the default for the container type: ``stack`` for a ``SiderealStream``, ``el`` for a ``RingMap``.
+    dataset : str
+        Apply the delay filter to this dataset.  If not set, the default for the container type (``vis``, ``map``).
+
+    Works in place and returns the input container with the dataset and the weights on the device.  A ``RingMap`` has
+    one filter per ``el``, from the masks of the weights of both polarisations together (``f_samp`` counts the ``(pol,
+    ra)`` samples), as the reference's reshaping makes it; the weights have no beam axis: every beam and polarisation
+    is filtered with the same matrix and the weights are multiplied by the masks once.  ``TypeError`` for a container without a
+    frequency axis; ``NotImplementedError`` for ``HybridVisMModes`` and ``GridBeam`` (the reference's other two
+    defaults), for other containers, and for an ``axis`` or ``dataset`` other than the default: those layouts have no
+    apply path.  ``RuntimeError`` if the SVD of a filter does not converge.  The whole band must be in this process.
+    """
+
+    _config_names = ("axis", "dataset")
+    axis = None
+    dataset = None
+
+    _defaults = ((containers.SiderealStream, "stack", "vis"), (containers.HybridVisMModes, "m", "vis"), (containers.RingMap, "el", "map"), (containers.GridBeam, "theta", "beam"))
+
+    def setup(self, telescope=None):
+        """Set the telescope needed to obtain baselines (kept for subclasses that cut by baseline)."""
+        self.telescope = io.get_telescope(telescope) if telescope is not None else None
+
+    def _delay_cut(self, ss, axis, ind):
+        """Return the delay cut to use for entry ``ind`` of ``axis`` of the container, in micro-seconds."""
+        return self.delay_cut
+
+    def process(self, ss):
+        """Filter out delays from a SiderealStream or a RingMap, in place."""
+        from .dayenu import _side
+
+        if not isinstance(ss, containers._FreqMixin):
+            raise TypeError(f"Can only process FreqContainer instances. Got {type(ss)}.")
+        for cls, axis, dset in self._defaults:
+            if isinstance(ss, cls):
+                break
+        else:
+            raise NotImplementedError(f"DelayFilterBase: no default axis known for {type(ss).__name__} containers, and only the default layouts run on the GPU")
+        if (self.axis is not None and self.axis != axis) or (self.dataset is not None and self.dataset != dset):
+            raise NotImplementedError(f"DelayFilterBase: only axis {axis!r} and dataset {dset!r} of a {cls.__name__} have an apply path, not {self.axis!r} / {self.dataset!r}")
+        if cls not in (containers.SiderealStream, containers.RingMap):
+            raise NotImplementedError(f"DelayFilterBase: the {cls.__name__} layout (axis {axis!r}) has no apply path on the GPU")
+        ss.redistribute(axis)
+        ctx = Context.get()
+        nax = len(ss.index_map[axis])
+        cuts = np.array([float(self._delay_cut(ss, axis, ind)) for ind in range(nax)])
+        if cls is containers.SiderealStream:
+            vis = _dev_dataset(ss.vis, ctx, np.complex128 if np.dtype(ss.vis.dtype) == np.complex128 else np.complex64)
+            weight = _dev_dataset(ss.weight, ctx, np.float32)
+            nfreq, nstack, nt = (int(s) for s in vis.shape)
+            data = _side(vis, 2 * nt, 2 * nstack * nt, 1, 2 * nt, 0)
+            wside = _side(weight, nt, nstack * nt, 1, nt, 0)
+            self._filter(ctx, _real_code(vis), _lib.DMM_DAYENU_F32, _lib.DMM_DAYENU_COLS, ss.freq[:], cuts, nstack, 1, [data], wside)
+            ss.vis.set_device(vis)
+            ss.weight.set_device(weight)
+            return ss
+        rmap = _dev_dataset(ss.map, ctx, np.float32 if np.dtype(ss.map.dtype) == np.float32 else np.float64)
+        weight = _dev_dataset(ss.weight, ctx, np.float32 if np.dtype(ss.weight.dtype) == np.float32 else np.float64)
+        nbeam, npol, nfreq, nra, nel = (int(s) for s in rmap.shape)
+        plane = nfreq * nra * nel
+        datas = [_side(rmap[b], nra, nra * nel, nel, 1, plane) for b in range(nbeam)]
+        wside = _side(weight, nra, nra * nel, nel, 1, plane)
+        self._filter(ctx, _real_code(rmap), _real_code(weight), _lib.DMM_DAYENU_ITEMS, ss.freq[:], np.tile(cuts, npol), nel, npol, datas, wside, join=True)
+        ss.map.set_device(rmap)
+        ss.weight.set_device(weight)
+        return ss

@@ -1,9 +1,15 @@
-"""Masked moving median on the GPU (``draco/util/filters.py:99-130``).
+"""Masked moving median (``draco/util/filters.py:99-130``) and the delay null-space filter
+(``draco/util/filters.py:133-212``) on the GPU.
 
 ``medfilt`` wraps caput's ``moving_weighted_median`` [3P] in the reference; here it is ``dmm_rfi_medfilt``
 (``csrc/rfi.hip``) under the conventions of DESIGN.md section 7i: the window is centred on the sample and clipped at
 the array's edge, the result is ``0.5 * (v[(n-1)//2] + v[n//2])`` of the ``n`` unmasked samples ``v`` of the window in
 ascending order and NaN for an empty window.  Window sizes are odd.  Only 0/1 weights exist: a sample is masked or not.
+
+``null_filter`` projects out (or keeps) the span of the Fourier modes ``exp(2 pi i f s)``, ``f = linspace(-cutoff,
+cutoff, num_modes)``, on the unmasked samples: ``dmm_nullfilter_build`` (``csrc/nullfilter.hip``)
+takes the SVD of the real form of that matrix by a batched one-sided Jacobi in float64.  :func:`build_null_filters` is
+the batched form the tasks of ``draco_amd.analysis.delay`` use.
 """
 
 from __future__ import annotations
@@ -88,3 +94,120 @@ def medfilt(x, mask, size, *args):
     if ndim == 1:
         out = out.reshape(-1)
     return out if is_tensor else out.cpu().numpy()
+
+
+# ---- the delay null-space filter
+
+NULL_MAX_ORDER = 1024  # samples, and Fourier modes, of one filter
+
+
+def null_filter_window(samples, window):
+    """The window ``null_filter`` applies, ``[n]`` float64 on the host: ``True`` is 'nuttall', a false value is no
+    window (``None``)."""
+    if isinstance(window, (bool, np.bool_)) or window is None:
+        if not window:
+            return None
+        window = "nuttall"
+    from ..analysis.delay import _window_coef
+
+    samples = np.asarray(samples, dtype=np.float64)
+    return np.ascontiguousarray(_window_coef((samples - samples.min()) / np.ptp(samples), str(window)))
+
+
+def _check_null_modes(num_modes):
+    num_modes = int(num_modes)
+    if num_modes < 1:
+        raise ValueError(f"null_filter: num_modes must be positive, got {num_modes} (the cutoff is too small for the bandwidth: 4 x bandwidth x cutoff < 0.5)")
+    if num_modes == 1:
+        raise NotImplementedError(
+            "null_filter: num_modes == 1 leaves the single, unpaired mode exp(2 pi i cutoff s), which makes the filter genuinely complex; "
+            "only the real filters of two or more modes (symmetric about zero delay) run on the GPU"
+        )
+    if num_modes > NULL_MAX_ORDER:
+        raise ValueError(f"null_filter: {num_modes} modes, the kernels take 2 ... {NULL_MAX_ORDER}")
+    return num_modes
+
+
+def build_null_filters(ctx, samples_d, cutoffs, num_modes, masks, window=None, tol=1e-8, type_="high", workspace_mib=1024, info=None):
+    """Build one filter per ``(cutoffs[m], num_modes[m], masks[m])``.
+
+    ``samples_d [n]``: float64 on the device; ``cutoffs [nmat]``, ``num_modes [nmat]`` (or one integer) and ``masks
+    [nmat, n]`` (non-zero: sample kept) on the host; ``window``: the ``[n]`` float64 coefficients on the host
+    (:func:`null_filter_window`) or ``None``.  Returns ``(nf, status, nkeep, sig)``: ``nf [nmat, n, n]`` float64 on the
+    device, and on the host ``status [nmat]`` (non-zero: the Jacobi sweeps of that matrix did not converge, its filter
+    is not to be used), ``nkeep [nmat]`` (singular values above ``tol`` times the largest) and ``sig [nmat, max
+    num_modes]`` (the singular values in descending order, zero beyond a matrix's own ``num_modes``).  Matrices with
+    different ``num_modes`` go through ``dmm_nullfilter_build`` together (one block per matrix), in chunks whose factors
+    fit ``workspace_mib``.
+    ``info``: a dict that receives ``sweeps [nmat]``."""
+    masks = np.ascontiguousarray(np.asarray(masks) != 0).view(np.uint8)
+    nmat, n = masks.shape
+    cutoffs = np.asarray(cutoffs, dtype=np.float64).reshape(nmat)
+    kk = np.broadcast_to(np.asarray(num_modes, dtype=np.int64), (nmat,))
+    for k in np.unique(kk):
+        _check_null_modes(k)
+    if not 1 <= n <= NULL_MAX_ORDER:
+        raise ValueError(f"null_filter: {n} samples, the kernels take 1 ... {NULL_MAX_ORDER}")
+    if type_ not in {"high", "low"}:
+        raise ValueError(f"Filter type must be one of [high, low]. Got {type_}")
+    kmax = int(kk.max()) if nmat else 0
+    nf = ctx.empty((nmat, n, n), np.float64)
+    status, nkeep, sweeps = (np.zeros(nmat, dtype=np.int32) for _ in range(3))
+    sig = np.zeros((nmat, kmax), dtype=np.float64)
+    window_d = ctx.to_device(np.ascontiguousarray(window, dtype=np.float64)) if window is not None else None
+    per = max(1, min(65535, (int(workspace_mib) << 20) // (8 * max(kmax, 1) * n)))
+    for m0 in range(0, nmat, per):
+        m1 = min(nmat, m0 + per)
+        nm, kp = m1 - m0, int(kk[m0:m1].max())
+        modes = np.zeros((nm, kp), dtype=np.float64)
+        for r in range(nm):
+            modes[r, : kk[m0 + r]] = np.linspace(-cutoffs[m0 + r], cutoffs[m0 + r], int(kk[m0 + r]))
+        modes_d, masks_d, kk_d = ctx.to_device(modes), ctx.to_device(np.ascontiguousarray(masks[m0:m1])), ctx.to_device(kk[m0:m1].astype(np.int32))
+        sig_d = ctx.empty((nm, kp), np.float64)
+        words = ctx.zeros((3, nm), np.int32)
+        _lib.check(
+            _lib.lib.dmm_nullfilter_build(
+                ctx.handle, int(n), int(nm), kp, ptr(kk_d), int(type_ == "low"), float(tol), ptr(samples_d), ptr(modes_d), ptr(masks_d), ptr(window_d), ptr(nf[m0:m1]), ptr(sig_d),
+                ptr(words[0]), ptr(words[1]), ptr(words[2]),
+            )
+        )
+        w = words.cpu().numpy()
+        nkeep[m0:m1], status[m0:m1], sweeps[m0:m1] = w[0], w[1], w[2]
+        sig[m0:m1, :kp] = -np.sort(-sig_d.cpu().numpy(), axis=1)
+        ctx.uses(modes_d, masks_d, kk_d, sig_d, words)
+    ctx.uses(window_d)
+    if info is not None:
+        info["sweeps"] = sweeps
+    return nf, status, nkeep, sig
+
+
+def null_filter(samples, cutoff, mask, num_modes=200, tol=1e-8, window=True, type_="high", lapack_driver="gesvd", device=True):
+    """Create a high-pass or low-pass filter by nulling Fourier modes (``filters.py:133-212``).
+
+    ``samples [n]``: where there is data (at most 1024); ``cutoff``: the Fourier-inverse cut; ``mask [n]``: non-zero
+    where a sample is kept (as in the reference, whose tasks pass ``f_mask``); ``num_modes``: Fourier modes in
+    ``[-cutoff, cutoff]``; ``tol``: relative cut on the singular values; ``window``: ``True`` ('nuttall'), a window name,
+    or a false value; ``type_``: 'high' or 'low'.  ``lapack_driver`` is accepted and ignored (the SVD is a Jacobi on the
+    device).  Returns the ``[n, n]`` filter, a float64 tensor **on the device**, or a NumPy array with
+    ``device=False``.
+
+    The filter is real.  The reference returns a complex array, but its modes are symmetric about zero, so ``F F^H`` and
+    the projector are real and the imaginary part it carries (2e-9 ... 5e-8 in the cases tried) is the rounding error
+    of its complex SVD, not signal.  ``num_modes == 1`` is the exception (one unpaired mode, a genuinely complex
+    filter): ``NotImplementedError``.  Mask and window multiply the filter's columns only; the rows of masked samples
+    come out zero because the basis is zero there.  ``numpy.linalg.LinAlgError`` if the sweeps do not converge.
+    """
+    if type_ not in {"high", "low"}:
+        raise ValueError(f"Filter type must be one of [high, low]. Got {type_}")
+    num_modes = _check_null_modes(num_modes)
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    mask = np.asarray(mask)
+    if samples.ndim != 1 or mask.shape != samples.shape:
+        raise ValueError(f"null_filter: samples {samples.shape} and mask {mask.shape} must be one-dimensional and alike")
+    ctx = Context.get()
+    samples_d = ctx.to_device(samples)
+    nf, status, _, _ = build_null_filters(ctx, samples_d, [float(cutoff)], num_modes, mask[np.newaxis, :], null_filter_window(samples, window), tol=tol, type_=type_)
+    ctx.uses(samples_d)
+    if status[0]:
+        raise np.linalg.LinAlgError("null_filter: the Jacobi SVD did not converge")
+    return nf[0] if device else nf[0].cpu().numpy()

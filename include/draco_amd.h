@@ -571,6 +571,36 @@ int dmm_dayenu_apply(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner,
                      const int32_t* item_matrix, const uint8_t* atten, const int32_t* units, int64_t nunit,
                      const dmm_dayenu_side* data, const dmm_dayenu_side* weight);
 
+/* Delay null-space filter (draco/util/filters.py:133-212, draco/analysis/delay.py:29-339), csrc/nullfilter.hip.
+ *
+ * dmm_nullfilter_build: nmat filters of order nfreq (1 ... 1024) in one launch, one block per matrix.  num_modes (2 ...
+ * 1024) is the pitch of the per-matrix tables; nmodes [nmat] int32 [dev] holds each matrix's own number of Fourier modes
+ * (2 ... num_modes; anything else sets status 2 and leaves nf of that matrix with no mode projected), NULL: all num_modes.
+ * samples [nfreq] float64, modes [nmat][num_modes] float64 = numpy.linspace(-cutoff, cutoff, num_modes) of each matrix
+ * (ascending and symmetric about zero: only the positive half of the first nmodes entries is read), mask [nmat][nfreq] bytes (non-zero: channel
+ * kept), window [nfreq] float64 or NULL, all [dev].  Per matrix the real form Fr [nfreq][num_modes] of the masked,
+ * windowed Fourier matrix (columns sqrt2 cos / sqrt2 sin of the positive modes, ones for the zero mode of an odd
+ * num_modes) is factored by a one-sided Jacobi SVD in float64; sig [nmat][num_modes] [dev] = its singular values (in
+ * the order the columns end in, which is not sorted), nkeep [nmat] int32 [dev] = #(sig > tol max sig),
+ * U = the left singular vectors of those, and nf [nmat][nfreq][nfreq] [dev] = (I - U U^T) o (1 x mask) o (1 x window)
+ * for low = 0, (U U^T) o (1 x mask) o (1 x window) for low = 1: mask and window scale the columns only.  status [nmat]
+ * int32 [dev]: 0, or 1 where the sweeps did not converge within the cap of 60 (nf of that matrix is not to be used).
+ * sweeps [nmat] int32 [dev] or NULL: the sweeps each matrix took.  nmat num_modes nfreq float64 of the context's
+ * scratch hold the factors.
+ *
+ * dmm_nullfilter_mask: the weight as a dmm_dayenu_side (above), dtype and layout as for dmm_dayenu_mask.  Per item
+ * f_samp[f] = #c(weight > 0), flag [nouter][ninner][nfreq] bytes [dev] = (f_samp == max_f f_samp), t_mask[c] likewise
+ * from t_samp[c] = #f(weight > 0), and weight *= flag x t_mask in place (an item without weight keeps both masks full
+ * and its zeros).  join_outer = 1: the nouter items of one inner index are one item with nouter ncol samples (the two
+ * polarisations of a ring map's el): f_samp is summed over them, both maxima are joint, and they get the same flag.
+ * nitem (nfreq + ncol) int32 of the context's scratch hold the counts.
+ *
+ * The filters are applied with dmm_dayenu_apply (weight and atten NULL). */
+int dmm_nullfilter_build(dmm_ctx* ctx, int nfreq, int nmat, int num_modes, const int32_t* nmodes, int low, double tol, const double* samples, const double* modes,
+                         const uint8_t* mask, const double* window, double* nf, double* sig, int32_t* nkeep, int32_t* status, int32_t* sweeps);
+int dmm_nullfilter_mask(dmm_ctx* ctx, int dtype, int layout, int nfreq, int ninner, int nouter, int join_outer, const dmm_dayenu_side* weight,
+                        uint8_t* flag);
+
 /* DAYENU filter of hybrid beam-formed visibilities (draco/analysis/dayenu.py:407-572) and the east-west averages of
  * RADependentWeights (draco/analysis/ringmapmaker.py:1202-1315), csrc/dayenu_hybrid.hip.  All arrays [dev]; weight is
  * the stream's vis_weight [npol][nfreq][new][nra] float32, and there is one filter per (ew, ra) sample: item_matrix
