@@ -46,6 +46,9 @@ DMM_GP_GAUSSIAN, DMM_GP_RATIONAL, DMM_GP_MATERN15, DMM_GP_MATERN25 = 0, 1, 2, 3
 DMM_GP_OK, DMM_GP_NOT_POSDEF = 0, 1
 DMM_RFI_MAX_WINDOW, DMM_RFI_MAX_STRIP, DMM_RFI_MAX_ROW, DMM_RFI_MAX_ST_WINDOW = 255, 8192, 16384, 4096
 DMM_RFI_OR, DMM_RFI_SELECT = 0, 1
+DMM_RFI_WMED_MAX_WINDOW, DMM_RFI_WMED_MAX_STRIP, DMM_RFI_WMED_TILE = 1023, 8192, 64
+DMM_REDUCE_CHISQ, DMM_REDUCE_VAR_NONE, DMM_REDUCE_VAR_MASKED, DMM_REDUCE_VAR_WEIGHTED, DMM_REDUCE_WMEAN = 0, 1, 2, 3, 4
+DMM_REDUCE_F32, DMM_REDUCE_F64, DMM_REDUCE_C64, DMM_REDUCE_C128 = 0, 1, 2, 3
 DMM_SENS_MAX_GROUP = 64
 DMM_PS_MAX_BINS = 4096
 DMM_STACK_SRC_CHUNK, DMM_STACK_MAX_FREQ = 256, 2048
@@ -206,6 +209,9 @@ _SIGS = {
     "dmm_gp_compact": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmm_gp_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i] + [_vp] * 15),
     "dmm_rfi_medfilt": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dmm_rfi_wmedfilt": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dmm_rfi_wdev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dmm_axis_reduce": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i64, _i64, _d, _vp, _vp]),
     "dmm_rfi_quantile": (_i, [_vp, _vp, _vp, _i64, _i, _d, _vp, _vp]),
     "dmm_rfi_sumthreshold": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "dmm_rfi_sir": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp]),

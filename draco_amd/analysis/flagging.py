@@ -8,7 +8,9 @@ in-place semantics (the input container is returned with its weights zeroed).  I
 
 The RFI part (``flagging.py:1808-2377`` and ``:3231-3381``): ``RFISensitivityMask``, ``RFIMask`` and
 ``ApplyTimeFreqMask`` (alias ``ApplyRFIMask``), ``NegativeAutosMask`` (``:666-699``), with the functions ``mad``,
-``tv_channels_flag``, ``sigma_to_p``, ``p_to_sigma`` and ``inverse_binom_cdf_prob``.  The planes stay on the device across the iterations of a mask task:
+``tv_channels_flag``, ``sigma_to_p``, ``p_to_sigma`` and ``inverse_binom_cdf_prob``; and ``RFIMaskChisqHighDelay``
+(``:1425-1805``), the mask from a chi-squared test statistic, whose medians are weighted (``dmm_rfi_wmedfilt``, DESIGN.md
+section 7s).  The planes stay on the device across the iterations of a mask task:
 medians, SumThreshold, SIR and the elementwise stages are the kernels of ``csrc/rfi.hip``; only scalars (the TV
 thresholds, from SciPy) and the frequency-length arrays of the static channel mask are formed on the host.  The
 convention is ``True`` for contaminated samples.
@@ -24,11 +26,11 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..core import containers
+from ..core import containers, io
 from ..core.task import ContainerTask
 from ..device import Context, ptr
-from ..util import filters, rfi
-from .transform import _dev_dataset
+from ..util import filters, rfi, tools
+from .transform import _dev_dataset, axis_reduce_device
 
 
 def _prodstack(cont):
@@ -440,6 +442,245 @@ class RFISensitivityMask(ContainerTask):
         seed = mask & ~np.asarray(baseflag, dtype=bool)[:, None]
         along = (-1,) if self.only_time else (0, -1)
         return mask | rfi.scale_invariant_rank(seed, eta=self.eta, axis=along)
+
+
+class RFIMaskChisqHighDelay(ContainerTask):
+    """Mask frequencies and times with an anomalous chi-squared test statistic (drop-in for ``flagging.py:1425-1805``).
+
+    The input holds a chi-squared per degree of freedom in its visibility (or map) dataset and the number of degrees of
+    freedom in its weight, as ``ReduceChisq`` leaves them after a delay filter.  Every axis that is neither frequency
+    nor time / RA (nor ``pol`` with ``separate_pol``) is averaged away with the weights; then whole channels are dropped
+    whose median over time lies far from a smooth baseline over frequency (``mask_1d``), and samples that lie far from
+    the weighted moving median of the plane (``mask_2d``, or ``mask_2d_sumthreshold``).
+
+    Config (names and defaults are the reference's):
+
+    ``flag_ew`` (None)
+        multiplied into the weights along an ``ew`` axis before the average.
+    ``reg_arpls`` (1e5), ``nsigma_1d`` (5.0)
+        smoothness of the baseline over frequency, and the cut of the channel test in scaled MADs (0: no test).
+    ``win_t`` (601), ``win_f`` (1), ``nsigma_2d`` (5.0)
+        the window of the moving median, and the cut in expected standard deviations ``sqrt(2 / ndof)`` (0: no test).
+    ``estimate_var`` (False)
+        scale the deviations by their own moving MAD over the same window.
+    ``only_positive`` (False), ``separate_pol`` (False)
+        flag positive excursions only; one mask per polarisation.
+    ``mask_type`` ("mad"), ``niter`` (5), ``rho`` (1.5), ``max_m`` (32)
+        "mad" or "sumthreshold"; for the latter the passes, the factor between their thresholds, the largest window.
+
+    The collapse is ``dmm_axis_reduce``, the medians ``dmm_rfi_quantile`` and ``dmm_rfi_wmedfilt``; the plane stays on
+    the device across the iterations.  Only the baseline fit over the frequency axis (``tools.arPLS_1d``) and the hooks
+    run on the host.  An empty row's median enters the baseline fit as 0.0 (it carries no weight there); an empty
+    moving window gives NaN, and a NaN deviation is not flagged by the comparison.
+    """
+
+    flag_ew = None
+    reg_arpls = 1e5
+    nsigma_1d = 5.0
+    win_t = 601
+    win_f = 1
+    nsigma_2d = 5.0
+    estimate_var = False
+    only_positive = False
+    separate_pol = False
+    mask_type = "mad"
+    niter = 5
+    rho = 1.5
+    max_m = 32
+    _config_names = ("flag_ew", "reg_arpls", "nsigma_1d", "win_t", "win_f", "nsigma_2d", "estimate_var", "only_positive", "separate_pol", "mask_type", "niter", "rho",
+                     "max_m")
+
+    MAD_TO_RMS = 1.48625  # as the reference writes it here
+
+    telescope = None
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.mask_type not in ("mad", "sumthreshold"):
+            raise ValueError(f"mask_type must be 'mad' or 'sumthreshold', not {self.mask_type!r}")
+        if self.flag_ew is not None:
+            self.flag_ew = np.asarray(self.flag_ew)
+
+    def setup(self, telescope=None):
+        """``telescope``: only used to convert (LSD, RA) to UNIX time for sidereal streams."""
+        self.telescope = None if telescope is None else io.get_telescope(telescope)
+        if self.mask_type == "sumthreshold":
+            self.threshold = self.nsigma_2d * self.rho ** np.arange(self.niter)[::-1]
+
+    def process(self, stream):
+        """``TimeStream | SiderealStream | HybridVisStream | RingMap`` -> ``RFIMask | SiderealRFIMask | RFIMaskByPol |
+        SiderealRFIMaskByPol``, True where a sample is flagged."""
+        if self.mask_type == "sumthreshold" and not hasattr(self, "threshold"):
+            self.setup(self.telescope)
+        stream.redistribute("freq")
+        freq = stream.freq
+        sidereal = "ra" in stream.index_map
+
+        multiple_days = False
+        if sidereal:
+            if self.telescope is None:
+                raise RuntimeError("For sidereal streams, must provide telescope object during setup.")
+            csd = stream.attrs.get("lsd", stream.attrs.get("csd"))
+            if csd is None:
+                raise ValueError("Data does not have a `csd` or `lsd` attribute.")
+            if not np.isscalar(csd):
+                csd = np.floor(np.mean(csd))
+                multiple_days = True
+            timestamp = self.telescope.lsd_to_unix(csd + stream.ra / 360.0)
+        else:
+            timestamp = stream.time
+
+        ctx = Context.get()
+        data = stream.datasets["vis" if "vis" in stream.datasets else "map"]
+        dax = list(data.attrs["axis"])
+        separate_pol = bool(self.separate_pol) and "pol" in dax
+        chisq, wsum = self._collapse(ctx, stream, data, dax, separate_pol)  # [(pol,) freq, time] float64
+        nfreq, ntime = (int(s) for s in chisq.shape[-2:])
+        mask_input = wsum.eq(0.0).to(torch.uint8)
+
+        if multiple_days:
+            mask_daytime = np.zeros(timestamp.size, dtype=bool)
+        else:
+            mask_daytime = np.asarray(self._day_flag_hook(timestamp), dtype=bool)
+        mask_sources = _u8(ctx, np.broadcast_to(np.asarray(self._source_flag_hook(timestamp, freq), dtype=bool), (nfreq, ntime)))
+        day_rows = _u8(ctx, np.broadcast_to(mask_daytime, (nfreq, ntime)))
+
+        if separate_pol:
+            kind = containers.SiderealRFIMaskByPol if sidereal else containers.RFIMaskByPol
+        else:
+            kind = containers.SiderealRFIMask if sidereal else containers.RFIMask
+        output = kind(axes_from=stream, attrs_from=stream, allocate=False)
+
+        planes = []
+        for p in range(chisq.shape[0] if separate_pol else 1):
+            y, ws, m_in = (chisq[p], wsum[p], mask_input[p]) if separate_pol else (chisq, wsum, mask_input)
+            mask = _mask_op(ctx, _lib.DMM_RFI_OR, m_in.contiguous(), mask_sources)
+            result = torch.zeros((nfreq, ntime), dtype=torch.uint8, device=ctx.device)
+            if self.nsigma_1d > 0.0:
+                rows = self.mask_1d(y, _mask_op(ctx, _lib.DMM_RFI_OR, mask, day_rows)).to(torch.uint8)
+                _lib.check(_lib.lib.dmm_rfi_rows(ctx.handle, None, ptr(mask), None, ptr(rows), nfreq, ntime))
+                _lib.check(_lib.lib.dmm_rfi_rows(ctx.handle, None, ptr(result), None, ptr(rows), nfreq, ntime))
+            if self.nsigma_2d > 0.0:
+                # the inverse variance of a chi-squared per degree of freedom is ndof / 2, and ndof is the weight
+                w = mask.eq(0).to(torch.float64) * ws / 2.0
+                found = self.mask_2d(y, w) if self.mask_type == "mad" else self.mask_2d_sumthreshold(y, w)
+                _or_into(ctx, result, found.to(torch.uint8) * day_rows.eq(0).to(torch.uint8))
+            planes.append(result)
+        total = torch.stack(planes) if separate_pol else planes[0]
+        output.attach("mask", total.view(torch.bool))
+        return output
+
+    def _collapse(self, ctx, stream, data, dax, separate_pol):
+        """The weighted average of the real part of the data over every axis but frequency, time / RA and, if kept,
+        polarisation: ``(chisq, wsum)``, float64 on the device.  The weight is broadcast along the axes it lacks, so
+        ``wsum`` counts every sample of them: the reference's factor on the summed weight is in the sum.  The reduced axes are brought together first (a copy, when the dataset does not hold them adjacent with
+        the time-like axis last)."""
+        weight = stream.weight
+        wax = list(weight.attrs["axis"])
+        x = data.device(ctx)
+        if x.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+            raise TypeError(f"the data must be real or complex floating point, got {x.dtype}")
+        w = weight.device(ctx)
+        w = w.reshape([w.shape[wax.index(ax)] if ax in wax else 1 for ax in dax])
+        if self.flag_ew is not None and "ew" in dax:
+            few = ctx.to_device(np.asarray(self.flag_ew), np.dtype(weight.dtype)).reshape([-1 if ax == "ew" else 1 for ax in dax])
+            w = w * few
+        keep = ["freq", "time", "ra"] + (["pol"] if separate_pol else [])
+        timelike = [i for i, ax in enumerate(dax) if ax in ("time", "ra")]
+        lead = [i for i, ax in enumerate(dax) if ax in keep and i not in timelike]
+        red = [i for i, ax in enumerate(dax) if ax not in keep]
+        order = lead + red + timelike
+        if order != list(range(len(dax))):
+            x = x.permute(order).contiguous()
+            w = w.expand(*data.shape).permute(order) if w.dim() else w
+        shape = [int(s) for s in x.shape]
+        if not red:  # nothing to average: one reduced sample per column
+            x, w = x.unsqueeze(len(lead)), w.unsqueeze(len(lead))
+            red = [0]
+        first = len(lead)
+        chisq, wsum = axis_reduce_device(ctx, _lib.DMM_REDUCE_WMEAN, x, w, first, first + len(red) - 1)
+        kept = [shape[i] for i in range(len(lead))] + [shape[-1]]
+        return chisq.reshape(kept), wsum.reshape(kept)
+
+    def mask_1d(self, y, m):
+        """Frequency channels whose median chi-squared over time deviates from the neighbouring channels.
+
+        ``y [nfreq, ntime]``: chi-squared per degree of freedom; ``m``: the samples to ignore in the median over time.
+        Returns the Boolean ``[nfreq]``.  Device tensors in, a device tensor out; arrays in, an array out.  The row
+        medians and the MAD are ``dmm_rfi_quantile``; the baseline fit runs on the host."""
+        on_device = isinstance(y, torch.Tensor)
+        ctx = Context.get()
+        yd = ctx.to_device(y if on_device else np.asarray(y), np.float64)
+        flag = m if (isinstance(m, torch.Tensor) and m.dtype == torch.uint8) else _u8(ctx, m)
+        nfreq = int(yd.shape[0])
+        med_d, kept = filters.quantile_device(ctx, yd, flag.contiguous(), 0.5, count=True)
+        med_m = kept.cpu().numpy() == 0
+        med_y = np.where(med_m, 0.0, med_d.cpu().numpy())  # (an empty row has no median: any finite value does)
+        baseline = tools.arPLS_1d(med_y, mask=med_m, lam=self.reg_arpls)
+        abs_dev = np.where(med_m, 0.0, np.abs(med_y - baseline))
+        spread = filters.quantile_device(ctx, ctx.to_device(abs_dev).reshape(1, nfreq), _u8(ctx, med_m).reshape(1, nfreq), 0.5).cpu().numpy()[0]
+        scale = self.MAD_TO_RMS * (0.0 if np.isnan(spread) else spread)
+        bad = abs_dev > (self.nsigma_1d * scale)
+        return ctx.to_device(bad.view(np.uint8)).ne(0) if on_device else bad
+
+    def _planes(self, y, w):
+        ctx = Context.get()
+        on_device = isinstance(y, torch.Tensor)
+        yd = ctx.to_device(y if on_device else np.asarray(y), np.float64)
+        wd = ctx.to_device(w if isinstance(w, torch.Tensor) else np.asarray(w), np.float64)
+        return ctx, on_device, yd, wd, filters.check_weighted_size((self.win_f, self.win_t), 2)
+
+    def _deviation(self, ctx, y, w, f, size):
+        """``(dy, |dy|)`` with ``dy = (y - median) sqrt(w)``, the median weighted by ``f``."""
+        med = filters.moving_weighted_median_device(ctx, y, f, size)
+        dy, ady = torch.empty_like(y), torch.empty_like(y)
+        _lib.check(_lib.lib.dmm_rfi_wdev(ctx.handle, ptr(y), ptr(med), ptr(w), y.numel(), ptr(dy), ptr(ady)))
+        return dy, ady
+
+    def mask_2d(self, y, w):
+        """Samples whose chi-squared deviates from the local weighted median.
+
+        ``y [nfreq, ntime]``: chi-squared per degree of freedom; ``w``: its inverse variance, zero for samples
+        already masked.  Returns the Boolean plane; device tensors in, a device tensor out."""
+        ctx, on_device, y, w, size = self._planes(y, w)
+        dy, ady = self._deviation(ctx, y, w, w, size)
+        if self.estimate_var:
+            spread = filters.moving_weighted_median_device(ctx, ady, w.gt(0.0).to(torch.float64), size)
+        else:
+            spread = torch.ones_like(y)
+        scale = self.MAD_TO_RMS if self.estimate_var else 1.0
+        _, _, mask = _nsigma(ctx, dy if self.only_positive else ady, spread, scale, self.nsigma_2d)
+        mask = mask.ne(0)
+        return mask if on_device else mask.cpu().numpy()
+
+    def mask_2d_sumthreshold(self, y, w):
+        """The same by SumThreshold, iterated: every pass re-estimates the median (and the variance) with the mask so
+        far and lowers the threshold by ``rho``.  Arguments and result as :meth:`mask_2d`."""
+        if not hasattr(self, "threshold"):
+            self.setup(self.telescope)
+        ctx, on_device, y, w, size = self._planes(y, w)
+        flag = w.eq(0.0).to(torch.uint8)
+        ones = torch.ones_like(y)
+        for nsigma in self.threshold:
+            f = flag.eq(0).to(torch.float64) * w
+            dy, ady = self._deviation(ctx, y, w, f, size)
+            if self.estimate_var:
+                spread = filters.moving_weighted_median_device(ctx, ady, f.gt(0.0).to(torch.float64), size)
+                _, variance, _ = _nsigma(ctx, ady, spread, self.MAD_TO_RMS, float(nsigma), want_var=True, want_mask=False)
+            else:
+                variance = ones
+            rfi.sumthreshold_device(ctx, dy, flag, self.max_m, float(nsigma), 1.0, (1, 0), variance=variance, correct_for_missing=True, only_positive=self.only_positive)
+        mask = flag.ne(0)
+        return mask if on_device else mask.cpu().numpy()
+
+    def _source_flag_hook(self, times, freq):
+        """Hook for subclasses: bright point sources to leave out, Boolean ``[nfreq, ntime]`` (True masks a sample)."""
+        return np.zeros((freq.size, times.size), dtype=bool)
+
+    def _day_flag_hook(self, times):
+        """Hook for subclasses: the daytime samples, Boolean ``[ntime]``: they take no part in the channel test and are
+        not flagged by the 2-D test."""
+        return np.zeros(times.size, dtype=bool)
 
 
 def _stack_plane(ds, ind):

@@ -454,3 +454,173 @@ class LanczosRegridder(ContainerTask):
 
 # Alias for compatibility
 Regridder = LanczosRegridder
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Weighted reductions over axes (``transform.py:1904-2117``), ``csrc/reduce.hip``
+
+_REDUCE_DTYPE = {torch.float32: _lib.DMM_REDUCE_F32, torch.float64: _lib.DMM_REDUCE_F64, torch.complex64: _lib.DMM_REDUCE_C64, torch.complex128: _lib.DMM_REDUCE_C128}
+
+
+def _merged_strides(shape, strides):
+    """The ``(length, stride)`` runs that address the same elements as the axes given, in the same order: axes of
+    length one are dropped and an axis is merged into the one before it where ``stride_before == length * stride``."""
+    runs = []
+    for n, s in zip(shape, strides):
+        n, s = int(n), int(s)
+        if n == 1:
+            continue
+        if runs and runs[-1][1] == n * s:
+            runs[-1] = (runs[-1][0] * n, s)
+        else:
+            runs.append((n, s))
+    return runs
+
+
+def axis_reduce_device(ctx, op, x, w, first, last, factor=1.0):
+    """Reduce the adjacent axes ``first ... last`` of the contiguous device tensor ``x`` (float32, float64, complex64 or
+    complex128) with ``dmm_axis_reduce``.
+
+    ``w``: ``None`` or a float32 / float64 device tensor that broadcasts against ``x`` (same number of axes, length one
+    where it lacks an axis); it is read in place through its strides when the axes ahead of the reduced ones, and those
+    behind them, merge into one stride each and the reduced ones into at most two, and is expanded otherwise.  Returns
+    ``(out, out_w)`` shaped like ``x`` with every reduced axis of length one; their types are the header's.
+    """
+    if x.dtype not in _REDUCE_DTYPE:
+        raise TypeError(f"axis_reduce: data of type {x.dtype} is not supported")
+    x = x.contiguous()
+    shape = [int(s) for s in x.shape]
+    nouter, nred, ninner = (int(np.prod(shape[a:b], dtype=np.int64)) for a, b in ((0, first), (first, last + 1), (last + 1, len(shape))))
+    wdtype, strides = _lib.DMM_REDUCE_F32, (0, 1, 0, 0, 0)  # (outer, nred2, red1, red2, inner)
+    if w is not None:
+        if w.dtype not in (torch.float32, torch.float64):
+            w = w.to(torch.float32)
+        wdtype = _lib.DMM_REDUCE_F64 if w.dtype == torch.float64 else _lib.DMM_REDUCE_F32
+        wv = w.expand(*shape)
+        for attempt in range(2):
+            groups = [_merged_strides(shape[a:b], wv.stride()[a:b]) for a, b in ((0, first), (first, last + 1), (last + 1, len(shape)))]
+            if len(groups[0]) <= 1 and len(groups[1]) <= 2 and len(groups[2]) <= 1:
+                break
+            wv = w = wv.contiguous()  # (the second attempt always merges)
+        red = groups[1] + [(1, 0)] * (2 - len(groups[1]))
+        strides = (groups[0][0][1] if groups[0] else 0, red[1][0], red[0][1], red[1][1], groups[2][0][1] if groups[2] else 0)
+        if len(groups[1]) == 1:  # one run: it is the inner of the two reduced axes
+            strides = (strides[0], nred if nred else 1, 0, red[0][1], strides[4])
+    keep = [1 if first <= d <= last else s for d, s in enumerate(shape)]
+    if op == _lib.DMM_REDUCE_WMEAN:
+        out, out_w = ctx.empty(keep, np.float64), ctx.empty(keep, np.float64)
+    else:
+        out = torch.empty(keep, dtype=x.dtype, device=x.device)
+        out_w = ctx.empty(keep, np.float64 if wdtype == _lib.DMM_REDUCE_F64 else np.float32)
+    _lib.check(
+        _lib.lib.dmm_axis_reduce(
+            ctx.handle, int(op), _REDUCE_DTYPE[x.dtype], ptr(x), nouter, nred, ninner, ptr(w), wdtype, int(strides[0]), int(max(strides[1], 1)), int(strides[2]),
+            int(strides[3]), int(strides[4]), float(factor), ptr(out), ptr(out_w),
+        )
+    )
+    return out, out_w
+
+
+class ReduceBase(ContainerTask):
+    """Apply a weighted reduction across adjacent axes of one dataset (``transform.py:1904-2062``).
+
+    Config: ``axes``, the names of the axes to reduce; ``dataset``, the dataset to reduce; ``weighting``, "none",
+    "masked" or "weighted" where the operation has a choice.  At least one axis must be left.  The output is a
+    container of the input's class in which every reduced axis has length one and carries the first entry of its index
+    map, with the attributes ``reduced``, ``reduction_axes``, ``reduced_dataset`` and ``reduction_op``; only the
+    reduced dataset and the weight are set, and both stay on the device.  The weight is the reduced weight at index 0
+    of the axes the input's weight lacks.  Reduced axes that are not adjacent in the dataset: ``NotImplementedError``.
+    """
+
+    axes = None
+    dataset = None
+    weighting = "none"
+    _config_names = ("axes", "dataset", "weighting")
+    _op = None
+
+    def read_config(self, params):
+        super().read_config(params)
+        if self.weighting not in ("none", "masked", "weighted"):
+            raise ValueError(f"weighting must be 'none', 'masked' or 'weighted', not {self.weighting!r}")
+
+    def process(self, data):
+        axes = list(self.axes or ())
+        ds = data.datasets[self.dataset]
+        ds_axes = list(ds.attrs["axis"])
+        if not [ax for ax in ds_axes if ax not in axes]:
+            raise ValueError("Could not find a valid axis to redistribute. At least one axis must be omitted from filtering.")
+        weight, w_axes = self._get_weights(data)
+        apply_over = sorted(ds_axes.index(ax) for ax in axes if ax in ds_axes)
+        if not apply_over or apply_over != list(range(apply_over[0], apply_over[-1] + 1)):
+            raise NotImplementedError(f"the reduced axes {axes} must be adjacent axes of the dataset, which has {ds_axes}")
+        out = self._make_output_container(data)
+
+        ctx = Context.get()
+        x = ds.device(ctx)
+        wt = None
+        if weight is not None:
+            wt = weight.device(ctx) if isinstance(weight, containers.Dataset) else ctx.to_device(np.asarray(weight[:]))
+            wt = wt.reshape([wt.shape[w_axes.index(ax)] if ax in w_axes else 1 for ax in ds_axes])
+        reduced, reduced_weight = self.reduction(x, wt, (apply_over[0], apply_over[-1]))
+
+        if self.dataset not in out._dataset_spec:
+            out.add_dataset(self.dataset, allocate=False)
+        out.attach(self.dataset, reduced)
+        wname = self._weight_name(data)
+        if wname is not None:
+            pick = tuple(slice(None) if ax in w_axes else 0 for ax in ds_axes)
+            out.attach(wname, reduced_weight[pick].contiguous())
+        return out
+
+    @staticmethod
+    def _weight_name(data):
+        return next((name for name in ("weight", "vis_weight") if name in data.datasets), None)
+
+    def _get_weights(self, data):
+        """The weight dataset and its axis names, ``(None, None)`` for a container without weights."""
+        name = self._weight_name(data)
+        if name is None:
+            if self.weighting != "none":
+                raise RuntimeError("No weights available. Cannot use weighted or masked weighting.")
+            return None, None
+        return data.datasets[name], list(data.datasets[name].attrs["axis"])
+
+    def _make_output_container(self, data):
+        # the first entry of a reduced axis' index map stands for the whole axis, whatever the operation
+        output_axes = {ax: np.array([data.index_map[ax][0]]) for ax in self.axes}
+        out = data.__class__(axes_from=data, attrs_from=data, allocate=False, **output_axes)
+        out.attrs["reduced"] = True
+        out.attrs["reduction_axes"] = np.array(self.axes)
+        out.attrs["reduced_dataset"] = self.dataset
+        out.attrs["reduction_op"] = self._op
+        return out
+
+    def reduction(self, arr, weight, axis):
+        """``(reduced, reduced_weight)`` of the device tensor ``arr`` over its adjacent axes ``axis = (first, last)``,
+        both with those axes of length one; ``weight`` broadcasts against ``arr`` or is ``None``."""
+        raise NotImplementedError
+
+
+class ReduceVar(ReduceBase):
+    """The weighted variance over the axes (``transform.py:2065-2089``): with "none" ``mean |x - mean x|^2`` and unit
+    weights; with "masked" (weights set to ``w > 0``) and "weighted", ``sum w (x - mu)^2 / sum w`` about the weighted
+    mean ``mu`` and the weight ``sum w``."""
+
+    _op = "variance"
+
+    def reduction(self, arr, weight, axis):
+        op = {"none": _lib.DMM_REDUCE_VAR_NONE, "masked": _lib.DMM_REDUCE_VAR_MASKED, "weighted": _lib.DMM_REDUCE_VAR_WEIGHTED}[self.weighting]
+        if op != _lib.DMM_REDUCE_VAR_NONE and weight is None:
+            raise RuntimeError("No weights available. Cannot use weighted or masked weighting.")
+        return axis_reduce_device(Context.get(), op, arr, weight, axis[0], axis[1])
+
+
+class ReduceChisq(ReduceBase):
+    """The chi-squared per degree of freedom over the axes (``transform.py:2092-2117``), for data that is uncorrelated
+    noise of inverse variance ``weight``: ``sum w |x - mu|^2 / num`` about the weighted mean, with ``num`` one less than
+    the number of samples of positive weight, which is also the weight that comes out."""
+
+    _op = "chisq_per_dof"
+
+    def reduction(self, arr, weight, axis):
+        return axis_reduce_device(Context.get(), _lib.DMM_REDUCE_CHISQ, arr, weight, axis[0], axis[1])

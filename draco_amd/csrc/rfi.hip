@@ -13,6 +13,11 @@
 // inside it and a settled column is not read again.  The bisection starts below the common leading bits of the
 // window's smallest and largest key.  The result is a sample (or the mean of two), never an accumulated value: it does
 // not depend on the block shape or the launch order.
+// k_wmedfilt: the weighted moving median of RFIMaskChisqHighDelay (draco/analysis/flagging.py:1670-1773; the convention is
+// DESIGN.md section 7s).  k_medfilt's strip, sort and bisection, with each key's weight as payload: every sorted column
+// carries the inclusive prefix sums of its weights, a probe reads the prefix weight at the place it finds, and the wave
+// reduces the weight instead of the count and compares it with half the window's total.  The strip holds 16 bytes per
+// sample, up to 8192 samples, and the windows reach 1023 columns: the kernel is compiled for 4, 10 and 16 columns per lane.
 // k_quantile: one wave per row, the same bisection over the unsorted row in LDS.
 // k_st_hit / k_st_spread: one SumThreshold step (one window length along one axis) as two launches, so that the flag
 // update of an axis completes before the next one reads it.  Window sums run in ascending sample order in float64.
@@ -264,6 +269,264 @@ __global__ __launch_bounds__(kMedThreads) void k_medfilt(MedArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- weighted moving median
+
+constexpr int kWmedPer = DMM_RFI_WMED_MAX_STRIP / kMedThreads;  // strip samples per thread in the sort
+
+__device__ inline double wave_sum_d(double v) {
+  for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+  return v;
+}
+
+struct WMedArgs {
+  const double* x;
+  const double* w;
+  double* out;
+  int nf, nt, hf, ht, T;
+};
+
+// The sorted columns one lane owns, as in ColumnSet, with the inclusive prefix sums of the weights beside the keys:
+// pw[c R + i] is the weight of the i + 1 smallest kept samples of column c.  wl[j] is the prefix weight below lo[j]; a
+// column whose bracket is empty answers a probe from it without an LDS read.
+template <int CPL>
+struct WColumnSet {
+  const uint64_t* keys;
+  const double* pw;
+  const int* cnt;
+  int R, c0, cb;  // this lane's columns are c0 + 64 j, those beyond cb do not exist
+  int lo[CPL], hi[CPL], mid[CPL];
+  double wl[CPL];
+  __device__ inline double below(int j, int l) const { return l > 0 ? pw[(c0 + j * kWave) * R + l - 1] : 0.0; }
+  // this lane's count and weight of keys < t
+  __device__ inline int probe(uint64_t t, double& wsum) {
+    int tot = 0;
+    double ws = 0.0;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      int l = lo[j], len = hi[j] - l;
+      double wj = wl[j];
+      if (len > 0) {
+        const uint64_t* col = keys + (c0 + j * kWave) * R;
+        while (len > 0) {
+          const int half = len >> 1;
+          if (col[l + half] < t) {
+            l += half + 1;
+            len -= half + 1;
+          } else {
+            len = half;
+          }
+        }
+        if (l != lo[j]) wj = below(j, l);
+      }
+      mid[j] = l;
+      tot += l;
+      ws = ws + wj;
+    }
+    wsum = ws;
+    return tot;
+  }
+  __device__ inline void accept(bool up) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      if (up) {
+        if (mid[j] != lo[j]) {
+          lo[j] = mid[j];
+          wl[j] = below(j, lo[j]);
+        }
+      } else {
+        hi[j] = mid[j];
+      }
+    }
+  }
+  __device__ inline uint64_t bracket_min() const {
+    uint64_t best = kDropped;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      if (lo[j] < hi[j]) {
+        const uint64_t k = keys[(c0 + j * kWave) * R + lo[j]];
+        best = k < best ? k : best;
+      }
+    }
+    return best;
+  }
+  __device__ inline double weight_le() const {  // no key lies in (x, U) when this is asked
+    double ws = 0.0;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) ws = ws + below(j, hi[j]);
+    return ws;
+  }
+  __device__ inline uint64_t min_gt() const {
+    uint64_t best = kDropped;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int c = c0 + j * kWave;
+      if (c <= cb && hi[j] < cnt[c]) {
+        const uint64_t k = keys[c * R + hi[j]];
+        best = k < best ? k : best;
+      }
+    }
+    return best;
+  }
+};
+
+// 0.5 (lo + hi) of the n >= 1 weighted keys a wave holds, W > 0 their total weight and c(v) the weight of the keys <= v:
+// lo the smallest key with c(lo) >= W / 2, hi the smallest with c(hi) > W / 2.  With g(t) the weight of the keys < t, lo
+// is the largest t with g(t) < W / 2: the bisection of wave_select with the weight in the place of the count.  The
+// count is carried along for the early exit only: one key left in [x, U) is lo.  hi is lo unless c(lo) == W / 2
+// exactly, then the next key.  Every weight is a sum of per-column prefix sums in one fixed order (a lane's columns in
+// ascending order, then the butterfly): it depends on the output's window alone, not on the tile or the block.
+template <int CPL>
+__device__ inline double wave_wselect(WColumnSet<CPL>& s, int n, double W, uint64_t kmin, uint64_t kmax) {
+  const double half = 0.5 * W;
+  uint64_t x = kmin;
+  if (kmin != kmax) {
+    const int b = 63 - __clzll((long long)(kmin ^ kmax));
+    x = b == 63 ? 0ull : ((kmin >> (b + 1)) << (b + 1));
+    int clo = 0, chi = n;
+    for (int bit = b; bit >= 0; --bit) {
+      const uint64_t t = x | (1ull << bit);
+      double g;
+      const int c = wave_sum(s.probe(t, g));
+      g = wave_sum_d(g);
+      const bool up = g < half;
+      if (up) {
+        x = t;
+        clo = c;
+      } else {
+        chi = c;
+      }
+      s.accept(up);
+      if (chi - clo == 1) {
+        x = wave_min(s.bracket_min());
+        break;
+      }
+    }
+  }
+  uint64_t x2 = x;
+  if (wave_sum_d(s.weight_le()) == half) x2 = wave_min(s.min_gt());
+  return 0.5 * (val_of(x) + val_of(x2));
+}
+
+// One block per frequency row and tile of T output times, as k_medfilt.  LDS: the keys [C][R], the weights and then
+// their prefix sums [C][R], the kept count of every column.  Samples whose weight is not > 0 carry the largest key and
+// are dropped by the sort.
+template <int CPL>
+__global__ __launch_bounds__(kMedThreads) void k_wmedfilt(WMedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char wmed_lds[];
+  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+  const int f = blockIdx.y;
+  const int t0 = blockIdx.x * a.T;
+  const int t1 = min(t0 + a.T, a.nt);
+  const int r0 = max(f - a.hf, 0), r1 = min(f + a.hf, a.nf - 1);
+  const int c0 = max(t0 - a.ht, 0), c1 = min(t1 - 1 + a.ht, a.nt - 1);
+  const int R = r1 - r0 + 1, C = c1 - c0 + 1, total = R * C;  // total <= DMM_RFI_WMED_MAX_STRIP (checked by the host)
+  uint64_t* keys = (uint64_t*)wmed_lds;   // [C][R]
+  double* pw = (double*)(keys + total);   // [C][R]
+  int* cnt = (int*)(pw + total);          // [C]
+  const size_t plane = (size_t)blockIdx.z * a.nf * a.nt;
+  const double* x = a.x + plane;
+  const double* w = a.w + plane;
+
+  for (int e = tid; e < total; e += kMedThreads) {  // time fastest: coalesced reads
+    const int r = e / C, c = e - r * C;
+    const size_t o = (size_t)(r0 + r) * a.nt + (c0 + c);
+    const double wv = w[o];
+    const bool kept = wv > 0.0;
+    keys[c * R + r] = kept ? key_of(x[o]) : kDropped;
+    pw[c * R + r] = kept ? wv : 0.0;
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += kMedThreads) {
+    int n = 0;
+    for (int r = 0; r < R; ++r) n += keys[c * R + r] != kDropped;
+    cnt[c] = n;
+  }
+  // rank sort of every column, the weight travelling with its key; equal keys keep their row order
+  uint64_t kk[kWmedPer];
+  double ww[kWmedPer];
+  int rk[kWmedPer];
+#pragma unroll
+  for (int i = 0; i < kWmedPer; ++i) {
+    const int e = tid + i * kMedThreads;
+    rk[i] = -1;
+    kk[i] = kDropped;
+    ww[i] = 0.0;
+    if (e < total) {
+      const int c = e / R, r = e - c * R;
+      const uint64_t k = keys[e];
+      if (k != kDropped) {
+        const uint64_t* col = keys + c * R;
+        int rank = 0;
+        for (int q = 0; q < R; ++q) {
+          const uint64_t u = col[q];
+          rank += (u < k) || (u == k && q < r);
+        }
+        kk[i] = k;
+        ww[i] = pw[e];
+        rk[i] = c * R + rank;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kWmedPer; ++i) {
+    if (rk[i] >= 0) {
+      keys[rk[i]] = kk[i];
+      pw[rk[i]] = ww[i];
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += kMedThreads) {  // inclusive prefix sums in sorted order, strictly sequential
+    double s = 0.0;
+    const int n = cnt[c];
+    for (int r = 0; r < n; ++r) {
+      s = s + pw[c * R + r];
+      pw[c * R + r] = s;
+    }
+  }
+  __syncthreads();
+
+  for (int t = t0 + wave; t < t1; t += kMedWaves) {  // uniform per wave
+    const int ca = max(t - a.ht, 0) - c0, cb = min(t + a.ht, a.nt - 1) - c0;  // cb - ca < 64 CPL (chosen by the host)
+    WColumnSet<CPL> s;
+    s.keys = keys;
+    s.pw = pw;
+    s.cnt = cnt;
+    s.R = R;
+    s.c0 = ca + lane;
+    s.cb = cb;
+    int n = 0;
+    double W = 0.0;
+    uint64_t kmin = kDropped, kmax = 0;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const int c = ca + lane + j * kWave;
+      s.lo[j] = s.mid[j] = s.hi[j] = 0;
+      s.wl[j] = 0.0;
+      if (c <= cb) {
+        const int m = cnt[c];
+        s.hi[j] = m;
+        if (m > 0) {
+          const uint64_t lo = keys[c * R], hi = keys[c * R + m - 1];
+          kmin = lo < kmin ? lo : kmin;
+          kmax = hi > kmax ? hi : kmax;
+          W = W + pw[c * R + m - 1];
+        }
+        n += m;
+      }
+    }
+    n = wave_sum(n);
+    double res = __longlong_as_double(0x7FF8000000000000ll);  // empty window
+    if (n > 0) {
+      W = wave_sum_d(W);
+      kmin = wave_min(kmin);
+      kmax = wave_max(kmax);
+      res = wave_wselect(s, n, W, kmin, kmax);
+    }
+    if (lane == 0) a.out[plane + (size_t)f * a.nt + t] = res;
+  }
+}
+
 // ---------------------------------------------------------------- row quantile ("split" method)
 
 struct RowSet {
@@ -490,6 +753,15 @@ __global__ __launch_bounds__(256) void k_absdev(const double* yr, const double* 
   ady[i] = yi ? hypot(dr, yi[i] - mi[i]) : fabs(dr);
 }
 
+// the deviation from the weighted median in expected standard deviations: w is the inverse variance
+__global__ __launch_bounds__(256) void k_wdev(const double* y, const double* med, const double* w, int64_t n, double* dy, double* ady) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double d = (y[i] - med[i]) * __dsqrt_rn(w[i]);
+  dy[i] = d;
+  if (ady) ady[i] = fabs(d);
+}
+
 __global__ __launch_bounds__(256) void k_nsigma(const double* ady, const double* mad, double scale, double nsigma, double nan_fill, int divide, int64_t n, double* ratio,
                                                 double* var, uint8_t* mask) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -626,6 +898,40 @@ int dmm_rfi_medfilt(dmm_ctx* ctx, const double* x, const uint8_t* flag, int npla
   return DMM_OK;
 }
 
+int dmm_rfi_wmedfilt(dmm_ctx* ctx, const double* x, const double* w, int nplane, int nf, int nt, int size_f, int size_t_, double* out) {
+  DMM_REQUIRE(ctx != nullptr, "dmm_rfi_wmedfilt: ctx is NULL");
+  DMM_REQUIRE(nplane >= 0 && nf >= 0 && nt >= 0, "dmm_rfi_wmedfilt: bad sizes nplane=%d nf=%d nt=%d", nplane, nf, nt);
+  DMM_REQUIRE(size_f >= 1 && size_t_ >= 1 && (size_f & 1) && (size_t_ & 1), "dmm_rfi_wmedfilt: window sizes must be odd and positive, got (%d, %d)", size_f, size_t_);
+  DMM_REQUIRE(size_f <= DMM_RFI_WMED_MAX_WINDOW && size_t_ <= DMM_RFI_WMED_MAX_WINDOW && (int64_t)size_f * size_t_ <= DMM_RFI_WMED_MAX_STRIP,
+              "dmm_rfi_wmedfilt: window (%d, %d) beyond the supported bound: each size at most %d, their product at most %d", size_f, size_t_,
+              DMM_RFI_WMED_MAX_WINDOW, DMM_RFI_WMED_MAX_STRIP);
+  if (nplane == 0 || nf == 0 || nt == 0) return DMM_OK;
+  DMM_REQUIRE(x && w && out, "dmm_rfi_wmedfilt: NULL argument");
+  DMM_REQUIRE(nplane <= 65535 && nf <= 65535, "dmm_rfi_wmedfilt: nplane %d or nf %d does not fit the grid (65535)", nplane, nf);
+  const int rows = std::min(size_f, nf);
+  const int T = std::max(1, std::min(DMM_RFI_WMED_TILE, DMM_RFI_WMED_MAX_STRIP / rows - (size_t_ - 1)));
+  const int cols = std::min(T + size_t_ - 1, nt);
+  DMM_REQUIRE((int64_t)rows * cols <= DMM_RFI_WMED_MAX_STRIP, "dmm_rfi_wmedfilt: strip of %d x %d does not fit", rows, cols);
+  DMM_HIP(hipSetDevice(ctx->device));
+  WMedArgs a{x, w, out, nf, nt, size_f / 2, size_t_ / 2, T};
+  const size_t lds = (size_t)rows * cols * (sizeof(uint64_t) + sizeof(double)) + (size_t)cols * sizeof(int);
+  const dim3 grid((unsigned)((nt + T - 1) / T), (unsigned)nf, (unsigned)nplane);
+  const int wcols = std::min(size_t_, nt);  // columns of one output's window, 64 per lane and pass
+  if (wcols <= 4 * kWave) {
+    DMM_HIP(hipFuncSetAttribute((const void*)k_wmedfilt<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_wmedfilt<4>, grid, dim3(kMedThreads), lds, ctx->stream, a);
+  } else if (wcols <= 10 * kWave) {
+    DMM_HIP(hipFuncSetAttribute((const void*)k_wmedfilt<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_wmedfilt<10>, grid, dim3(kMedThreads), lds, ctx->stream, a);
+  } else {
+    static_assert(DMM_RFI_WMED_MAX_WINDOW <= 16 * kWave, "columns per lane");
+    DMM_HIP(hipFuncSetAttribute((const void*)k_wmedfilt<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_wmedfilt<16>, grid, dim3(kMedThreads), lds, ctx->stream, a);
+  }
+  DMM_HIP(hipGetLastError());
+  return DMM_OK;
+}
+
 int dmm_rfi_quantile(dmm_ctx* ctx, const double* y, const uint8_t* flag, int64_t nrow, int n, double q, double* out, int32_t* count) {
   DMM_REQUIRE(ctx != nullptr, "dmm_rfi_quantile: ctx is NULL");
   DMM_REQUIRE(nrow >= 0 && nrow <= 0x7fffffff, "dmm_rfi_quantile: bad nrow %lld", (long long)nrow);
@@ -702,6 +1008,17 @@ int dmm_rfi_absdev(dmm_ctx* ctx, const double* y, const double* med, const doubl
   DMM_REQUIRE((y_imag != nullptr) == (med_imag != nullptr), "dmm_rfi_absdev: the imaginary parts come both or not at all");
   DMM_HIP(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_absdev, dim3(blocks256(n)), dim3(256), 0, ctx->stream, y, med, y_imag, med_imag, n, dy, ady);
+  DMM_HIP(hipGetLastError());
+  return DMM_OK;
+}
+
+int dmm_rfi_wdev(dmm_ctx* ctx, const double* y, const double* med, const double* w, int64_t n, double* dy, double* ady) {
+  DMM_REQUIRE(ctx != nullptr, "dmm_rfi_wdev: ctx is NULL");
+  DMM_REQUIRE(n >= 0 && n <= ((int64_t)1 << 39), "dmm_rfi_wdev: bad count %lld", (long long)n);
+  if (n == 0) return DMM_OK;
+  DMM_REQUIRE(y && med && w && dy, "dmm_rfi_wdev: NULL argument");
+  DMM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_wdev, dim3(blocks256(n)), dim3(256), 0, ctx->stream, y, med, w, n, dy, ady);
   DMM_HIP(hipGetLastError());
   return DMM_OK;
 }

@@ -1,10 +1,11 @@
-"""Masked moving median (``draco/util/filters.py:99-130``) and the delay null-space filter
-(``draco/util/filters.py:133-212``) on the GPU.
+"""Masked moving median (``draco/util/filters.py:99-130``), the weighted moving median of the chi-squared mask, and the
+delay null-space filter (``draco/util/filters.py:133-212``) on the GPU.
 
 ``medfilt`` wraps caput's ``moving_weighted_median`` [3P] in the reference; here it is ``dmm_rfi_medfilt``
 (``csrc/rfi.hip``) under the conventions of DESIGN.md section 7i: the window is centred on the sample and clipped at
 the array's edge, the result is ``0.5 * (v[(n-1)//2] + v[n//2])`` of the ``n`` unmasked samples ``v`` of the window in
-ascending order and NaN for an empty window.  Window sizes are odd.  Only 0/1 weights exist: a sample is masked or not.
+ascending order and NaN for an empty window.  Window sizes are odd.  ``medfilt`` has 0/1 weights only: a sample is masked
+or not.  :func:`moving_weighted_median` takes real weights and longer windows (``dmm_rfi_wmedfilt``).
 
 ``null_filter`` projects out (or keeps) the span of the Fourier modes ``exp(2 pi i f s)``, ``f = linspace(-cutoff,
 cutoff, num_modes)``, on the unmasked samples: ``dmm_nullfilter_build`` (``csrc/nullfilter.hip``)
@@ -21,8 +22,7 @@ from .. import _lib
 from ..device import Context, ptr
 
 
-def check_size(size, ndim):
-    """The window as ``(size_f, size_t)``; ``ValueError`` for an even size or one beyond the kernel's bound."""
+def _check_window(size, ndim, max_window, max_strip):
     if np.ndim(size) == 0:
         size = (int(size),) * ndim
     size = tuple(int(s) for s in size)
@@ -32,12 +32,14 @@ def check_size(size, ndim):
         size = (size[0], 1)
     if any(s < 1 or s % 2 == 0 for s in size):
         raise ValueError(f"window sizes must be odd and positive, got {size}")
-    if max(size) > _lib.DMM_RFI_MAX_WINDOW or size[0] * size[1] > _lib.DMM_RFI_MAX_STRIP:
-        raise ValueError(
-            f"window {size} is beyond the supported bound: each size at most {_lib.DMM_RFI_MAX_WINDOW}, "
-            f"their product at most {_lib.DMM_RFI_MAX_STRIP}"
-        )
+    if max(size) > max_window or size[0] * size[1] > max_strip:
+        raise ValueError(f"window {size} is beyond the supported bound: each size at most {max_window}, their product at most {max_strip}")
     return size
+
+
+def check_size(size, ndim):
+    """The window as ``(size_f, size_t)``; ``ValueError`` for an even size or one beyond the kernel's bound."""
+    return _check_window(size, ndim, _lib.DMM_RFI_MAX_WINDOW, _lib.DMM_RFI_MAX_STRIP)
 
 
 def medfilt_device(ctx, x, flag, size):
@@ -91,6 +93,72 @@ def medfilt(x, mask, size, *args):
     if ndim == 1:
         xt, ft = xt.reshape(-1, 1), ft.reshape(-1, 1)
     out = medfilt_device(ctx, xt, ft, size)
+    if ndim == 1:
+        out = out.reshape(-1)
+    return out if is_tensor else out.cpu().numpy()
+
+
+# ---- the weighted moving median
+
+
+def check_weighted_size(size, ndim):
+    """The window of the weighted median as ``(size_f, size_t)``; ``ValueError`` for an even size or one beyond the
+    kernel's bound (each size at most ``DMM_RFI_WMED_MAX_WINDOW``, their product at most ``DMM_RFI_WMED_MAX_STRIP``)."""
+    return _check_window(size, ndim, _lib.DMM_RFI_WMED_MAX_WINDOW, _lib.DMM_RFI_WMED_MAX_STRIP)
+
+
+def moving_weighted_median_device(ctx, x, w, size):
+    """``x [..., nf, nt]`` and ``w`` float64 device tensors of one shape -> the weighted moving median of every plane,
+    a new tensor.  ``size``: ``(size_f, size_t)`` as :func:`check_weighted_size` returns it.  Weights that are
+    negative or NaN are not looked for here: such a sample is dropped."""
+    nf, nt = int(x.shape[-2]), int(x.shape[-1])
+    nplane = int(np.prod(x.shape[:-2])) if x.dim() > 2 else 1
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib.dmm_rfi_wmedfilt(ctx.handle, ptr(x), ptr(w), nplane, nf, nt, int(size[0]), int(size[1]), ptr(out)))
+    return out
+
+
+def moving_weighted_median(x, w, size):
+    """Weighted moving median of ``x`` (caput's ``moving_weighted_median`` [3P] as ``flagging.py:1670-1773`` calls it).
+
+    ``x``: a 1-D array or ``[..., freq, time]`` real planes; ``w``: the weights, of the same shape; ``size``: the odd
+    window size in each dimension.  NumPy in, NumPy out; device tensors in, a device tensor out.
+
+    The convention: the window is centred on the sample and clipped at the array's edge, without
+    padding.  Only samples with a weight > 0 take part.  With the window's samples in ascending order, ``W`` their
+    total weight and ``c(v)`` the weight of all samples ``<= v``: ``lo`` is the smallest sample with ``c(lo) >= W/2``,
+    ``hi`` the smallest with ``c(hi) > W/2``, and the result is ``0.5 * (lo + hi)``; a window without a sample gives
+    NaN.  With 0/1 weights this is :func:`medfilt`'s ``0.5 * (v[(n-1)//2] + v[n//2])``.  Signed zeros and NaN samples
+    as there.
+
+    Weight sums are float64.  Where every partial sum is exact (integer or dyadic weights of modest size) the result is
+    exactly the stated one, whatever the shape of the plane.  Elsewhere it is the stated one wherever ``c(v)`` misses
+    ``W/2`` by more than the rounding of the sums; a window whose split is decided by a rounding error may give
+    ``lo`` or ``0.5 * (lo + hi)``.
+
+    ``ValueError``: an even or non-positive size, a window beyond the bound (:func:`check_weighted_size`), shapes that
+    differ, complex data, and -- for NumPy input -- a negative or NaN weight.  Device input is not inspected: there a
+    negative or NaN weight is undefined.
+    """
+    is_tensor = isinstance(x, torch.Tensor)
+    ndim = x.dim() if is_tensor else np.ndim(x)
+    if ndim < 1:
+        raise ValueError("moving_weighted_median needs at least one dimension")
+    size = check_weighted_size(size, min(ndim, 2))
+    if tuple(x.shape) != tuple(w.shape):
+        raise ValueError(f"data {tuple(x.shape)} and weight {tuple(w.shape)} differ in shape")
+    if (x.is_complex() if is_tensor else np.iscomplexobj(x)):
+        raise ValueError("moving_weighted_median takes real data")
+    if not is_tensor:
+        wh = np.asarray(w, dtype=np.float64)
+        if np.isnan(wh).any() or (wh < 0).any():
+            raise ValueError("moving_weighted_median: weights must be non-negative numbers")
+    ctx = Context.get()
+    xt = ctx.to_device(x if is_tensor else np.asarray(x), np.float64)
+    wt = ctx.to_device(w if is_tensor else wh, np.float64)
+    if ndim == 1:
+        xt, wt = xt.reshape(-1, 1), wt.reshape(-1, 1)
+    out = moving_weighted_median_device(ctx, xt.contiguous(), wt.contiguous(), size)
     if ndim == 1:
         out = out.reshape(-1)
     return out if is_tensor else out.cpu().numpy()

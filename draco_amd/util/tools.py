@@ -207,3 +207,79 @@ def baseline_vector(index_map, telescope):
     a, b = _stack_feeds(index_map)
     unique = np.asarray(telescope.feedmap[a, b], dtype=np.int64)
     return np.ascontiguousarray(np.asarray(telescope.baselines, dtype=np.float64)[unique].T)
+
+
+def penalized_least_squares_1d(y, reweight_func, mask=None, lam=1e2, epsilon=1e-2, max_iter=100):
+    """A smooth baseline of the 1-D signal ``y`` by iteratively reweighted penalised least squares (``tools.py:604-714``).
+
+    Every iteration solves ``(W + lam D^T D) z = W y`` with ``D`` the second-difference operator and ``W`` the diagonal
+    weights, through ``scipy.linalg.solveh_banded`` (the matrix has two sub-diagonals), then asks ``reweight_func(y - z,
+    mask, iteration)`` for the next weights; masked samples always weigh nothing.  It stops when ``norm(w - w_next) /
+    norm(w) < epsilon``, and warns after ``max_iter`` iterations without that.  An input that is masked everywhere gives
+    zeros and a warning.  Host only: the arrays are one frequency axis long.
+    """
+    import warnings
+
+    import scipy.linalg as la
+
+    y = np.squeeze(y)
+    if y.ndim != 1:
+        raise ValueError(f"Expected 1D data array - got array with shape {y.shape}")
+    n = y.shape[0]
+    if mask is None:
+        mask = np.zeros(n, dtype=bool)
+    elif np.all(mask):
+        warnings.warn("Entire dataset is masked.")
+        return np.zeros_like(y)
+    mask = np.squeeze(mask)
+    if mask.ndim != 1:
+        raise ValueError(f"Expected 1D mask array - got array with shape {mask.shape}")
+
+    # lam D D^T in lower band form: the rows hold the main diagonal and the two below it
+    band = np.ones((3, n), dtype=np.float64)
+    pattern = np.array([1.0, -2.0, 1.0])
+    for k in range(3):
+        diag = np.zeros(n - k if n > k else 0)
+        for j in range(max(n - 2, 0)):  # column j of D holds the pattern in rows j ... j + 2
+            for a in range(3 - k):
+                diag[j + a] += (lam * pattern[a + k]) * pattern[a]
+        band[k, : n - k] = diag
+    weights = np.zeros_like(band)
+    weights[0] = 1.0
+
+    z = None
+    for it in range(max_iter):
+        weights[:, mask] = 0.0
+        w = weights[0]
+        z = la.solveh_banded(band + weights, w * y, lower=True, check_finite=False)
+        try:
+            w_next = reweight_func(y - z, mask, it)
+        except Exception as exc:
+            raise RuntimeError("Invalid reweighting function") from exc
+        if la.norm(w - w_next) / la.norm(w) < epsilon:
+            break
+        weights[0] = w_next
+    else:
+        warnings.warn(f"PLS did not converge after {max_iter} iterations.")
+    return z
+
+
+def arPLS_1d(y, mask=None, lam=1e2, epsilon=1e-2, max_iter=100):
+    """Baseline of ``y`` by asymmetrically reweighted penalised least squares (``tools.py:717-780``; Baek et al. 2015).
+
+    The weights are ``1 / (1 + exp(2 (r - (2 sigma - mu)) / sigma))`` with ``r = y - z`` and ``mu``, ``sigma`` the mean
+    and the standard deviation of the negative, unmasked residuals: samples far above the baseline stop pulling on it.
+    The rest is :func:`penalized_least_squares_1d`.
+    """
+    y = np.asarray(y)
+    largest = np.log(np.finfo(y.dtype).max)  # exp() of anything beyond would overflow
+
+    def reweight(resid, masked, it):
+        below = (resid < 0) & ~masked
+        mu = np.mean(resid, where=below)
+        sigma = np.std(resid, where=below)
+        arg = 2 * (resid - (2 * sigma - mu)) * invert_no_zero(sigma)
+        arg = np.clip(arg, -largest, largest)
+        return invert_no_zero(np.exp(arg) + 1.0)
+
+    return penalized_least_squares_1d(y, reweight, mask, lam, epsilon, max_iter)

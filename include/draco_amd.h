@@ -997,6 +997,44 @@ int dmm_rfi_radiometer(dmm_ctx* ctx, const float* measured, const float* radiome
 int dmm_rfi_apply_mask(dmm_ctx* ctx, float* weight, int ndim, const int64_t* dims, int nt, const uint8_t* mask, const int64_t* mask_stride, int64_t mask_stride_t,
                        int nmask, int nsel, const int32_t* data_index, const int32_t* mask_index);
 
+/* Weighted moving median (caput's moving_weighted_median as draco/analysis/flagging.py:1670-1773 uses it; the
+ * convention is pinned in DESIGN.md section 7s), csrc/rfi.hip.  x, w, out float64 [nplane][nf][nt] [dev].
+ * dmm_rfi_wmedfilt: the window of (size_f, size_t) samples is centred on the sample and clipped at the plane's edge;
+ * the samples with w > 0 take part.  In ascending order, W their total weight and c(v) the weight of the samples <= v:
+ * lo the smallest sample with c(lo) >= W / 2, hi the smallest with c(hi) > W / 2, the result 0.5 (lo + hi); NaN for a
+ * window without a sample.  With 0/1 weights that is dmm_rfi_medfilt's result.  Weight sums are float64, per column of
+ * the window in sorted order and then over the columns in a fixed order that depends on the window alone: where every
+ * partial sum is exact the result is exact for any launch shape, elsewhere it is the stated one wherever c(v) misses
+ * W / 2 by more than the rounding of those sums.  A negative or NaN weight drops the sample (callers reject them).
+ * Signed zeros and NaN samples as for dmm_rfi_medfilt.
+ * Supported: both sizes odd, each <= DMM_RFI_WMED_MAX_WINDOW, their product <= DMM_RFI_WMED_MAX_STRIP; anything else is
+ * DMM_E_ARG.  A block keeps min(size_f, nf) x (T + size_t - 1) <= DMM_RFI_WMED_MAX_STRIP samples of 16 bytes (key and
+ * prefix weight) and 4 bytes per column in LDS, T <= DMM_RFI_WMED_TILE output times: at most 128 KiB + 4.3 KiB of the
+ * 160 KiB of a CU, one block per CU at the bound.
+ * dmm_rfi_wdev: dy = (y - med) sqrt(w), ady = |dy| (may be NULL), n samples: the deviation from the median in expected
+ * standard deviations, w the inverse variance. */
+#define DMM_RFI_WMED_MAX_WINDOW 1023
+#define DMM_RFI_WMED_MAX_STRIP 8192
+#define DMM_RFI_WMED_TILE 64
+int dmm_rfi_wmedfilt(dmm_ctx* ctx, const double* x, const double* w, int nplane, int nf, int nt, int size_f, int size_t_, double* out);
+int dmm_rfi_wdev(dmm_ctx* ctx, const double* y, const double* med, const double* w, int64_t n, double* dy, double* ady);
+
+/* Weighted reductions over adjacent axes (draco/analysis/transform.py:1904-2117 and the collapse of
+ * draco/analysis/flagging.py:1548-1579), csrc/reduce.hip.  x [nouter][nred][ninner] [dev] of type dtype; the weight w
+ * [dev] (float32 or float64 by wdtype; NULL: all ones) of sample (o, r, i) lies at o ws_outer + (r / nred2) ws_red1 +
+ * (r % nred2) ws_red2 + i ws_inner elements, a stride of 0 for an axis the weight lacks; nred2 divides nred.  Sums are
+ * float64 in ascending r, one rounding at the store; inz(v) = 1 / v, 0 for v = 0.  out, out_w [nouter][ninner] [dev].
+ * DMM_REDUCE_CHISQ: num = max(#(w > 0) - 1, 0), mu = sum(w x) inz(sum w), out = sum(w |x - mu|^2) inz(num) in x's
+ * type, out_w = num in the weight's type.
+ * DMM_REDUCE_VAR_NONE: out = mean |x - mean x|^2, out_w = 1.  _MASKED (w <- w > 0) and _WEIGHTED: ws = sum w, mu =
+ * sum(w x) inz(ws), out = sum(w (x - mu)^2) inz(ws) (the square of a complex number, as the reference has it), out_w =
+ * ws.  Both need w.
+ * DMM_REDUCE_WMEAN: s = factor sum w, out = sum(w Re x) inz(s), out_w = s, both float64. */
+enum { DMM_REDUCE_CHISQ = 0, DMM_REDUCE_VAR_NONE = 1, DMM_REDUCE_VAR_MASKED = 2, DMM_REDUCE_VAR_WEIGHTED = 3, DMM_REDUCE_WMEAN = 4 };
+enum { DMM_REDUCE_F32 = 0, DMM_REDUCE_F64 = 1, DMM_REDUCE_C64 = 2, DMM_REDUCE_C128 = 3 };
+int dmm_axis_reduce(dmm_ctx* ctx, int op, int dtype, const void* x, int64_t nouter, int64_t nred, int64_t ninner, const void* w, int wdtype, int64_t ws_outer,
+                    int64_t nred2, int64_t ws_red1, int64_t ws_red2, int64_t ws_inner, double factor, void* out, void* out_w);
+
 /* System sensitivity of a time stream (draco/analysis/sensitivity.py:11-261) and the mask of negative autocorrelations
  * (draco/analysis/flagging.py:666-699), csrc/sensitivity.hip.  vis complex64 and weight float32 are [nf][nstack][nt]
  * [dev] and are read once; sums run in float64 in a fixed order (no atomics: two runs give the same bits) and are
