@@ -55,6 +55,7 @@ DMM_STACK_SRC_CHUNK, DMM_STACK_MAX_FREQ = 256, 2048
 DMM_STACK3D_INPUT, DMM_STACK3D_DEC, DMM_STACK3D_PATCH = 0, 1, 2
 DMM_WD_MAX_FREQ = 1024
 DMM_NRML_MAX_CHAN, DMM_NRML_MAX_DELAY = 1024, 2048
+DMM_WCONV_MAX_TAPS, DMM_RFI_HYST_MAX_SWEEPS = 1023, 4096
 
 
 class DmmError(RuntimeError):
@@ -234,6 +235,12 @@ _SIGS = {
     "dmm_ringmap_stack3d": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "dmm_wienerdelay_build": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 9 + [_i, _i64, C.POINTER(_i64)]),
     "dmm_wienerdelay_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dmm_stokes_i_sum": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "dmm_wconv_filter": (_i, [_vp, _i, _vp, _vp, _i64, _i, _vp, _i, _i, _vp]),
+    "dmm_beam_abs_fft_supported": (_i, [_i]),
+    "dmm_beam_abs_fft": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "dmm_rfi_hysteresis": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "dmm_rfi_beam_count": (_i, [_vp, _vp, _i, _i, _i, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree

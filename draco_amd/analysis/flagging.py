@@ -10,7 +10,8 @@ The RFI part (``flagging.py:1808-2377`` and ``:3231-3381``): ``RFISensitivityMas
 ``ApplyTimeFreqMask`` (alias ``ApplyRFIMask``), ``NegativeAutosMask`` (``:666-699``), with the functions ``mad``,
 ``tv_channels_flag``, ``sigma_to_p``, ``p_to_sigma`` and ``inverse_binom_cdf_prob``; and ``RFIMaskChisqHighDelay``
 (``:1425-1805``), the mask from a chi-squared test statistic, whose medians are weighted (``dmm_rfi_wmedfilt``, DESIGN.md
-section 7s).  The planes stay on the device across the iterations of a mask task:
+section 7s); and ``RFIVisMask`` / ``RFITransientVisMask`` (``:1042-1277``), the mask made from the visibilities themselves
+(``csrc/vismask.hip``).  The planes stay on the device across the iterations of a mask task:
 medians, SumThreshold, SIR and the elementwise stages are the kernels of ``csrc/rfi.hip``; only scalars (the TV
 thresholds, from SciPy) and the frequency-length arrays of the static channel mask are formed on the host.  The
 convention is ``True`` for contaminated samples.
@@ -30,6 +31,8 @@ from ..core import containers, io
 from ..core.task import ContainerTask
 from ..device import Context, ptr
 from ..util import filters, rfi, tools
+from ..util.rfi import apply_hysteresis_threshold  # noqa: F401  (the name the reference's module carries)
+from . import transform
 from .transform import _dev_dataset, axis_reduce_device
 
 
@@ -681,6 +684,180 @@ class RFIMaskChisqHighDelay(ContainerTask):
         """Hook for subclasses: the daytime samples, Boolean ``[ntime]``: they take no part in the channel test and are
         not flagged by the 2-D test."""
         return np.zeros(times.size, dtype=bool)
+
+
+class RFIVisMask(ContainerTask):
+    """Identify and flag RFI in visibility data: the non-functional base class (drop-in for ``flagging.py:1042-1188``).
+
+    Config: ``stokes_i`` (True): flag on the instrumental Stokes-I visibilities (``transform.stokes_I``, a quarter of
+    the baselines) rather than on every stack entry.
+
+    ``process`` turns a ``TimeStream`` into an ``RFIMask`` and a ``SiderealStream`` into a ``SiderealRFIMask``; what
+    the mask is made of is :meth:`generate_mask`, which a subclass supplies.  Visibilities, weights and the initial
+    mask are device tensors.
+    """
+
+    stokes_i = True
+    _config_names = ("stokes_i",)
+
+    SPEED_OF_LIGHT = 299792458.0  # m / s
+
+    telescope = None
+
+    def setup(self, telescope):
+        """``telescope``: the baselines, the latitude and the time maps are read from it."""
+        self.telescope = io.get_telescope(telescope)
+
+    def process(self, stream):
+        """``TimeStream | SiderealStream`` with axes frequency, stack and time / RA -> ``RFIMask | SiderealRFIMask``,
+        True where a sample is flagged."""
+        stream.redistribute("freq")
+        if "time" in stream.index_map:
+            times = stream.time
+            out = containers.RFIMask(axes_from=stream, attrs_from=stream, allocate=False)
+        elif "ra" in stream.index_map:
+            csd = stream.attrs.get("lsd", stream.attrs.get("csd"))
+            if csd is None:
+                raise ValueError("Dataset does not have a `csd` or `lsd` attribute.")
+            times = self.telescope.lsd_to_unix(csd + stream.ra / 360.0)
+            out = containers.SiderealRFIMask(axes_from=stream, attrs_from=stream, allocate=False)
+        else:
+            raise TypeError(f"Expected data with `time` or `ra` axis. Got {type(stream)}.")
+
+        ctx = Context.get()
+        freq = stream.freq
+        if self.stokes_i:
+            vis, weight, baselines = transform.stokes_I(stream, self.telescope)
+        else:
+            vis = _dev_dataset(stream.vis, ctx, np.complex64).contiguous()
+            weight = _dev_dataset(stream.weight, ctx, np.float32).contiguous()
+            baselines = self.telescope.baselines
+
+        mask = weight.eq(0).all(dim=1).to(torch.uint8)
+        static = np.asarray(self._static_rfi_mask_hook(freq, times[0]), dtype=bool)
+        _lib.check(_lib.lib.dmm_rfi_rows(ctx.handle, None, ptr(mask), None, ptr(_u8(ctx, static)), int(mask.shape[0]), int(mask.shape[1])))
+        if self.log.isEnabledFor(logging.DEBUG):
+            self.log.debug(f"{100.0 * float(mask.float().mean()):.2f}% of data initially flagged.")
+
+        result = self.generate_mask(vis, weight, mask, freq, baselines, times)
+        result = result if isinstance(result, torch.Tensor) else ctx.to_device(np.ascontiguousarray(np.asarray(result, dtype=bool)).view(np.uint8))
+        out.attach("mask", result.ne(0) if result.dtype != torch.bool else result)
+        return out
+
+    def generate_mask(self, vis, weight, mask, freq, baselines, times):
+        """The time-frequency mask, ``[nfreq, ntime]`` (a device tensor or an array), True masking a sample.
+
+        ``vis``, ``weight [nfreq, nstack, ntime]``: complex64 / float32 device tensors; ``mask [nfreq, ntime]``: the
+        initial mask, a uint8 device tensor; ``freq`` in MHz; ``baselines [nstack, 2]`` in metres; ``times``: UNIX
+        seconds.  Not implemented in the base class.
+        """
+        raise NotImplementedError
+
+    def _static_rfi_mask_hook(self, freq, timestamp=None):
+        """Hook for subclasses: the channels to mask for the whole stream, ``[nfreq]`` Boolean (True masks a channel).
+        ``timestamp`` is the first time sample.  The default masks none."""
+        return np.zeros_like(freq, dtype=bool)
+
+
+class RFITransientVisMask(RFIVisMask):
+    """Identify and flag transient RFI in visibility data (drop-in for ``flagging.py:1191-1277``).
+
+    Each frequency is high-pass filtered along time (``filters.highpass_weighted_convolution_filter``), transformed
+    across the baseline axis into "beams" and its modulus compared with its moving median in units of its moving MAD
+    (:func:`mad`); a hysteresis threshold keeps what is above ``sigma_high`` and what is above ``sigma_low`` and
+    connected to it.  The SIR operator then runs along time and along frequency, and a time-frequency sample is flagged
+    if more than ``frac_samples`` of its beams are.
+
+    Config (names and defaults are the reference's): ``mad_base_size`` ([1, 101]) and ``mad_dev_size`` ([1, 51]), the
+    (beam, time) windows of the median and of the MAD; ``sigma_high`` (8.0), ``sigma_low`` (2.0); ``frac_samples``
+    (0.01).  ``workspace_mib`` (1024): the device memory the frequency batches of the first phase and the beam slabs of
+    the second are sized for; the result does not depend on it.
+
+    Everything from the stream to the mask runs on the device (``csrc/vismask.hip`` and ``csrc/rfi.hip``, DESIGN.md
+    section 7t); the flag cube ``[freq, beam, time]``, a byte per sample, stays there if it takes at most half the
+    workspace and is staged through the host otherwise.
+    """
+
+    mad_base_size = (1, 101)
+    mad_dev_size = (1, 51)
+    sigma_high = 8.0
+    sigma_low = 2.0
+    frac_samples = 0.01
+    workspace_mib = 1024.0
+    _config_names = ("stokes_i", "mad_base_size", "mad_dev_size", "sigma_high", "sigma_low", "frac_samples", "workspace_mib")
+
+    # device bytes per (beam, time) sample of one frequency in the first phase: the Stokes-I planes (12), the filtered
+    # plane (16), the modulus (8), the two medians, the deviation, the ratio and the flags of `_mad_device` (8 each,
+    # real and imaginary baseline counted), the hysteresis state
+    _PHASE1_BYTES = 12 + 16 + 8 + 6 * 8 + 4
+    # ... and per flag of the second phase: the slab, its copy, the result and the 16 bytes of SIR scratch
+    _PHASE2_BYTES = 3 + 16
+
+    def read_config(self, params):
+        super().read_config(params)
+        for name in ("mad_base_size", "mad_dev_size"):
+            size = tuple(int(s) for s in getattr(self, name))
+            if len(size) != 2:
+                raise ValueError(f"{name} must have two entries, got {size}")
+            setattr(self, name, size)
+
+    def generate_mask(self, vis, weight, mask, freq, baselines, times, info=None):
+        """Mask scattered transient RFI.  Arguments as :meth:`RFIVisMask.generate_mask`; returns a Boolean array.
+        ``info``: a dict that receives the batch sizes and the largest sweep count of the hysteresis."""
+        ctx = Context.get()
+        windows = filters.check_size(self.mad_base_size, 2), filters.check_size(self.mad_dev_size, 2)
+        ra = np.unwrap(self.telescope.unix_to_lsa(times), period=360.0) * np.pi / 180.0
+        dec = np.deg2rad(self.telescope.latitude)
+        lambda_inv = np.min(freq) * 1e6 / self.SPEED_OF_LIGHT
+        hpf_cut = lambda_inv * np.asarray(baselines)[:, 0].max() / np.cos(dec)
+        taps = ctx.to_device(filters.convolution_taps(ra, hpf_cut))
+
+        nfreq, nbeam, ntime = (int(s) for s in vis.shape)
+        if not _lib.lib.dmm_beam_abs_fft_supported(nbeam):
+            raise _lib.DmmError(_lib.DMM_E_UNSUPPORTED, f"RFITransientVisMask: {nbeam} baselines do not fit the in-LDS transform")
+        budget = max(int(float(self.workspace_mib) * (1 << 20)), 1)  # (a fraction of a MiB is accepted: one frequency, one beam at a time)
+        cube_dev = ctx.device if nfreq * nbeam * ntime <= budget // 2 else torch.device("cpu")
+        cube = torch.empty((nfreq, nbeam, ntime), dtype=torch.uint8, device=cube_dev)
+        cube.copy_(mask[:, None, :].expand(nfreq, nbeam, ntime))
+
+        # phase 1: per frequency, in batches
+        active = np.flatnonzero(~mask.ne(0).all(dim=1).cpu().numpy())  # a fully masked frequency is skipped
+        per = max(1, budget // (self._PHASE1_BYTES * nbeam * ntime))
+        sweeps = 0
+        hinfo = {}
+        for i0 in range(0, len(active), per):
+            sel = active[i0 : i0 + per]
+            run = len(sel) == sel[-1] - sel[0] + 1  # adjacent frequencies: views, no gather
+            take = slice(int(sel[0]), int(sel[-1]) + 1) if run else ctx.to_device(sel.astype(np.int64))
+            v, w = vis[take].contiguous(), weight[take].contiguous()
+            hp = filters.wconv_filter_device(ctx, v, w, taps, highpass=True)
+            beams = torch.empty(hp.shape, dtype=torch.float64, device=hp.device)
+            _lib.check(_lib.lib.dmm_beam_abs_fft(ctx.handle, ptr(hp), len(sel), nbeam, ntime, ptr(beams)))
+            del hp
+            flags = mask[take][:, None, :].expand(len(sel), nbeam, ntime).contiguous()
+            ratio = _mad_device(ctx, beams, flags, *windows)[0]
+            rfi.hysteresis_device(ctx, ratio, self.sigma_low, self.sigma_high, out=flags, info=hinfo)
+            sweeps = max(sweeps, hinfo["sweeps"])
+            cube[take if run else torch.as_tensor(sel, device=cube_dev)] = flags.to(cube_dev)
+        ctx.uses(taps)
+
+        # phase 2: SIR along time and along frequency, in slabs of beams, and the count over beams
+        count = torch.zeros((nfreq, ntime), dtype=torch.int32, device=ctx.device)
+        slab_beams = max(1, min(nbeam, budget // (self._PHASE2_BYTES * nfreq * ntime)))
+        keep = mask.eq(0).to(torch.uint8)[:, None, :]
+        for b0 in range(0, nbeam, slab_beams):
+            slab = cube[:, b0 : b0 + slab_beams, :].contiguous().to(ctx.device)
+            nb = int(slab.shape[1])
+            seed = slab * keep  # nothing that was masked to begin with is extended
+            grown = rfi.sir_device(ctx, seed.view(nfreq * nb, ntime), 0.2, 1)
+            rfi.sir_device(ctx, seed.view(nfreq, nb * ntime), 0.1, 0, out=grown.view(nfreq, nb * ntime))
+            _or_into(ctx, slab, grown.view(nfreq, nb, ntime))
+            _lib.check(_lib.lib.dmm_rfi_beam_count(ctx.handle, ptr(slab), nfreq, nb, ntime, ptr(count)))
+        if info is not None:
+            info.update(freq_per_batch=per, beams_per_slab=slab_beams, sweeps=sweeps, cube_on_device=cube_dev.type != "cpu")
+        # count / nbeam is the reference's mean over beams of a Boolean array: an exact integer over nbeam, in float64
+        # (one small plane, compared on the host with NumPy's own division)
+        return (count.cpu().numpy().astype(np.float64) / nbeam) > self.frac_samples
 
 
 def _stack_plane(ds, ind):

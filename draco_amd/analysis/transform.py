@@ -624,3 +624,57 @@ class ReduceChisq(ReduceBase):
 
     def reduction(self, arr, weight, axis):
         return axis_reduce_device(Context.get(), _lib.DMM_REDUCE_CHISQ, arr, weight, axis[0], axis[1])
+
+
+def stokes_i_table(tel):
+    """The products that make up instrumental Stokes I, per unique baseline (``transform.py:1403-1442``).
+
+    The telescope's ``baselines`` are rounded to 0.1 mm and grouped; a product enters its baseline's sum if it is
+    co-polar, if its baseline occurs with all four polarisation pairs, and if its ``feedmap`` entry is not -1.  Returns
+    ``(ubase [nbase, 2], ptr [nbase + 1], rows)``, the products of baseline ``b`` being ``rows[ptr[b]:ptr[b + 1]]`` in
+    ascending order, the order in which the reference accumulates them.
+    """
+    bl_round = np.around(tel.baselines[:, 0] + 1.0j * tel.baselines[:, 1], 4)
+    ubase, uinv, ucount = np.unique(bl_round, return_inverse=True, return_counts=True)
+    ubase = ubase.astype(np.complex128, copy=False).view(np.float64).reshape(-1, 2)
+    pairs = np.asarray(tel.uniquepairs)
+    pols = np.asarray(tel.polarisation)[pairs]
+    keep = (pols[:, 0] == pols[:, 1]) & (ucount[uinv] >= 4) & (np.asarray(tel.feedmap)[pairs[:, 0], pairs[:, 1]] != -1)
+    prods = np.flatnonzero(keep)
+    order = np.argsort(uinv[prods], kind="stable")  # by baseline, ascending product within one
+    rows = prods[order].astype(np.int32)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(uinv[prods], minlength=len(ubase)))]).astype(np.int32)
+    return ubase, ptr, rows
+
+
+def stokes_i_device(ctx, vis, weight, base_ptr, rows):
+    """``vis [nf, nprod, nt]`` complex64 and ``weight`` float32 device tensors -> ``(vis_I, weight_I)`` ``[nf, nbase,
+    nt]`` (``dmm_stokes_i_sum``); ``base_ptr`` / ``rows``: int32 device tensors of :func:`stokes_i_table`."""
+    nf, nprod, nt = (int(s) for s in vis.shape)
+    nbase = int(base_ptr.numel()) - 1
+    vis_i = torch.empty((nf, nbase, nt), dtype=torch.complex64, device=vis.device)
+    weight_i = torch.empty((nf, nbase, nt), dtype=torch.float32, device=vis.device)
+    if vis_i.numel():
+        _lib.check(_lib.lib.dmm_stokes_i_sum(ctx.handle, ptr(vis), ptr(weight), nf, nprod, nt, ptr(base_ptr), ptr(rows), nbase, int(rows.numel()), ptr(vis_i), ptr(weight_i)))
+    return vis_i, weight_i
+
+
+def stokes_I(sstream, tel):
+    """Extract instrumental Stokes I from a time / sidereal stream (``transform.py:1382-1448``).
+
+    Returns ``(vis_I, weight_I, ubase)``: ``[nfreq, nbase, ntime]`` complex64 and float32 device tensors and the
+    ``[nbase, 2]`` baseline vectors.  The sums are the reference's (:func:`stokes_i_table`), accumulated in the
+    stream's own precision in product order.  A telescope whose redundancy classes do not hold all four polarisation
+    pairs per baseline (``pair_rule="canonical"``) keeps nothing: every row comes back zero.
+    """
+    sstream.redistribute("freq")
+    ctx = Context.get()
+    ubase, ptr_h, rows_h = stokes_i_table(tel)
+    vis = _dev_dataset(sstream.vis, ctx, np.complex64).contiguous()
+    weight = _dev_dataset(sstream.weight, ctx, np.float32).contiguous()
+    if int(vis.shape[1]) != len(tel.uniquepairs):
+        raise ValueError(f"stokes_I: the stream has {int(vis.shape[1])} stack entries, the telescope {len(tel.uniquepairs)} unique pairs")
+    ptr_d, rows_d = ctx.to_device(ptr_h), ctx.to_device(rows_h if len(rows_h) else np.zeros(1, dtype=np.int32))
+    vis_i, weight_i = stokes_i_device(ctx, vis, weight, ptr_d, rows_d[: len(rows_h)])
+    ctx.uses(ptr_d, rows_d)
+    return vis_i, weight_i, ubase

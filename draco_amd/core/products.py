@@ -129,6 +129,11 @@ class TransitTelescope:
         """Inverse of :meth:`unix_to_lsd`."""
         return (np.asarray(lsd, dtype=np.float64) - self.longitude / 360.0) * self.SIDEREAL_S + self.lsd_start
 
+    def unix_to_lsa(self, unix):
+        """Local stellar angle in degrees, ``360 (unix_to_lsd(unix) mod 1)``: the same LINEAR stand-in for caput's
+        ``Observer.unix_to_lsa`` [3P] as :meth:`unix_to_lsd`."""
+        return 360.0 * np.mod(self.unix_to_lsd(unix), 1.0)
+
     def _build_pairs(self):
         """Redundancy of a regular cylinder grid, autos included."""
         self._free = False

@@ -11,6 +11,10 @@ or not.  :func:`moving_weighted_median` takes real weights and longer windows (`
 cutoff, num_modes)``, on the unmasked samples: ``dmm_nullfilter_build`` (``csrc/nullfilter.hip``)
 takes the SVD of the real form of that matrix by a batched one-sided Jacobi in float64.  :func:`build_null_filters` is
 the batched form the tasks of ``draco_amd.analysis.delay`` use.
+
+``lowpass_weighted_convolution_filter`` / ``highpass_weighted_convolution_filter`` (``draco/util/filters.py:22-96``): the
+taps are designed on the host as the reference designs them, the weighted convolution is ``dmm_wconv_filter``
+(``csrc/vismask.hip``), a direct sum in float64.
 """
 
 from __future__ import annotations
@@ -162,6 +166,83 @@ def moving_weighted_median(x, w, size):
     if ndim == 1:
         out = out.reshape(-1)
     return out if is_tensor else out.cpu().numpy()
+
+
+# ---- the weighted convolution filter
+
+
+def convolution_taps(samples, cutoff):
+    """The FIR taps of the weighted convolution filter, float64 on the host, exactly as the reference designs them: the
+    median sampling rate ``fs``, an odd ``order = ceil(fs / cutoff) // 2 * 2 + 1`` and a flat-top windowed
+    ``scipy.signal.firwin``.  A ``ValueError`` of firwin (a cutoff at or above ``fs / 2``) propagates."""
+    from scipy import signal
+
+    fs = 1 / np.median(abs(np.diff(samples)))
+    order = int(np.ceil(fs / cutoff) // 2 * 2 + 1)
+    taps = np.ascontiguousarray(signal.firwin(order, cutoff, window="flattop", fs=fs), dtype=np.float64)
+    if len(taps) > _lib.DMM_WCONV_MAX_TAPS:
+        raise ValueError(f"weighted convolution filter: {len(taps)} taps, at most {_lib.DMM_WCONV_MAX_TAPS} are supported")
+    return taps
+
+
+def wconv_filter_device(ctx, data, weight, taps, highpass=False):
+    """``data [..., n]`` (complex64 with a float32 weight, or complex128 / float64 with a float64 weight) and ``weight``
+    of the same shape, contiguous device tensors; ``taps`` float64 on the host or the device.  Returns the low-pass
+    ``conv(d w) inz(conv(w))`` (or ``d`` minus it) as a new complex128 / float64 tensor."""
+    kind = {torch.complex64: (_lib.DMM_REDUCE_C64, torch.float32, torch.complex128), torch.complex128: (_lib.DMM_REDUCE_C128, torch.float64, torch.complex128),
+            torch.float64: (_lib.DMM_REDUCE_F64, torch.float64, torch.float64)}.get(data.dtype)
+    if kind is None:
+        raise TypeError(f"weighted convolution filter: data of type {data.dtype} is not supported")
+    if weight.dtype != kind[1] or tuple(weight.shape) != tuple(data.shape):
+        raise TypeError(f"weighted convolution filter: {data.dtype} data {tuple(data.shape)} needs a {kind[1]} weight of the same shape, got {weight.dtype} {tuple(weight.shape)}")
+    taps_d = taps if isinstance(taps, torch.Tensor) else ctx.to_device(np.ascontiguousarray(taps, dtype=np.float64))
+    data, weight = data.contiguous(), weight.contiguous()
+    out = torch.empty(data.shape, dtype=kind[2], device=data.device)
+    n = int(data.shape[-1])
+    if data.numel():
+        _lib.check(_lib.lib.dmm_wconv_filter(ctx.handle, kind[0], ptr(data), ptr(weight), data.numel() // n, n, ptr(taps_d), int(taps_d.numel()), int(bool(highpass)), ptr(out)))
+    ctx.uses(taps_d)
+    return out
+
+
+def _wconv(data, weight, samples, cutoff, axis, highpass):
+    is_tensor = isinstance(data, torch.Tensor)
+    taps = convolution_taps(np.asarray(samples.cpu() if isinstance(samples, torch.Tensor) else samples), cutoff)
+    ctx = Context.get()
+    d = data.to(ctx.device) if is_tensor else ctx.to_device(np.asarray(data))
+    w = weight.to(ctx.device) if isinstance(weight, torch.Tensor) else ctx.to_device(np.asarray(weight))
+    if d.dtype == torch.float32:
+        d = d.to(torch.float64)
+    if d.dtype not in (torch.complex64, torch.complex128, torch.float64):
+        raise TypeError(f"weighted convolution filter: data of type {d.dtype} is not supported")
+    if w.is_complex():
+        raise TypeError("weighted convolution filter: the weight must be real")
+    w = torch.broadcast_to(w.to(torch.float32 if d.dtype == torch.complex64 else torch.float64), d.shape)
+    d, w = torch.movedim(d, axis, -1).contiguous(), torch.movedim(w, axis, -1).contiguous()
+    out = torch.movedim(wconv_filter_device(ctx, d, w, taps, highpass), -1, axis)
+    return out if is_tensor else out.cpu().numpy()
+
+
+def lowpass_weighted_convolution_filter(data, weight, samples, cutoff, axis=-1):
+    """Apply a low-pass weighted convolution filter along an axis (``filters.py:22-65``).
+
+    ``data``: real or complex; ``weight``: its weights; ``samples``: the sample positions along ``axis``; ``cutoff``:
+    the cutoff frequency in their inverse units.  With ``h`` the taps (:func:`convolution_taps`) the result is
+    ``(h * (d w)) inz(h * w)``, each convolution the slice of the full one that is centred on the data (SciPy's
+    ``mode="same"``), ``inz(v) = 1 / v`` and 0 for 0.  NumPy in, NumPy out; device tensors in, a device tensor out.
+    The result is complex128 or float64.
+
+    The sums are direct, in float64: over a window of zero weights ``h * w`` is exactly zero and so is the result.  The
+    reference convolves by FFT in the input's precision, where that sum is rounding noise and its inverse a number of
+    order one.
+    """
+    return _wconv(data, weight, samples, cutoff, axis, False)
+
+
+def highpass_weighted_convolution_filter(data, weight, samples, cutoff, axis=-1):
+    """Apply a crude high-pass weighted convolution filter along an axis (``filters.py:68-96``): the data minus
+    :func:`lowpass_weighted_convolution_filter` of them."""
+    return _wconv(data, weight, samples, cutoff, axis, True)
 
 
 # ---- the delay null-space filter

@@ -3,6 +3,9 @@
 Signatures, defaults and errors are the reference's.  NumPy arrays go in and come out, or device tensors do; the work
 is ``dmm_rfi_sumthreshold`` / ``dmm_rfi_sir`` (``csrc/rfi.hip``) either way.  The planes are two-dimensional
 ``[freq, time]`` (a one-dimensional array is one line); the deprecated ``sir`` is not carried.
+
+``apply_hysteresis_threshold`` is scikit-image's function of that name [3P], which ``RFITransientVisMask`` calls: here
+``dmm_rfi_hysteresis`` (``csrc/vismask.hip``).
 """
 
 from __future__ import annotations
@@ -126,6 +129,58 @@ def sumthreshold_py(
 
 
 sumthreshold = sumthreshold_py  # the reference exports the routine under both names
+
+
+def hysteresis_device(ctx, x, low, high, out=None, info=None):
+    """The hysteresis threshold of float64 ``[..., nf, nt]`` device planes (``dmm_rfi_hysteresis``): a new uint8 tensor,
+    or OR-ed into ``out``.  ``info``: a dict that receives ``sweeps``."""
+    nf, nt = int(x.shape[-2]), int(x.shape[-1])
+    nplane = x.numel() // (nf * nt) if nf * nt else 0
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    sweeps = C.c_int32(0)
+    if x.numel():
+        state = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        changed = torch.empty(1, dtype=torch.int32, device=x.device)
+        # planes beyond the grid's 65535 go in runs
+        xf, of, sf = x.reshape(nplane, nf, nt), out.reshape(nplane, nf, nt), state.reshape(nplane, nf, nt)
+        total = 0
+        for p0 in range(0, nplane, 65535):
+            p1 = min(nplane, p0 + 65535)
+            _lib.check(_lib.lib.dmm_rfi_hysteresis(ctx.handle, ptr(xf[p0:p1]), p1 - p0, nf, nt, float(low), float(high), int(accumulate), ptr(sf[p0:p1]), ptr(changed),
+                                                   ptr(of[p0:p1]), C.byref(sweeps)))
+            total = max(total, sweeps.value)
+        sweeps = C.c_int32(total)
+    if info is not None:
+        info["sweeps"] = int(sweeps.value)
+    return out
+
+
+def apply_hysteresis_threshold(image, low, high):
+    """Hysteresis threshold (scikit-image's ``filters.apply_hysteresis_threshold``, as ``flagging.py:1262`` calls it).
+
+    True at every sample above ``low`` whose connected region of samples above ``low`` -- neighbours along the last two
+    axes, no diagonals -- holds a sample above ``high``.  Comparisons are strict; a NaN is in neither set; ``low`` is
+    ``min(low, high)``.  ``image``: one line, one ``[nf, nt]`` plane, or planes ``[..., nf, nt]`` that are treated one
+    by one.  NumPy in, NumPy out; a device tensor in, a device tensor out.
+    """
+    is_tensor = isinstance(image, torch.Tensor)
+    ndim = image.dim() if is_tensor else np.ndim(image)
+    if ndim < 1:
+        raise ValueError("apply_hysteresis_threshold needs at least one dimension")
+    if np.isnan(low) or np.isnan(high):
+        raise ValueError("apply_hysteresis_threshold: a threshold is NaN")
+    if (image.is_complex() if is_tensor else np.iscomplexobj(image)):
+        raise ValueError("apply_hysteresis_threshold takes real data")
+    ctx = Context.get()
+    x = ctx.to_device(image if is_tensor else np.asarray(image), np.float64).contiguous()
+    if ndim == 1:
+        x = x.reshape(1, -1)
+    out = hysteresis_device(ctx, x, low, high).ne(0)
+    if ndim == 1:
+        out = out.reshape(-1)
+    return out if is_tensor else out.cpu().numpy()
 
 
 _SIR_WORK = {}

@@ -1147,6 +1147,39 @@ int dmm_wienerdelay_build(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, i
 int dmm_wienerdelay_apply(dmm_ctx* ctx, int npol, int nfreq, int nra, int nel, int ndelay, const void* op, int op_dtype, const double* map, const double* weight, void* spectrum,
                           float* sweight);
 
+/* Transient RFI mask from visibilities (draco/analysis/flagging.py:1042-1277, draco/analysis/transform.py:1382-1448,
+ * draco/util/filters.py:22-96), csrc/vismask.hip.  No floating-point atomics: two runs give the same bits.  Everything
+ * is [dev] unless marked [host]; every argument is checked before anything is launched.
+ * dmm_stokes_i_sum: vis [nf][nprod][nt] complex64 and weight float32 -> vis_i [nf][nbase][nt] = the sum over the rows
+ * rows[ptr[b] ... ptr[b+1]) of baseline b, in ascending order of the table, in complex64 / float32 from a zero (the
+ * reference's `+=`, bit for bit); weight_i likewise.  A baseline without rows is a zero row.  ptr [nbase + 1], rows
+ * [nrows] int32; an index outside its axis is clamped.
+ * dmm_wconv_filter: per row of data [nrow][n] (dtype DMM_REDUCE_C64 with float32 weight, DMM_REDUCE_C128 or
+ * DMM_REDUCE_F64 with float64 weight) and taps [ntap] float64, ntap odd, c = (ntap - 1) / 2, samples outside the row
+ * zero: vw[t] = sum_j taps[j] (d w)[t + c - j], ww[t] = sum_j taps[j] w[t + c - j], lp = vw inz(ww), inz(v) = 1 / v and
+ * 0 for v = 0 -- the centred slice of the full convolution, also for ntap > n.  Sums are float64 in ascending j, one
+ * rounding at the store.  out [nrow][n] complex128 / float64 = lp, or d - lp with highpass.  ntap <= DMM_WCONV_MAX_TAPS.
+ * dmm_beam_abs_fft: x [nplane][nstack][nt] complex128 -> out (float64, same shape) [p][k][t] = |sum_s x[p][s][t]
+ * exp(-2 pi i k s / nstack)|, one in-LDS transform per column.  dmm_beam_abs_fft_supported(n): as dmm_uv_fft2_supported
+ * (powers of two to 8192, other lengths to 4096); a longer axis is DMM_E_UNSUPPORTED, before anything is launched.
+ * dmm_rfi_hysteresis: x [nplane][nf][nt] float64, low <- min(low, high): out (bytes) = 1 at every sample with x > low
+ * whose 4-connected component of {x > low} within its plane holds a sample with x > high; comparisons are strict, a NaN
+ * is in neither set.  accumulate: out |= that.  state [nplane nf nt] bytes and changed [1] int32 are scratch.  *sweeps
+ * [host] (may be NULL) receives the number of sweeps (rows both ways, then columns both ways), the last of which
+ * changed nothing; DMM_E_STATE, and an unfinished out left unwritten, if DMM_RFI_HYST_MAX_SWEEPS did not reach the fixed
+ * point.  Synchronises the context's stream once per sweep.
+ * dmm_rfi_beam_count: count [nf][nt] int32 += #{b : flag[f][b][t] != 0}, flag [nf][nb][nt] bytes. */
+#define DMM_WCONV_MAX_TAPS 1023
+#define DMM_RFI_HYST_MAX_SWEEPS 4096
+int dmm_stokes_i_sum(dmm_ctx* ctx, const void* vis, const float* weight, int nf, int nprod, int nt, const int32_t* ptr, const int32_t* rows, int nbase, int nrows,
+                     void* vis_i, float* weight_i);
+int dmm_wconv_filter(dmm_ctx* ctx, int dtype, const void* data, const void* weight, int64_t nrow, int n, const double* taps, int ntap, int highpass, void* out);
+int dmm_beam_abs_fft_supported(int n);
+int dmm_beam_abs_fft(dmm_ctx* ctx, const void* x, int nplane, int nstack, int nt, double* out);
+int dmm_rfi_hysteresis(dmm_ctx* ctx, const double* x, int nplane, int nf, int nt, double low, double high, int accumulate, uint8_t* state, int32_t* changed, uint8_t* out,
+                       int32_t* sweeps);
+int dmm_rfi_beam_count(dmm_ctx* ctx, const uint8_t* flag, int nf, int nb, int nt, int32_t* count);
+
 #ifdef __cplusplus
 }
 #endif
