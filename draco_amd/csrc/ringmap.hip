@@ -11,18 +11,20 @@
 // All HBM-bound elementwise / small-reduction work plus one length-nra inverse FFT per
 // (pol, freq, el):
 //   k_rm_reduce  lanes across el (coalesced 512-byte row pieces of hv / bv), the (+/-, ew) sums in registers, the modes transposed through LDS to rows contiguous in m, and the
-//                block's share of the three per-row sums over m the next stage needs (normalisation, noise weight,
-//                dirty-beam power by Parseval), so that every mode is read ONCE downstream;
+//                block's share of the four per-row sums over m the next stage needs (normalisation, noise weight,
+//                dirty-beam power by Parseval, the norm of the map modes), so that every mode is read ONCE downstream;
 //   k_rm_fft     one inverse FFT per TWO rows: the Hermitian spectra of two rows' map modes are packed into one
 //                complex sequence z = X_map(row0) + i X_map(row1) (when the RA-space dirty beam is asked for:
-//                z = X_map + i X_dirty of one row); powers of two run the in-LDS radix passes, other lengths
-//                Bluestein (shared machinery, fft_lds.h);
+//                z = X_map + i X_dirty of one row), each of the two scaled by a power of two to the other's size
+//                (rm_seq_scale); powers of two run the in-LDS radix passes, other lengths Bluestein (shared machinery,
+//                fft_lds.h);
 //   k_rm_store   tiled transpose [el][ra] -> the reference's [ra][el] layout.
 // Where nra is a power of two, the RA-space dirty beam is not asked for and every row is normalised by itself:
 //   k_rm_fused<EL, PARK>  the three stages in one pass: a block owns 8 or 16 elevations of one (pol, freq) for all m, so
 //                neither the modes nor the [el][ra] rows reach HBM (16 elevations: 128-byte pieces of the input rows;
 //                PARK: the second eight's image waits in a scratch image while the first eight's is transformed).
-// The term-weight rule (rm_term_weight), the per-(m, el) mode (rm_mode) and the row finish (rm_row_finish) are shared.
+// The term-weight rule (rm_term_weight), the per-(m, el) mode (rm_mode), the row finish (rm_row_finish) and the scaling of the
+// two sequences that share a transform (rm_seq_scale) are shared.
 // float64 arithmetic throughout (the reference mixes float32 and float64 by weight scheme).
 #include <math.h>
 
@@ -33,6 +35,12 @@ namespace {
 
 using dmm_fft::C;
 constexpr int kThreads = 256;
+
+// What a row needs from all its m before its transform, four sums: dirty (point-source normalisation), q^2 (noise weight),
+// c_m dirty^2 (dirty-beam power by Parseval; the scale of the dirty-beam modes) and c_m |map_m|^2 (the scale of the map modes).
+struct RmSums {
+  double d, q2, p2, x2;
+};
 
 struct RmParams {
   int nm, nm_beam, npol, nfreq, new_, nel, nra, mmax;
@@ -47,7 +55,7 @@ struct RmParams {
   const float* window;  // [nfreq, nm, nel] or null
   double2* s_map;     // [npol*nfreq][nel][nm] map modes (re, im)
   double* s_dirty;    // [npol*nfreq][nel][nm] dirty-beam modes (real)
-  double4* psum;      // [npol*nfreq][nchunk][nel] partial sums over the chunk's m: {dirty, q^2, c_m dirty^2, -}
+  RmSums* psum;       // [npol*nfreq][nchunk][nel] the chunk's share of the per-row sums over m
   double* tmp_map;    // [npol*nfreq][nel][nra]
   double* tmp_db;     // same or null
   double* dbp;        // [npol*nfreq][nel]   -> dirty_beam_power [1, npol, nfreq, nel]
@@ -82,10 +90,10 @@ __device__ __forceinline__ void rm_term_weight(const RmParams& p, int m, int pol
   g = w * w * (iv > 0.0 ? 1.0 / iv : 0.0);
 }
 
-// One (m, el) from its (+/-, ew) sums: the map mode (ar, ai), the dirty-beam mode rd, and the mode's share of the three
-// per-row sums over m -- dirty (point-source normalisation), q^2 (noise weight), c_m dirty^2 (dirty-beam power by Parseval).
+// One (m, el) from its (+/-, ew) sums: the map mode (ar, ai), the dirty-beam mode rd, and the mode's share of the four
+// per-row sums over m (RmSums).
 __device__ __forceinline__ void rm_mode(const RmParams& p, double sw, double mre, double mim, double sg, int m, int f, int el,
-                                        double& ar, double& ai, double& rd, double& acc_d, double& acc_q, double& acc_p) {
+                                        double& ar, double& ai, double& rd, double& acc_d, double& acc_q, double& acc_p, double& acc_x) {
   const double cinv = p.skip ? 1.0 : p.eps[(int64_t)f * p.nm + m] + sw;
   const double ic = cinv != 0.0 ? 1.0 / cinv : 0.0;
   const double win = p.window ? (double)p.window[((int64_t)f * p.nm + m) * p.nel + el] : 1.0;
@@ -96,7 +104,25 @@ __device__ __forceinline__ void rm_mode(const RmParams& p, double sw, double mre
   acc_d += rd;
   acc_q += qv * qv;
   // weight of mode m in sum_k X_ext(k)^2 of the Hermitian extension to N bins: DC and (even N) Nyquist once
-  acc_p += ((m == 0 || 2 * m == p.nra) ? 1.0 : 2.0) * rd * rd;
+  const bool edge = m == 0 || 2 * m == p.nra;
+  acc_p += (edge ? 1.0 : 2.0) * rd * rd;
+  acc_x += edge ? ar * ar : 2.0 * (ar * ar + ai * ai);  // (the transform drops the imaginary part of the DC and Nyquist modes)
+}
+
+// Two real sequences share one complex transform, z = X_A + i X_B, whose rounding error is relative to the norm of z: a
+// weak row -- an elevation far down the beam, a row whose regularisation dwarfs its weights -- beside a strong one would
+// come out with the strong one's absolute error.  So each sequence goes in divided by a power of two near the norm of
+// its spectrum (exact; `x2` = sum_k |X_ext(k)|^2) and comes out multiplied by it: `scl` on the way in, `isc` on the way
+// out.  A sequence without any mode comes out as zeros whatever its partner leaves behind (isc = 0).
+__device__ __forceinline__ void rm_seq_scale(double x2, double& scl, double& isc) {
+  scl = 1.0;
+  isc = x2 == 0.0 ? 0.0 : 1.0;
+  if (x2 > 0.0 && x2 < INFINITY) {
+    int e = ilogb(x2) >> 1;
+    e = e < -480 ? -480 : (e > 480 ? 480 : e);
+    scl = ldexp(1.0, -e);
+    isc = ldexp(1.0, e);
+  }
 }
 
 // A row from its three sums over m: normalisation, noise weight, and the dirty-beam power by Parseval --
@@ -111,21 +137,20 @@ __device__ __forceinline__ void rm_row_finish(double d, double q2, double p2, in
 
 // One (el tile, 16 m, pol x freq) per block; EPL elevations per lane (1 is what ships).
 // Per (m, el): the (+/-, ew) sums, the map / dirty-beam modes (to s_map / s_dirty, transposed through LDS so that
-// rows are contiguous in m) and the block's share of three sums over m that the FFT stage needs per row -- dirty
-// (point-source normalisation), q^2 (noise weight) and c_m dirty^2 (dirty-beam power by Parseval) -- so that the FFT
-// stage reads every mode once.
+// rows are contiguous in m) and the block's share of the four sums over m that the FFT stage needs per row (RmSums), so
+// that the FFT stage reads every mode once.
 template <int EPL>
 __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
   constexpr int ET = 64 * EPL;
   __shared__ double2 tmap[MT][ET + 1];
   __shared__ double tdirty[MT][ET + 1];
-  __shared__ double wsum[3][kThreads / 64][ET];
+  __shared__ double wsum[4][kThreads / 64][ET];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int el0 = blockIdx.x * ET, m0 = blockIdx.y * MT, pf = blockIdx.z;
   const int pol = pf / p.nfreq, f = pf - pol * p.nfreq;
-  double acc_d[EPL], acc_q[EPL], acc_p[EPL];
+  double acc_d[EPL], acc_q[EPL], acc_p[EPL], acc_x[EPL];
 #pragma unroll
-  for (int u = 0; u < EPL; ++u) acc_d[u] = acc_q[u] = acc_p[u] = 0.0;
+  for (int u = 0; u < EPL; ++u) acc_d[u] = acc_q[u] = acc_p[u] = acc_x[u] = 0.0;
   for (int mi = wave; mi < MT; mi += kThreads / 64) {
     const int m = m0 + mi;
     double sw[EPL], mre[EPL], mim[EPL], sg[EPL];
@@ -181,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
     for (int u = 0; u < EPL; ++u) {
       double2 rm = make_double2(0.0, 0.0);
       double rd = 0.0;
-      if (m < p.nm && el + u < p.nel) rm_mode(p, sw[u], mre[u], mim[u], sg[u], m, f, el + u, rm.x, rm.y, rd, acc_d[u], acc_q[u], acc_p[u]);
+      if (m < p.nm && el + u < p.nel) rm_mode(p, sw[u], mre[u], mim[u], sg[u], m, f, el + u, rm.x, rm.y, rd, acc_d[u], acc_q[u], acc_p[u], acc_x[u]);
       tmap[mi][EPL * lane + u] = rm;
       tdirty[mi][EPL * lane + u] = rd;
     }
@@ -191,17 +216,19 @@ __global__ __launch_bounds__(kThreads) void k_rm_reduce(RmParams p) {
     wsum[0][wave][EPL * lane + u] = acc_d[u];
     wsum[1][wave][EPL * lane + u] = acc_q[u];
     wsum[2][wave][EPL * lane + u] = acc_p[u];
+    wsum[3][wave][EPL * lane + u] = acc_x[u];
   }
   __syncthreads();
   // this block's share of the per-row sums, waves added in a fixed order
   for (int e = threadIdx.x; e < ET; e += kThreads) {
     if (el0 + e < p.nel) {
-      double4 t = make_double4(wsum[0][0][e], wsum[1][0][e], wsum[2][0][e], 0.0);
+      RmSums t = {wsum[0][0][e], wsum[1][0][e], wsum[2][0][e], wsum[3][0][e]};
 #pragma unroll
       for (int w2 = 1; w2 < kThreads / 64; ++w2) {
-        t.x += wsum[0][w2][e];
-        t.y += wsum[1][w2][e];
-        t.z += wsum[2][w2][e];
+        t.d += wsum[0][w2][e];
+        t.q2 += wsum[1][w2][e];
+        t.p2 += wsum[2][w2][e];
+        t.x2 += wsum[3][w2][e];
       }
       p.psum[((int64_t)pf * p.nchunk + blockIdx.y) * p.nel + el0 + e] = t;
     }
@@ -240,6 +267,7 @@ __device__ __forceinline__ void rm_spec(const RmParams& p, int64_t row, int k, i
 template <int PAIR>
 __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int kRbMax = 8;  // (the plan's rb_max)
   C<double>* buf = reinterpret_cast<C<double>*>(smem);
   const bool blue = q.chirp != nullptr;
   const int N = p.nra, M = q.M, RB = q.RB, P = q.P;
@@ -247,6 +275,46 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   const int64_t t0 = (int64_t)blockIdx.x * RB;  // first transform of the block; transform t holds rows PAIR t (, +1)
   const C<double>* tw = dmm_fft::stage_twiddles<double, kThreads, true>(q, buf + (size_t)RB * P);
   const int half = (N - 1) / 2;
+  // per transform and sequence: the row's normalisation, noise weight and dirty-beam power (PAIR = 2: sequence w is row
+  // row0 + w; PAIR = 1: both are row0's), and the sequence's scale in and out of the transform (rm_seq_scale)
+  __shared__ double s_nrm[kRbMax][2], s_wv[kRbMax][2], s_dbp[kRbMax][2], s_scl[kRbMax][2], s_isc[kRbMax][2];
+  // per-row sums over m from the reduce stage's chunk partials: a wave per row, lanes over the chunks, then a butterfly
+  // -- the same order every time
+  for (int job = threadIdx.x >> 6; job < RB * PAIR; job += kThreads / 64) {
+    const int r = job / PAIR, w2 = job - r * PAIR, ln = threadIdx.x & 63;
+    const int64_t row = (t0 + r) * PAIR + w2;
+    double d = 0.0, q2 = 0.0, p2 = 0.0, x2 = 0.0, d1 = 0.0;
+    if (row < nrow) {
+      const int64_t pf = row / p.nel;
+      const int el = (int)(row - pf * p.nel);
+      const int eln = p.skip ? p.iref : el;  // skip_deconvolution: normalised at the reference declination
+      for (int c = ln; c < p.nchunk; c += 64) {
+        d += p.psum[(pf * p.nchunk + c) * p.nel + eln].d;
+        const RmSums t = p.psum[(pf * p.nchunk + c) * p.nel + el];
+        q2 += t.q2;
+        p2 += t.p2;
+        x2 += t.x2;
+        d1 += t.d;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      d += __shfl_xor(d, o, 64);
+      q2 += __shfl_xor(q2, o, 64);
+      p2 += __shfl_xor(p2, o, 64);
+      x2 += __shfl_xor(x2, o, 64);
+      d1 += __shfl_xor(d1, o, 64);
+    }
+    if (ln == 0) {  // (a row past the end: all zero)
+      rm_row_finish(d, q2, p2, p.nm, N, s_nrm[r][w2], s_wv[r][w2], s_dbp[r][w2]);
+      rm_seq_scale(x2, s_scl[r][w2], s_isc[r][w2]);
+      // (the dirty-beam modes add up in phase at RA 0.  Beside the map it is that peak, the sum of the modes, that has to
+      // be of the map's size: Bluestein's last product mixes the two, and the peak's rounding would be the map's error
+      // there.  The beam's sidelobes in turn take the map's rounding, so the peak is left four times the map's norm.)
+      if (PAIR == 1) rm_seq_scale(fmax(p2, 0.0625 * d1 * d1), s_scl[r][1], s_isc[r][1]);
+    }
+  }
+  __syncthreads();
   for (int idx = threadIdx.x; idx < RB * M; idx += kThreads) {
     const int r = idx / M, k = idx - r * M;
     C<double> v = {0.0, 0.0};
@@ -259,6 +327,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
       } else {
         rm_spec(p, row0, k, N, half, true, br, bi);
       }
+      ar *= s_scl[r][0], ai *= s_scl[r][0], br *= s_scl[r][1], bi *= s_scl[r][1];
       // z = A + i B = (ar - bi) + i (ai + br); we load conj(z)
       v = {ar - bi, -(ai + br)};
       if (blue) v = dmm_fft::cmul<double>(v, {q.chirp[k].x, q.chirp[k].y});
@@ -280,38 +349,13 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
   } else {
     dmm_fft::row_fft_inverse<double, kThreads>(q, false, buf, tw);
   }
-  // finish: y = conj(result) / N; first output = Re y, second = Im y, each times its row's normalisation
+  // finish: y = conj(result) / N; first output = Re y, second = Im y, each times its row's normalisation and its
+  // sequence's scale
   __shared__ double red[kThreads];
-  __shared__ double s_nrm[2], s_wv[2], s_dbp[2];
   for (int r = 0; r < RB; ++r) {
     const int64_t row0 = (t0 + r) * PAIR;
     if (row0 >= nrow) break;  // uniform
-    // per-row sums over m from the reduce stage's chunk partials (fixed order): wave w < PAIR serves row0 + w
-    if ((threadIdx.x >> 6) < PAIR) {  // lanes over the chunks, then a butterfly: the same order every time
-      const int w2 = threadIdx.x >> 6, ln = threadIdx.x & 63;
-      const int64_t row = row0 + w2;
-      double d = 0.0, q2 = 0.0, p2 = 0.0;
-      if (row < nrow) {
-        const int64_t pf = row / p.nel;
-        const int el = (int)(row - pf * p.nel);
-        const int eln = p.skip ? p.iref : el;  // skip_deconvolution: normalised at the reference declination
-        for (int c = ln; c < p.nchunk; c += 64) {
-          d += p.psum[(pf * p.nchunk + c) * p.nel + eln].x;
-          const double4 t = p.psum[(pf * p.nchunk + c) * p.nel + el];
-          q2 += t.y;
-          p2 += t.z;
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        d += __shfl_xor(d, o, 64);
-        q2 += __shfl_xor(q2, o, 64);
-        p2 += __shfl_xor(p2, o, 64);
-      }
-      if (ln == 0) rm_row_finish(d, q2, p2, p.nm, N, s_nrm[w2], s_wv[w2], s_dbp[w2]);  // (a row past the end: all zero)
-    }
-    __syncthreads();
-    const double sc0 = s_nrm[0] / (double)N, sc1 = s_nrm[PAIR - 1] / (double)N;
+    const double sc0 = s_nrm[r][0] / (double)N * s_isc[r][0], sc1 = s_nrm[r][PAIR - 1] / (double)N * s_isc[r][1];
     double pw = 0.0;
     for (int n = threadIdx.x; n < N; n += kThreads) {
       C<double> v = buf[r * P + n];
@@ -320,7 +364,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
       if (PAIR == 2) {
         if (row0 + 1 < nrow) p.tmp_map[(row0 + 1) * N + n] = -v.y * sc1;
       } else {
-        const double dbv = -v.y * sc0;
+        const double dbv = -v.y * sc1;
         if (p.tmp_db) p.tmp_db[row0 * N + n] = dbv;
         pw += dbv * dbv;
       }
@@ -335,8 +379,8 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
     }
     if (threadIdx.x < PAIR && row0 + threadIdx.x < nrow) {
       const int w2 = threadIdx.x;
-      p.dbp[row0 + w2] = PAIR == 1 ? red[0] / (double)N : s_dbp[w2];
-      p.wv[row0 + w2] = s_wv[w2];
+      p.dbp[row0 + w2] = PAIR == 1 ? red[0] / (double)N : s_dbp[r][w2];
+      p.wv[row0 + w2] = s_wv[r][w2];
     }
     __syncthreads();
   }
@@ -346,8 +390,8 @@ __global__ __launch_bounds__(kThreads) void k_rm_fft(RmParams p, RmFft q) {
 // normalisation): a block owns EL elevations of one (pol, freq) for ALL m.  Its 16 waves read the (sign, EW) terms of
 // 16 x 64 / EL m at a time -- lane = (m, el): pieces of 8 EL bytes of the hv / bv rows, each lane 2 x nterm loads in flight --,
 // keep the sums in registers and put the map modes straight into the LDS image of the inverse FFT (two rows per complex
-// sequence, bit-reversed positions, the Hermitian mirror bins written by the odd row's lane); the per-row sums over m
-// never leave the block.  After the in-LDS FFT the RA rows go out as pieces of map[ra][el] and weight[ra][el]:
+// sequence, bit-reversed positions: the even row's modes at the places of the bins m, the odd row's at those of the mirror
+// bins N - m, combined into one sequence once both rows' norms are known); the per-row sums over m never leave the block.  After the in-LDS FFT the RA rows go out as pieces of map[ra][el] and weight[ra][el]:
 // the [pol, el, m] modes and the [pol, el, ra] rows of the three-kernel form (1.34 GB of scratch traffic beside 2.69 GB
 // of input and output at the CHIME-like shape) never reach HBM.
 //   EL = 8 (round 3): 64-byte pieces.  Two blocks of neighbouring elevations share every 128-byte line of the input:
@@ -371,7 +415,8 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, in
   constexpr int kElOut = PARK ? 8 : EL;     // elevations per output pass
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double s_acc[3][kFuThreads / 64][EL];
-  __shared__ double s_nrm[EL], s_wv[EL];
+  __shared__ double s_nrm[EL], s_wv[EL], s_scl[EL], s_isc[EL];
+  __shared__ double s_x2[kFuThreads / 64][2];  // the waves' shares of the norms of the sequences' two rows
   C<double>* buf = reinterpret_cast<C<double>*>(smem);  // [kSeq][P]
   C<double>* twl = buf + (size_t)kSeq * q.P;
   const int N = p.nra, M = q.M, P = q.P;
@@ -435,24 +480,21 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, in
       }
     }
     double ar = 0.0, ai = 0.0, rd;
-    if (m_ok && el_ok) rm_mode(p, sw, mre, mim, sg, m, f, el, ar, ai, rd, acc_d, acc_q, acc_p);  // (never launched with `skip`)
+    if (m_ok && el_ok) {  // (never launched with `skip`)
+      double x2 = 0.0;  // (the norms of the rows are taken from the image below: an accumulator more in this loop spills)
+      rm_mode(p, sw, mre, mim, sg, m, f, el, ar, ai, rd, acc_d, acc_q, acc_p, x2);
+    }
     const bool edge = m == 0 || 2 * m == N;  // DC and Nyquist bins are real, and their own mirror
-    if (edge) ai = 0.0;
-    // rows 2j (A) and 2j + 1 (B) share a transform: z = X_A + i X_B, loaded conjugated at the bit-reversed position
-    const double orr = __shfl_xor(ar, 1, 64), oi = __shfl_xor(ai, 1, 64);
-    if (m_ok) {
-      const bool odd = eli & 1;
-      const double a_r = odd ? orr : ar, a_i = odd ? oi : ai, b_r = odd ? ar : orr, b_i = odd ? ai : oi;
-      const C<double> lo = {a_r - b_i, -(a_i + b_r)}, hi = {a_r + b_i, a_i - b_r};  // bins m and N - m (= conj(X[m]) of both rows)
-      if (!PARK || eli < 8) {  // straight into the LDS image (bit-reversed positions)
-        C<double>* row = buf + (size_t)(eli >> 1) * P;
-        if (!odd) row[dmm_fft::bitrev(m, q.logM)] = lo;
-        else if (!edge) row[dmm_fft::bitrev(N - m, q.logM)] = hi;
-      } else {  // elevations 8-15: parked in natural order (64-byte pieces per image row), transformed second
-        C<double>* row = pk + (size_t)((eli - 8) >> 1) * N;
-        if (!odd) row[m] = lo;
-        else if (!edge) row[N - m] = hi;
-      }
+    // rows 2j (A) and 2j + 1 (B) share a transform, z = X_A + i X_B.  Their modes are put down side by side first -- A's at
+    // the place of bin m, B's at the place of bin N - m; the real DC / Nyquist pair at the bin's own place -- and made
+    // into z once the rows' scales are known (below)
+    const double orr = __shfl_xor(ar, 1, 64);
+    const bool odd = eli & 1;
+    if (m_ok && !(edge && odd)) {
+      const int mm = odd ? N - m : m;
+      const C<double> v = {ar, edge ? orr : ai};
+      if (!PARK || eli < 8) buf[(size_t)(eli >> 1) * P + dmm_fft::bitrev(mm, q.logM)] = v;  // the LDS image: bit-reversed positions
+      else pk[(size_t)((eli - 8) >> 1) * N + mm] = v;  // elevations 8-15: parked in natural order, transformed second
     }
   }
   // the block's per-row sums over m: the m of a wave by a butterfly, the waves in a fixed order
@@ -481,19 +523,67 @@ __global__ __launch_bounds__(kFuThreads) void k_rm_fused(RmParams p, RmFft q, in
   }
   __syncthreads();
   for (int pass = 0; pass < kPass; ++pass) {
-    if (pass == 1) {  // the parked image of elevations 8-15 comes in (coalesced reads, bit reversal on the LDS side)
+    // the norms of the two rows of every sequence: kFuThreads / kSeq threads per sequence (whole waves), a butterfly per
+    // wave, the waves in a fixed order.  (Measured, CHIME-like shape: this pass and the one after it cost 0.07 ms of 0.85 at
+    // nra = 2048 -- parked form; 0.87 -> 0.95 with 8 elevations -- and 0.04 of 0.39 at nra = 1024.)
+    if (pass == 1) __syncthreads();
+    const int nh = N / 2 + 1;
+    {
+      constexpr int kTs = kFuThreads / kSeq;
+      const int j = threadIdx.x / kTs;
+      const C<double>* src = pass == 1 ? pk + (size_t)j * N : buf + (size_t)j * P;
+      double xa = 0.0, xb = 0.0;
+      for (int m = threadIdx.x - j * kTs; m < nh; m += kTs) {
+        if (m == 0 || 2 * m == N) {
+          const C<double> v = src[pass == 1 ? m : dmm_fft::bitrev(m, q.logM)];
+          xa += v.x * v.x;
+          xb += v.y * v.y;
+        } else {
+          const C<double> a = src[pass == 1 ? m : dmm_fft::bitrev(m, q.logM)], b = src[pass == 1 ? N - m : dmm_fft::bitrev(N - m, q.logM)];
+          xa += 2.0 * (a.x * a.x + a.y * a.y);
+          xb += 2.0 * (b.x * b.x + b.y * b.y);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        xa += __shfl_xor(xa, o, 64);
+        xb += __shfl_xor(xb, o, 64);
+      }
+      if (lane == 0) s_x2[wave][0] = xa, s_x2[wave][1] = xb;
       __syncthreads();
-      for (int idx = threadIdx.x; idx < 4 * N; idx += kFuThreads) {
-        const int j = idx / N, n = idx - j * N;
-        buf[(size_t)j * P + dmm_fft::bitrev(n, q.logM)] = pk[(size_t)j * N + n];
+      if (threadIdx.x < 2 * kSeq) {
+        const int js = threadIdx.x >> 1, ab = threadIdx.x & 1;
+        double x2 = 0.0;
+        for (int w2 = js * (kTs / 64); w2 < (js + 1) * (kTs / 64); ++w2) x2 += s_x2[w2][ab];
+        rm_seq_scale(x2, s_scl[kElOut * pass + threadIdx.x], s_isc[kElOut * pass + threadIdx.x]);
       }
       __syncthreads();
     }
+    // the side-by-side modes of each pair of rows become the conjugated z of its transform, every row times its scale:
+    // in place in the LDS image; from the parked image (coalesced reads, bit reversal on the LDS side) in the second pass
+    for (int idx = threadIdx.x; idx < kSeq * nh; idx += kFuThreads) {
+      const int j = idx / nh, m = idx - j * nh;
+      const double sa = s_scl[kElOut * pass + 2 * j], sb = s_scl[kElOut * pass + 2 * j + 1];
+      C<double>* row = buf + (size_t)j * P;
+      const C<double>* src = pass == 1 ? pk + (size_t)j * N : nullptr;
+      const int slot_a = dmm_fft::bitrev(m, q.logM), slot_b = dmm_fft::bitrev(N - m, q.logM);
+      if (m == 0 || 2 * m == N) {  // (A_r, B_r) -> conj(A_r + i B_r)
+        const C<double> v = pass == 1 ? src[m] : row[slot_a];
+        row[slot_a] = {v.x * sa, -(v.y * sb)};
+      } else {
+        C<double> a = pass == 1 ? src[m] : row[slot_a], b = pass == 1 ? src[N - m] : row[slot_b];
+        a = {a.x * sa, a.y * sa};
+        b = {b.x * sb, b.y * sb};
+        row[slot_a] = {a.x - b.y, -(a.y + b.x)};  // bin m: conj(X_A + i X_B)
+        row[slot_b] = {a.x + b.y, a.y - b.x};     // bin N - m: conj(conj(X_A) + i conj(X_B))
+      }
+    }
+    __syncthreads();
     dmm_fft::fft_dit<double, false, kFuThreads>(buf, twl, kSeq, M, q.logM, P);
     // y = conj(result) / N: even row = Re, odd row = -Im, each times its row's normalisation; pieces of 8 kElOut bytes of [ra][el]
     const int eo = threadIdx.x & (kElOut - 1);
     const int ele = el0 + kElOut * pass + eo;
-    const double sc = s_nrm[kElOut * pass + eo] / (double)N, wv = s_wv[kElOut * pass + eo];
+    const double sc = s_nrm[kElOut * pass + eo] / (double)N * s_isc[kElOut * pass + eo], wv = s_wv[kElOut * pass + eo];
     if (ele < p.nel)
       for (int ra = threadIdx.x / kElOut; ra < N; ra += kFuThreads / kElOut) {
         const C<double> v = buf[(size_t)(eo >> 1) * P + ra];
@@ -546,7 +636,7 @@ RmForm rm_single_pass_form(bool lds16_fits, size_t park_bytes, int variant) {
 }
 
 // window[f, m, el] = sum_i coef_i cos(2 pi i x), x = (m - min_m[f, el]) / (max_m[f, el] - min_m[f, el]), zero outside
-// [0, 1] (window_generalised, reference draco/util/tools.py:547-601, as used at ringmapmaker.py:917-925); float64
+// [0, 1] and wherever max_m <= min_m (window_generalised, reference draco/util/tools.py:547-601, as used at ringmapmaker.py:917-925); float64
 // arithmetic, stored float32 like the reference's `.astype(np.float32)`
 __global__ void k_rm_window(int nfreq, int nm, int nel, const double* __restrict__ min_m, const double* __restrict__ max_m,
                             double c0, double c1, double c2, double c3, float* __restrict__ out) {
@@ -558,7 +648,7 @@ __global__ void k_rm_window(int nfreq, int nm, int nel, const double* __restrict
     const double lo = min_m[(int64_t)f * nel + el], hi = max_m[(int64_t)f * nel + el];
     const double x = ((double)m - lo) / (hi - lo);
     double w = 0.0;
-    if (x >= 0.0 && x <= 1.0) {
+    if (hi > lo && x >= 0.0 && x <= 1.0) {  // (hi < lo: the reference selects lo <= m <= hi first, an empty window)
       const double t = 2.0 * M_PI * x;
       w = c0 + c1 * cos(t) + c2 * cos(2.0 * t) + c3 * cos(3.0 * t);
     }
@@ -644,7 +734,7 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   const int nchunk = (nm + MT - 1) / MT;
   const size_t b_map = (size_t)nrow * nm * sizeof(double2);
   const size_t b_dirty = ((size_t)nrow * nm * sizeof(double) + 255) / 256 * 256;
-  const size_t b_psum = (size_t)npol * nfreq * nchunk * nel * sizeof(double4);
+  const size_t b_psum = ((size_t)npol * nfreq * nchunk * nel * sizeof(RmSums) + 255) / 256 * 256;
   const size_t b_vec = ((size_t)nrow * sizeof(double) + 255) / 256 * 256;
   const size_t b_tmp = (size_t)nrow * nra * sizeof(double);
   void* scratch = nullptr;
@@ -656,7 +746,7 @@ extern "C" int dmm_ringmap_deconvolve(dmm_ctx* ctx, int nm, int nm_beam, int npo
   sp += b_map;
   p.s_dirty = (double*)sp;
   sp += b_dirty;
-  p.psum = (double4*)sp;
+  p.psum = (RmSums*)sp;
   sp += b_psum;
   p.wv = (double*)sp;
   sp += b_vec;

@@ -102,10 +102,12 @@ def regularisation(kind, freq, m, inv_SN=1e-6, gal_amp=1.41, gal_alpha=-1.75, ga
     return invert_no_zero(spectrum[:, np.newaxis, np.newaxis])
 
 
-def deconvolve(kind, hv, hw, bv, freq, el, ew, oddra, exclude_cyl=(), skip_deconvolution=False, window=None, weight_ew="natural", iref=None, **reg):
+def deconvolve(kind, hv, hw, bv, freq, el, ew, oddra, exclude_cyl=(), skip_deconvolution=False, window=None, weight_ew="natural", iref=None, eps=None, **reg):
     """The per-frequency loop of ``DeconvolveHybridMBase.process`` (``ringmapmaker.py:683-823``).
 
     ``window``: None (``window_type == "none"``) or float32 ``[nfreq, nm, nel]`` from :func:`get_window`.
+    ``eps``: None, or the regularisation ``[nfreq, nm]`` handed in directly, as ``dmm_ringmap_deconvolve`` receives it
+    (in place of :func:`regularisation`).
     """
     nm, _, npol, nfreq, new, nel = hv.shape
     mmax = nm - 1
@@ -130,7 +132,8 @@ def deconvolve(kind, hv, hw, bv, freq, el, ew, oddra, exclude_cyl=(), skip_decon
         weight = ew_weight(kind, weight_ew, inv_var, exclude_cyl) * (inv_var > 0.0)
         sum_weight = (weight * np.abs(bvf) ** 2).sum(axis=(1, -2))
         if not skip_deconvolution:
-            C_inv = regularisation(kind, f, m, **reg) + sum_weight
+            reg_f = regularisation(kind, f, m, **reg) if eps is None else np.asarray(eps)[lfi][:, np.newaxis, np.newaxis]
+            C_inv = reg_f + sum_weight
         else:
             C_inv = 1.0
         map_m = winf * (bvf.conj() * weight * hvf).sum(axis=(1, -2)) * invert_no_zero(C_inv)

@@ -62,7 +62,7 @@ def test_reference_golden(golden_dir):
         assert isinstance(rm, containers.RingMap)
         # the reference forms |b|^2 (np.abs of complex64) and, with inverse-variance weights, the whole
         # product in float32: agreement with the float64 kernel is single precision; the float64 oracle
-        # comparison below is the tight one
+        # comparison below is tighter, and test_gpu_ringmap_direct.py holds the kernels to a long-double truth
         tol = 5e-6
         for ds, name in ((rm.map, "map"), (rm.weight, "wgt"), (rm.dirty_beam_power, "dbp"), (rm.dirty_beam, "db")):
             ref = g[f"c{i}_{name}"]
